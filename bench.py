@@ -13,10 +13,15 @@ exchange is the all-gather of the R x N scoring-function values before a replica
 (reference utils/replica_exchange_monte_carlo.py:113-173), issued every --exchange-every steps as in
 the reference's e=100 Monte-Carlo iterations per exchange step, and once after the last step.
 
-Prints ONE JSON line (rank 0).  'roofline' prices the dominant kernel against the HARDWARE peaks only (HBM bytes, LDS-array
-cycles, VALU issue at the SIMD-32 pipe rate) and reports the kernel's own finalize-only floor separately (see
-roofline_block); 'cpu_baseline' times the CPU oracle (a port of the ViennaRNA recursions; ViennaRNA itself is not on this
-box) on the same workload and its results are compared with the GPU's.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and reports them (value, ms_per_step,
+kernel_ms).  --full adds what takes work or runs of its own beyond that: 'roofline' prices the dominant kernel against the
+HARDWARE peaks only (HBM bytes, LDS-array cycles, VALU issue at the SIMD-32 pipe rate) and reports the kernel's own
+finalize-only floor separately (see roofline_block); 'cpu_baseline' times the CPU oracle (a port of the ViennaRNA recursions;
+the project does not depend on ViennaRNA) on the same workload and its results are compared with the GPU's ('parity');
+'mc_loop' times the reference's Monte-Carlo loop and 'r_sweep' other batch sizes.
+
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs); the inputs are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import csv
@@ -381,6 +386,23 @@ def oracle_reference(seqs, target):
     return orc.score_batch(list(seqs), [target], pyoracle.FLAG_PF | pyoracle.FLAG_MFE, threads=cores)
 
 
+def dump_outputs(dirname, Epf, Emfe, ss, Ed, L, suffix="", limit=64 << 20):
+    """--dump-outputs: what a caller of the timed path receives for the batch, as DIR/<name>.npy: Epf, Emfe and Ed (E(target),
+    10 cal/mol units) one float64 per replica, mfe_ss the MFE structure's characters as float32 codes, replicas x L.  A batch
+    larger than `limit` bytes in all is cut to a fixed, seeded sample of replicas whose indices go to rows.npy."""
+    R = Epf.shape[0]
+    arrays = {"Epf": Epf.astype(np.float64), "Emfe": Emfe.astype(np.float64), "Ed": Ed.astype(np.float64),
+              "mfe_ss": ss.reshape(R, L).astype(np.float32)}
+    keep = max(1, limit // (3 * 8 + 4 * L + 8))
+    if R > keep:
+        rows = np.sort(np.random.default_rng(20260101).choice(R, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -392,11 +414,16 @@ def main():
     ap.add_argument("--target", default="eteV1_69.txt", help="Eterna100-V1 target giving L (69: L=200, 92: L=100, 53: L=400)")
     ap.add_argument("--exchange-every", type=int, default=100)
     ap.add_argument("--seqs", choices=["uniform", "design"], default="uniform")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the CPU baseline and parity against the oracle, mc_loop and r_sweep (the --no-* options leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-mc-loop", action="store_true", help="skip the end-to-end Monte-Carlo loop figure (mc_loop)")
     ap.add_argument("--r-sweep", action="store_true", help="(default at N = 1 since round 4; kept for old command lines)")
     ap.add_argument("--no-r-sweep", action="store_true", help="skip the replicas-per-call sweep (32 / 64 / 128 / 256) of the N = 1 line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))        # before torch / HIP are touched in this process
     if os.environ.get("DRNA_BENCH_ECHO_RANK"):           # tests/test_host_cpu.py: what a rank was started with, no GPU needed
@@ -539,10 +566,13 @@ def main():
     ts = eng.timing_sums()
     for key in tk:
         tk[key] = ts[key] / max(1, ts["calls"])
+    if args.dump_outputs:
+        # every rank its own replicas; at N > 1 under <name>_rank<k>.npy, each within its share of the 64 MB
+        dump_outputs(args.dump_outputs, d_Epf.cpu().numpy(), d_Emfe.cpu().numpy(), d_ss.cpu().numpy(), d_Ed.cpu().numpy(), L,
+                     suffix="_rank%d" % rank if world > 1 else "", limit=(64 << 20) // world)
 
     if rank == 0:
         folds = R_total * args.steps
-        dom = "pf" if tk["pf"] >= tk["mfe"] else "mfe"
         fused = bool(eng.get_option("last_fused"))
         out = {
             "metric": "replica-folds/sec (MFE+PF, L=%d, R=%d)" % (L, args.replicas),
@@ -558,13 +588,14 @@ def main():
                        "threads_per_workgroup": eng.info()["threads_per_wg"],
                        "launches_per_step": 1 if fused else 2},
             "kernel_ms": {k: round(v, 4) for k, v in tk.items()},
-            # (one launch for both folds: the kernel whose counters the inputs hold is that launch, its duration the step's device time)
-            "roofline": roofline_block(dom, tk["total"] if fused else tk[dom], L, R, tk, fused),
         }
-        rb = out["roofline"]
-        hb = rb.get("step_hbm")
-        out["achieved_hbm_GB_s"] = hb["GB_per_s"] if hb else None          # BASELINE metric: "HBM GB/s vs peak" (8000): both folds of a step
-        out["achieved_hbm_frac_of_peak"] = hb["frac_of_peak"] if hb else None
+        if args.full:
+            dom = "pf" if tk["pf"] >= tk["mfe"] else "mfe"
+            # (one launch for both folds: the kernel whose counters the inputs hold is that launch, its duration the step's device time)
+            out["roofline"] = roofline_block(dom, tk["total"] if fused else tk[dom], L, R, tk, fused)
+            hb = out["roofline"].get("step_hbm")
+            out["achieved_hbm_GB_s"] = hb["GB_per_s"] if hb else None          # BASELINE metric: "HBM GB/s vs peak" (8000): both folds of a step
+            out["achieved_hbm_frac_of_peak"] = hb["frac_of_peak"] if hb else None
         out["sync_fallbacks"] = eng.get_option("sync_fallbacks")          # calls redone with one workgroup per fold (lost partner)
         out["cus_occupied"] = {"workgroups": eng.get_option("last_workgroups"), "compute_units": eng.info()["compute_units"],
                                # folds by several workgroups: every launch is sized against the occupancy query (engine.hip, pair_blocks_per_cu)
@@ -583,11 +614,11 @@ def main():
                                           "stays flat as N grows and value does not scale; the weak mode (R per GPU) is the throughput mode"
                                           % (L - 4, tk["total"], R, args.replicas))
         ref = None
-        if not args.no_cpu_baseline and world == 1:      # the timed CPU baseline on rank 0 at N=1 only: at N>1 the other ranks would idle at the barrier
+        if args.full and not args.no_cpu_baseline and world == 1:   # the timed CPU baseline on rank 0 at N=1 only: at N>1 the other ranks would idle at the barrier
             out["cpu_baseline"], ref = cpu_baseline(seqs, target)
             out["speedup_vs_cpu_usable_cores"] = out["value"] / world / out["cpu_baseline"]["value"]
             out["speedup_vs_cpu_reference_style_R_processes"] = out["value"] / world / out["cpu_baseline"]["reference_style_R_processes"]["value"]
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             ref = oracle_reference(seqs, target)          # N > 1: rank 0's shard against the oracle (tens of ms of CPU), no timing
         if ref is not None:
             # what the timed steps left in the device buffers against the oracle's answers for the same batch:
@@ -604,9 +635,9 @@ def main():
             if not ok:
                 print(json.dumps(out))
                 raise SystemExit("bench: GPU results differ from the oracle")
-        if not args.no_mc_loop and not shared_card:
+        if args.full and not args.no_mc_loop and not shared_card:
             out["mc_loop"] = mc_loop_block(eng, target, R, args.exchange_every, out["value"] / world, tk["total"])
-        if not args.no_r_sweep and world == 1 and not shared_card:
+        if args.full and not args.no_r_sweep and world == 1 and not shared_card:
             out["r_sweep"] = r_sweep_block(target, local_rank)
         print(json.dumps(out))
     if multi:

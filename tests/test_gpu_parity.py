@@ -940,7 +940,7 @@ def test_bench_exchange_step_over_rccl_single_rank():
 
 
 def test_bench_line_carries_parity_roofline_baseline_and_the_monte_carlo_loop():
-    """The driver's own run in small: `bench.py --steps 3 --warmup 1` WITH the CPU baseline must end in one JSON line whose
+    """The driver's own run in small: `bench.py --full --steps 3 --warmup 1` WITH the CPU baseline must end in one JSON line whose
     timed device buffers were checked against the oracle (parity_checked), with the roofline of the dominant kernel, the CPU
     baseline beside it, and the end-to-end Monte-Carlo loop figure (reference utils/replica_exchange_monte_carlo.py:176-210)."""
     import json, os, subprocess, sys
@@ -948,7 +948,7 @@ def test_bench_line_carries_parity_roofline_baseline_and_the_monte_carlo_loop():
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "DRNA_BENCH_BACKEND", "DRNA_BENCH_FORCE_DIST"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--exchange-every", "20"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--exchange-every", "20"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
@@ -966,6 +966,35 @@ def test_bench_line_carries_parity_roofline_baseline_and_the_monte_carlo_loop():
     rs = {x["R"]: x for x in d["r_sweep"]}                     # replicas per call: more folds per call must not cost throughput
     assert sorted(rs) == [32, 64, 128, 256] and all(x["sync_fallbacks"] == 0 for x in rs.values())
     assert rs[128]["replica_folds_per_s"] > rs[64]["replica_folds_per_s"] and rs[256]["replica_folds_per_s"] > 0.95 * rs[128]["replica_folds_per_s"]
+
+
+def test_bench_plain_line_and_dumped_outputs(oracle, eterna_targets, tmp_path):
+    """A plain `bench.py --steps 2 --warmup 1 --dump-outputs DIR`: the headline fields only (nothing of --full), and the last timed
+    step's outputs in DIR, which are the oracle's answers for the benchmark's seeded batch (R = 64 uniform-random sequences, L = 200)."""
+    import json, os, subprocess, sys
+    from oracle import pyoracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "DRNA_BENCH_BACKEND", "DRNA_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "replica-folds/s" and d["metric"] and d["dtype"]
+    assert not {"roofline", "cpu_baseline", "parity", "mc_loop", "r_sweep"} & set(d)
+    target = eterna_targets["eteV1_69.txt"]
+    L = len(target)
+    rng = np.random.default_rng(20260101)                     # bench.py's batch at N = 1
+    seqs = ["".join(rng.choice(list("ACGU"), L)) for _ in range(64)]
+    r_Epf, r_Emfe, r_ss, r_Ed = oracle.score_batch(seqs, [target], pyoracle.FLAG_PF | pyoracle.FLAG_MFE)
+    got = {n: np.load(tmp_path / (n + ".npy")) for n in ("Epf", "Emfe", "Ed", "mfe_ss")}
+    assert sorted(os.listdir(tmp_path)) == ["Ed.npy", "Emfe.npy", "Epf.npy", "mfe_ss.npy"]
+    assert all(got[n].dtype == np.float64 and got[n].shape == (64,) for n in ("Epf", "Emfe", "Ed"))
+    assert got["mfe_ss"].dtype == np.float32 and got["mfe_ss"].shape == (64, L)
+    assert (got["Emfe"] == r_Emfe).all() and (got["Ed"] == r_Ed[:, 0]).all() and np.abs(got["Epf"] - r_Epf).max() < EPF_TOL_ORACLE
+    assert ["".join(map(chr, row.astype(np.uint8))) for row in got["mfe_ss"]] == r_ss
 
 
 def test_one_launch_form_equals_the_two_launches(eng400, oracle, eterna_targets):

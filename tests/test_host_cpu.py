@@ -10,11 +10,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_blob_matches_reference_file_when_present(blob):
-    ref = "/root/reference/rna_turner1999.par"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present on this box")
+    # the reference's rna_turner1999.par (ViennaRNA's Turner-1999 parameter file), stored gzipped with the goldens
+    import gzip
     from desirna_amd import params
-    assert (params.load_par_file(ref) == blob).all()
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "rna_turner1999.par.gz"), "rt") as fh:
+        assert (params.build_blob(params.parse_par_text(fh.read())) == blob).all()
 
 
 def test_blob_spot_values(blob):
@@ -134,6 +134,29 @@ def test_bench_strong_scaling_shards(tmp_path):
     assert [g["local_replicas"] for g in got] == [22, 21, 21] and all(g["scaling"] == "strong" for g in got)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and json.loads(r.stdout.strip().splitlines()[-1])["local_replicas"] == 64      # weak: --replicas per GPU
+
+
+def test_bench_dump_outputs_formats_and_seeded_sample(tmp_path):
+    """--dump-outputs writes float32 / float64 arrays; a batch over the size limit is cut to the same seeded sample of replicas
+    every time, its indices in rows.npy."""
+    import bench
+    R, L = 50, 12
+    rng = np.random.default_rng(7)
+    Epf, Emfe, Ed = rng.normal(size=R), rng.integers(-900, 0, R).astype(np.int32), rng.integers(-900, 0, R).astype(np.int32)
+    ss = rng.choice(np.frombuffer(b"().", dtype=np.uint8), R * L)
+    bench.dump_outputs(str(tmp_path / "all"), Epf, Emfe, ss, Ed, L)
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in ("Epf", "Emfe", "Ed", "mfe_ss")}
+    assert sorted(os.listdir(tmp_path / "all")) == ["Ed.npy", "Emfe.npy", "Epf.npy", "mfe_ss.npy"]
+    assert (got["Epf"] == Epf).all() and (got["Emfe"] == Emfe).all() and (got["Ed"] == Ed).all() and got["Emfe"].dtype == np.float64
+    assert got["mfe_ss"].dtype == np.float32 and (got["mfe_ss"] == ss.reshape(R, L)).all()
+    limit = 20 * (3 * 8 + 4 * L + 8)                                     # room for 20 replicas
+    for k in (1, 2):
+        bench.dump_outputs(str(tmp_path / ("cut%d" % k)), Epf, Emfe, ss, Ed, L, limit=limit)
+    rows = np.load(tmp_path / "cut1" / "rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 20 and (np.diff(rows) > 0).all()
+    assert (np.load(tmp_path / "cut2" / "rows.npy") == rows).all()
+    assert (np.load(tmp_path / "cut1" / "mfe_ss.npy") == ss.reshape(R, L)[rows.astype(int)]).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "cut1").iterdir()) <= limit + 5 * 128      # + the .npy headers
 
 
 def test_tile_product_schedule_never_reads_an_unfinished_operand():

@@ -14,14 +14,14 @@ REPO="$GRAFT_REPO_ROOT"
 O=gpurun_out/r4
 if has tests; then echo "== pytest gpu"; timeout -k 10 900 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log; fi
 if has bench; then
-  echo "== bench"; timeout -k 10 400 python bench.py --steps $STEPS --warmup 5 > $O/bench_uniform.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+  echo "== bench"; timeout -k 10 400 python bench.py --full --steps $STEPS --warmup 5 > $O/bench_uniform.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
   cat $O/bench_uniform.json
-  timeout -k 10 200 python bench.py --steps $STEPS --warmup 5 --seqs design --no-cpu-baseline --no-r-sweep > $O/bench_design.json 2>/dev/null || exit 1
-  DRNA_PF_HELPER=0 timeout -k 10 200 python bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --no-r-sweep > $O/bench_nohelper.json 2>/dev/null || exit 1
-  DRNA_FUSED=0 timeout -k 10 200 python bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --no-r-sweep > $O/bench_two_launches.json 2>/dev/null || exit 1
-  DRNA_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 20 --warmup 3 > $O/bench_gloo2_rehearsal.json 2> $O/bench_gloo2.err || { tail -5 $O/bench_gloo2.err; }
-  DRNA_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --scaling strong --steps 20 --warmup 3 > $O/bench_gloo2_strong_rehearsal.json 2> $O/bench_gloo2_strong.err || { tail -5 $O/bench_gloo2_strong.err; }
-  timeout -k 10 300 python bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --no-mc-loop --r-sweep > $O/bench_rsweep.json 2>/dev/null || exit 1
+  timeout -k 10 200 python bench.py --full --steps $STEPS --warmup 5 --seqs design --no-cpu-baseline --no-r-sweep > $O/bench_design.json 2>/dev/null || exit 1
+  DRNA_PF_HELPER=0 timeout -k 10 200 python bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline --no-r-sweep > $O/bench_nohelper.json 2>/dev/null || exit 1
+  DRNA_FUSED=0 timeout -k 10 200 python bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline --no-r-sweep > $O/bench_two_launches.json 2>/dev/null || exit 1
+  DRNA_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 20 --warmup 3 > $O/bench_gloo2_rehearsal.json 2> $O/bench_gloo2.err || { tail -5 $O/bench_gloo2.err; }
+  DRNA_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --scaling strong --steps 20 --warmup 3 > $O/bench_gloo2_strong_rehearsal.json 2> $O/bench_gloo2_strong.err || { tail -5 $O/bench_gloo2_strong.err; }
+  timeout -k 10 300 python bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline --no-mc-loop --r-sweep > $O/bench_rsweep.json 2>/dev/null || exit 1
   python3 -c "
 import json
 for f in ('bench_uniform','bench_design','bench_nohelper','bench_two_launches','bench_gloo2_rehearsal','bench_gloo2_strong_rehearsal','bench_rsweep'):
