@@ -40,8 +40,7 @@ static std::string g_create_error;
 #endif
 constexpr int MFE_FARK_MIN_STRIPS = DRNA_MFE_FARK_MIN_STRIPS;   // (measured: tools/time_strip_variants.py)
 struct drna_engine {
-  int device = 0, max_R = 0, max_L = 0, nt = 1024, cus = 0;
-  bool lds_path = true;   // LDS-resident kernels when n fits (DRNA_PATH=global forces the general path)
+  int device = 0, max_R = 0, max_L = 0, cus = 0;
   HostTables H;
   MfeTables* d_mfeT = nullptr;
   PfTables* d_pfT = nullptr;
@@ -53,7 +52,7 @@ struct drna_engine {
   size_t ws_bytes = 0;
   int ws_slots = 0;               // sequences the fold workspaces hold at once: max_R, or fewer under the workspace budget (DRNA_WS_GB,
                                   // default 8): larger batches are folded in chunks of ws_slots, back to back on the same streams
-  // staging for the host-buffer entry point
+  // device copies of the sequences and results of the ragged, ensemble-defect, second-best and co-fold entry points
   char* d_seqs = nullptr;
   double* d_Epf = nullptr;
   int32_t* d_Emfe = nullptr;
@@ -94,7 +93,6 @@ struct drna_engine {
   double *hm_Epf = nullptr, *dm_Epf = nullptr;
   int32_t *hm_Emfe = nullptr, *dm_Emfe = nullptr, *hm_Ed = nullptr, *dm_Ed = nullptr;
   size_t hm_Ed_cap = 0;
-  bool zero_copy = true;
   // two-workgroup kernels (small batches: 4 R <= CUs, n <= 200): exchange rows and flags, allocated on first use
   bool dual = true;               // DRNA_DUAL=0 turns them off
   bool dual_force = false;        // option "dual" = 2: also beside a partition function (tests, diagnostics)
@@ -130,8 +128,6 @@ struct drna_engine {
   // for the next SOLO_CALLS calls (option "solo_calls_left"); then one call probes again.  Any set_option of the paths resets it.
   int fallback_streak = 0, solo_left = 0;
   bool in_fallback = false;
-  int mc_threads_used = 0;        // worker threads (the caller included) of the last drna_mc_run
-  int mc_threads = 0;             // option "mc_threads" / DRNA_MC_THREADS: worker threads of drna_mc_run's host work (0 = min(8, usable CPUs / 2))
   int* d_sflags = nullptr;        // [2: partition function, MFE][max_R][STRIP_MAXS][32]
   int32_t* d_srec = nullptr;      // MFE strips: exchange records and list counts, srec_stride int32 per sequence
   long long srec_stride = 0;
@@ -160,6 +156,32 @@ static hipError_t upload(T** dst, const T* src, size_t count) {
 }
 
 static size_t mfe_ws_stride(int ld) { return (size_t)5 * ld * ld; }                       // int32
+static size_t pf_ws_stride(int ld) { return (size_t)7 * ld * ld + ((size_t)ld * ld + 7) / 8; }  // doubles
+
+// kernel arguments of a batch of sequences seqs (L = 0 for a ragged batch) with tables of pitch ld in the engine's workspaces;
+// call sites add what is their own (ragged descriptors, workspace offset of a chunk, helper flags, q5out, the strands' cut)
+static MfeArgs mfe_args(const drna_engine* e, const char* seqs, int L, int ld, int pk_rounds, int32_t* Emfe, char* ss) {
+  MfeArgs a;
+  a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = seqs; a.L = L; a.ld = ld;
+  a.pk_rounds = pk_rounds;
+  a.ws = e->d_ws_mfe; a.ws_stride = (long long)mfe_ws_stride(ld);
+  a.Emfe = Emfe; a.ss = ss; a.status = e->d_status;
+  return a;
+}
+static PfArgs pf_args(const drna_engine* e, const char* seqs, int L, int ld, double* Epf) {
+  PfArgs a;
+  a.T = e->d_pfT; a.plan = e->d_plan; a.hp_w = e->d_hp_w; a.scale = e->d_scale; a.eMLb = e->d_eMLb;
+  a.seqs = seqs; a.L = L; a.ld = ld;
+  a.ws = e->d_ws_pf; a.ws_stride = (long long)pf_ws_stride(ld);
+  a.Epf = Epf; a.status = e->d_status + e->max_R;
+  return a;
+}
+static EvalArgs eval_args(const drna_engine* e, const char* seqs, int L, int32_t* Ed) {
+  EvalArgs a{};
+  a.T = e->d_mfeT; a.hp_len = e->d_hp_len; a.bulge_len = e->d_bulge_len; a.int_len = e->d_int_len;
+  a.seqs = seqs; a.pt = e->d_pt; a.L = L; a.n_targets = e->n_targets; a.Ed = Ed;
+  return a;
+}
 // hand-over flags hold (epoch << 12 | diagonal) for the strips and ((epoch * 8 + round) << 10 | diagonal) for the two-workgroup
 // kernel, compared wrap-safe: valid while live values are less than 2^31 apart, i.e. 2^19 (2^18) epochs.  Reset at a quarter of that.
 constexpr int STRIP_EPOCH_RESET = 1 << 17, DUAL_EPOCH_RESET = 1 << 16;
@@ -172,7 +194,7 @@ constexpr int PF_HELPER_NMIN = DRNA_PF_HELPER_NMIN;       // shorter sequences h
 // strips of a sequence of length n (0 = not a strip case): widest strip STRIP_WMAX columns; the exchange records of the
 // S - 1 strip boundaries must fit tables 0 and 1 of the sequence's workspace
 static int strips_for(const drna_engine* e, int n, int ld) {
-  if (!e->strips || !e->lds_path || e->nt != 1024 || n > STRIP_NMAX) return 0;
+  if (!e->strips || n > STRIP_NMAX) return 0;
   int S = 0;
   if (n > PF_FAST_NMAX) S = strip_count(n, STRIP_WMAX);
   else if (e->strips == 2 && n > 64) S = 2;
@@ -257,7 +279,6 @@ static void launch_mfe_strips(drna_engine* e, const MfeArgs& a, int nseq, int S,
   if (e->d_sdbg) fprintf(stderr, "mfe strips: rec %p stride %lld max_R %d nseq %d S %d ld %d L %d ws %p\n", (void*)e->d_srec, e->srec_stride, e->max_R, nseq, S, a.ld, a.L, (void*)a.ws);
   for (int round = 0; round <= a.pk_rounds; round++) launch_mfe_strips_round(e, a, nseq, S, first_slot, idx, 0, st, round);
 }
-static size_t pf_ws_stride(int ld) { return (size_t)7 * ld * ld + ((size_t)ld * ld + 7) / 8; }  // doubles
 
 static int create_impl(drna_engine* e, const int32_t* params, int n_int32, int device, int max_R, int max_L) {
   if (!params || max_R < 1 || max_L < 1 || max_L > MAXN - 2) {
@@ -268,11 +289,6 @@ static int create_impl(drna_engine* e, const int32_t* params, int n_int32, int d
   if (!msg.empty()) { e->err = msg; return DRNA_ERR_PARAMS; }
   size_tables(e->H, max_L + 2);
   e->device = device; e->max_R = max_R; e->max_L = max_L;
-  if (const char* s = getenv("DRNA_NT")) {
-    int v = atoi(s);
-    if (v == 256 || v == 512 || v == 1024) e->nt = v;
-  }
-  if (const char* s = getenv("DRNA_PATH")) e->lds_path = std::string(s) != "global";
   HIP_TRY(hipSetDevice(device));
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -282,7 +298,6 @@ static int create_impl(drna_engine* e, const int32_t* params, int n_int32, int d
   if (const char* fv = getenv("DRNA_FUSED")) e->fused = atoi(fv) != 0;
   if (const char* mv = getenv("DRNA_MFE_SPLIT")) { const int v = atoi(mv); e->mfe_split = v < 1 ? 1 : v > 8 ? 8 : v; }
   if (const char* fv = getenv("DRNA_MFE_FARK_MIN_STRIPS")) { const int v = atoi(fv); e->mfe_fark_min_strips = v < 1 ? 1 : v; }
-  if (const char* tv = getenv("DRNA_MC_THREADS")) { const int v = atoi(tv); e->mc_threads = v < 0 ? 0 : v > 64 ? 64 : v; }
   if (const char* sv = getenv("DRNA_STRIPS")) { const int v = atoi(sv); e->strips = v < 0 ? 0 : v > 2 ? 2 : v; }
   HIP_TRY(upload(&e->d_mfeT, &e->H.mfe, 1));
   HIP_TRY(upload(&e->d_pfT, &e->H.pf, 1));
@@ -314,7 +329,6 @@ static int create_impl(drna_engine* e, const int32_t* params, int n_int32, int d
   HIP_TRY(hipHostMalloc((void**)&e->h_status, (size_t)2 * max_R * sizeof(int32_t), hipHostMallocMapped));
   HIP_TRY(hipHostGetDevicePointer((void**)&e->d_status, e->h_status, 0));
   memset(e->h_status, 0, (size_t)2 * max_R * sizeof(int32_t));
-  if (const char* z = getenv("DRNA_STAGING")) e->zero_copy = std::string(z) != "device";
   HIP_TRY(hipHostMalloc((void**)&e->hm_seqs, (size_t)max_R * max_L, hipHostMallocMapped));
   HIP_TRY(hipHostMalloc((void**)&e->hm_ss, (size_t)max_R * max_L, hipHostMallocMapped));
   HIP_TRY(hipHostMalloc((void**)&e->hm_Epf, (size_t)max_R * sizeof(double), hipHostMallocMapped));
@@ -382,7 +396,6 @@ extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!strcmp(name, "helper_fault")) { e->helper_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "strip_fault")) { e->strip_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "mfe_fark_min_strips")) { e->mfe_fark_min_strips = value < 1 ? 1 : value; return DRNA_OK; }
-  if (!strcmp(name, "mc_threads")) { e->mc_threads = value < 0 ? 0 : value > 64 ? 64 : value; return DRNA_OK; }
   if (!strcmp(name, "mfe_split")) { e->mfe_split = value < 1 ? 1 : value > 8 ? 8 : value; return DRNA_OK; }
   if (!strcmp(name, "debug_epoch")) { e->strip_epoch = value; e->dual_epoch = value; e->pfh_epoch = value; return DRNA_OK; }     // tests: jump near the reset point
   e->err = std::string("drna_set_option: unknown option ") + name;
@@ -410,8 +423,7 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "sync_fallbacks")) { *value = e->sync_fallbacks; return DRNA_OK; }
   if (!strcmp(name, "solo_calls_left")) { *value = e->solo_left; return DRNA_OK; }
   if (!strcmp(name, "last_workgroups")) { *value = e->last_wgs; return DRNA_OK; }
-  if (!strcmp(name, "mc_threads")) { *value = e->mc_threads; return DRNA_OK; }
-  if (!strcmp(name, "mc_threads_used")) { *value = e->mc_threads_used; return DRNA_OK; }
+  if (!strcmp(name, "mc_threads_used")) { *value = 1; return DRNA_OK; }       // drna_mc_run's host work runs on the calling thread
   if (!strcmp(name, "workspace_slots")) { *value = e->ws_slots; return DRNA_OK; }
   if (!strcmp(name, "flag_resets")) { *value = e->flag_resets; return DRNA_OK; }
   if (!strcmp(name, "debug_epoch")) { *value = std::max(e->pfh_epoch, std::max(e->strip_epoch, e->dual_epoch)); return DRNA_OK; }
@@ -420,6 +432,22 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
 
 extern "C" const char* drna_last_error(const drna_engine* e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 
+// pair table p[1..L] (partner or 0, p zeroed by the caller) of the target structure s[0..L): only '(' and ')' pair, every other
+// character is unpaired
+static int target_pairs(drna_engine* e, const char* who, const char* s, int L, short* p) {
+  std::vector<int> stk;
+  for (int i = 1; i <= L; i++) {
+    if (s[i - 1] == '(') stk.push_back(i);
+    else if (s[i - 1] == ')') {
+      if (stk.empty()) { e->err = std::string(who) + ": unbalanced ')'"; return DRNA_ERR_STRUCTURE; }
+      const int o = stk.back(); stk.pop_back();
+      p[o] = (short)i; p[i] = (short)o;
+    }
+  }
+  if (!stk.empty()) { e->err = std::string(who) + ": unbalanced '('"; return DRNA_ERR_STRUCTURE; }
+  return DRNA_OK;
+}
+
 extern "C" int drna_set_targets(drna_engine* e, int n_targets, int L, const char* targets) {
   if (!e) return DRNA_ERR_ARG;
   if (n_targets < 0 || L < 1 || L > e->max_L || (n_targets > 0 && !targets)) {
@@ -427,20 +455,9 @@ extern "C" int drna_set_targets(drna_engine* e, int n_targets, int L, const char
     return DRNA_ERR_ARG;
   }
   std::vector<short> pt((size_t)n_targets * (L + 2), 0);
-  std::vector<int> stk;
   for (int k = 0; k < n_targets; k++) {
-    stk.clear();
-    const char* s = targets + (size_t)k * L;
-    short* p = pt.data() + (size_t)k * (L + 2);
-    for (int i = 1; i <= L; i++) {
-      if (s[i - 1] == '(') stk.push_back(i);
-      else if (s[i - 1] == ')') {
-        if (stk.empty()) { e->err = "drna_set_targets: unbalanced ')'"; return DRNA_ERR_STRUCTURE; }
-        int o = stk.back(); stk.pop_back();
-        p[o] = (short)i; p[i] = (short)o;
-      }
-    }
-    if (!stk.empty()) { e->err = "drna_set_targets: unbalanced '('"; return DRNA_ERR_STRUCTURE; }
+    const int rc = target_pairs(e, "drna_set_targets", targets + (size_t)k * L, L, pt.data() + (size_t)k * (L + 2));
+    if (rc != DRNA_OK) return rc;
   }
   HIP_TRY(hipSetDevice(e->device));
   if (e->d_pt) { (void)hipFree(e->d_pt); e->d_pt = nullptr; }
@@ -451,15 +468,6 @@ extern "C" int drna_set_targets(drna_engine* e, int n_targets, int L, const char
     HIP_TRY(hipMalloc((void**)&e->d_Ed, (size_t)e->max_R * n_targets * sizeof(int32_t)));
   }
   return DRNA_OK;
-}
-
-template <int NT>
-static void launch_mfe(const MfeArgs& a, int R, hipStream_t s) {
-  hipLaunchKernelGGL(mfe_kernel<NT>, dim3(R), dim3(NT), 0, s, a);
-}
-template <int NT>
-static void launch_pf(const PfArgs& a, int R, hipStream_t s) {
-  hipLaunchKernelGGL(pf_kernel<NT>, dim3(R), dim3(NT), 0, s, a);
 }
 
 // Folds by several workgroups that wait for each other (fold_mfe_dual.hpp, pf_kfar_helper) need ALL their workgroups resident at
@@ -488,43 +496,56 @@ static bool fused_grid_fits(drna_engine* e, int R) {
   return (long long)fused_grid(R) <= (long long)e->fused_blocks_per_cu * e->cus;
 }
 
-extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char* d_seqs, uint32_t flags, double* d_Epf,
-                                       int32_t* d_Emfe, char* d_mfe_ss, int32_t* d_Ed) {
-  if (!e) return DRNA_ERR_ARG;
+// The status words of the R sequences just folded (MFE fold before partition function) as a return code, with the message in
+// e->err; the first sequence that failed decides.  Position q is the caller's sequence order[q] (ragged batches) or r_base + q.
+// A lost partner of a multi-workgroup fold (ST_SYNC) is DRNA_ERR_INTERNAL and sets *lost: the caller may redo the call by fold_solo
+static int fold_status(drna_engine* e, int R, bool want_mfe, bool want_pf, const int* order, int r_base, const char* internal_msg,
+                       bool* lost = nullptr) {
+  for (int q = 0; q < R; q++) {
+    const int sm = want_mfe ? e->h_status[q] : ST_OK, sp = want_pf ? e->h_status[e->max_R + q] : ST_OK;
+    const int st = sm != ST_OK ? sm : sp;
+    if (st == ST_OK) continue;
+    const int r = order ? order[q] : r_base + q;
+    char buf[192];
+    if (st == ST_BAD_CHAR) snprintf(buf, sizeof buf, "sequence %d holds a character other than A C G U T", r);
+    else if (st == ST_PF_RANGE) snprintf(buf, sizeof buf, "sequence %d: partition function left the fp64 range (pf_scale too small/large)", r);
+    else if (st == ST_SYNC) snprintf(buf, sizeof buf, "sequence %d: the workgroups of the fold lost each other (a wait expired)", r);
+    else snprintf(buf, sizeof buf, "sequence %d: %s", r, internal_msg);
+    e->err = buf;
+    if (lost) *lost = st == ST_SYNC;
+    return st == ST_BAD_CHAR ? DRNA_ERR_SEQUENCE : st == ST_PF_RANGE ? DRNA_ERR_PF_RANGE : DRNA_ERR_INTERNAL;
+  }
+  return DRNA_OK;
+}
+
+// fold() with one workgroup per fold: the strip kernels, the two-workgroup MFE kernel and the partition function's helpers off, so
+// only the general and LDS-resident kernels run, which wait for nobody
+template <class F>
+static int fold_solo(drna_engine* e, F&& fold) {
+  const int s_strips = e->strips;
+  const bool s_dual = e->dual, s_help = e->pf_helper;
+  e->in_fallback = true; e->strips = 0; e->dual = false; e->pf_helper = false;
+  const int rc = fold();
+  e->strips = s_strips; e->dual = s_dual; e->pf_helper = s_help; e->in_fallback = false;
+  return rc;
+}
+// HIP promises no dispatch order: a multi-workgroup fold whose bounded wait expired is not an error of the batch -- the whole
+// call is redone by fold_solo
+template <class F>
+static int redo_solo(drna_engine* e, F&& fold) {
+  const int rc = fold_solo(e, fold);
+  e->sync_fallbacks++;
+  if (++e->fallback_streak >= 3) { e->fallback_streak = 0; e->solo_left = SOLO_CALLS; }
+  return rc;
+}
+
+// one batch that fits the workspaces; its sequences are the caller's r_base, r_base + 1, ...
+static int score_batch_impl(drna_engine* e, int R, int L, const char* d_seqs, uint32_t flags, double* d_Epf, int32_t* d_Emfe,
+                            char* d_mfe_ss, int32_t* d_Ed, int r_base) {
   const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK),
              want_pk = flags & DRNA_NEED_PK, want_ev = flags & DRNA_NEED_EVAL;
-  if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || !d_seqs || (want_pf && !d_Epf) ||
-      (want_mfe && (!d_Emfe || !d_mfe_ss)) || (want_ev && !d_Ed)) {
-    e->err = "drna_score_batch: bad argument (R, L within the engine's limits; output pointers for every requested flag)";
-    return DRNA_ERR_ARG;
-  }
-  if (want_ev && (e->n_targets < 1 || e->L_targets != L)) {
-    e->err = "drna_score_batch: DRNA_NEED_EVAL needs drna_set_targets() with the same L";
-    return DRNA_ERR_ARG;
-  }
   e->cur_with_pf = want_pf;
-  if (!e->in_fallback && e->solo_left > 0) {             // after repeated lost partners: one workgroup per fold for a while
-    const int s_strips = e->strips;
-    const bool s_dual = e->dual, s_help = e->pf_helper;
-    e->in_fallback = true; e->strips = 0; e->dual = false; e->pf_helper = false;
-    const int rc = drna_score_batch_device(e, R, L, d_seqs, flags, d_Epf, d_Emfe, d_mfe_ss, d_Ed);
-    e->strips = s_strips; e->dual = s_dual; e->pf_helper = s_help; e->in_fallback = false;
-    e->solo_left--;
-    return rc;
-  }
   HIP_TRY(hipSetDevice(e->device));
-  if (R > e->ws_slots) {
-    // more sequences than the workspaces hold (DRNA_WS_GB): one sub-batch of ws_slots after the other
-    const int nt = std::max(1, e->n_targets);
-    for (int r0 = 0; r0 < R; r0 += e->ws_slots) {
-      const int m = std::min(e->ws_slots, R - r0);
-      const int rc = drna_score_batch_device(e, m, L, d_seqs + (size_t)r0 * L, flags, d_Epf ? d_Epf + r0 : nullptr,
-                                             d_Emfe ? d_Emfe + r0 : nullptr, d_mfe_ss ? d_mfe_ss + (size_t)r0 * L : nullptr,
-                                             d_Ed ? d_Ed + (size_t)r0 * nt : nullptr);
-      if (rc != DRNA_OK) return rc;
-    }
-    return DRNA_OK;
-  }
   const int ld = L + 2;
   for (int k = 0; k < 2 * e->max_R; k++) e->h_status[k] = ST_OK;
   // small batches leave most CUs idle with one workgroup per fold (R = 64: 128 workgroups on 256 CUs): the MFE fold then
@@ -535,8 +556,8 @@ extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char*
   // Shorter sequences do not repay the hand-shake: break-even (tools/dual_lengths.py, R = 64, with a sequence's two workgroups on
   // one XCD) at n = 120 without pseudoknot rounds (n = 130: 0.275 against 0.292 ms, n = 160: 0.336 against 0.383) and at n = 165
   // with them (their re-folds of masked sequences have little for the helper to do).
-  const long long resident = (long long)e->cus * ((e->dual || e->pf_helper) && e->nt == 1024 ? pair_blocks_per_cu(e) : 1);   // workgroups the chip holds at once
-  const bool use_dual = e->dual && e->lds_path && e->nt == 1024 && L <= MFE_FAST_NMAX && L > 2 * TURN + 2 && 4ll * R <= resident &&
+  const long long resident = (long long)e->cus * (e->dual || e->pf_helper ? pair_blocks_per_cu(e) : 1);   // workgroups the chip holds at once
+  const bool use_dual = e->dual && L <= MFE_FAST_NMAX && L > 2 * TURN + 2 && 4ll * R <= resident &&
                         (L >= (want_pk ? 170 : 125) || e->dual_force);
   if (use_dual) {
     if (e->dual_cap < R) {
@@ -570,7 +591,7 @@ extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char*
   // partition function of a small batch: a helper workgroup per sequence on a CU that would idle takes the far multiloop split
   // points (the main workgroup's vector-memory path is what they saturate); needs room for 2 R workgroups beside the MFE fold's
   const int mfe_wgs = want_mfe ? (use_dual ? 2 * R : mfe_strips ? R * mfe_strips : R) : 0;
-  const bool pf_help = want_pf && e->pf_helper && !pf_strips && e->lds_path && e->nt == 1024 && L <= PF_FAST_NMAX && L >= PF_HELPER_NMIN &&
+  const bool pf_help = want_pf && e->pf_helper && !pf_strips && L <= PF_FAST_NMAX && L >= PF_HELPER_NMIN &&
                        2ll * R + mfe_wgs <= resident;
   if (pf_help) {
     if (e->pflags_cap < R) {
@@ -595,12 +616,13 @@ extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char*
   // previous call is enqueued first
   // with a helper workgroup per sequence, E(targets) is evaluated by the helpers inside the partition-function launch
   const bool ev_in_pf = want_ev && pf_help;
-  auto make_eval_args = [&]() {
-    EvalArgs a{};
-    a.T = e->d_mfeT; a.hp_len = e->d_hp_len; a.bulge_len = e->d_bulge_len; a.int_len = e->d_int_len;
-    a.seqs = d_seqs; a.pt = e->d_pt; a.L = L; a.n_targets = e->n_targets; a.Ed = d_Ed;
-    return a;
-  };
+  const EvalArgs ev = want_ev ? eval_args(e, d_seqs, L, d_Ed) : EvalArgs{};
+  MfeArgs ma = mfe_args(e, d_seqs, L, ld, want_pk ? 3 : 0, d_Emfe, d_mfe_ss);
+  PfArgs pa = pf_args(e, d_seqs, L, ld, d_Epf);
+  if (pf_help) { pa.helper = e->helper_fault ? 2 : 1; pa.hflags = e->d_pflags; pa.hbase = (int)((unsigned)e->pfh_epoch << 12); }
+  DualLink lk;
+  lk.flagA = e->d_dflags; lk.flagB = e->d_dflags;
+  lk.xs = e->d_xs; lk.xa = e->d_xa_mfe; lk.xb = e->d_xb_mfe; lk.epoch = e->dual_epoch;
   // An MFE fold with pseudoknot rounds on the strip path is a chain of launches whose later links are sparse (only sequences that
   // found a pair fold again), the partition function is one dense launch.  On a chip the first fill already fills (R x strips >=
   // CUs) the partition function is therefore started when the last-but-one round has been queued: it runs beside the sparse rounds
@@ -610,74 +632,42 @@ extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char*
   int pf_gate_round = -1;
   static const int pf_gate_part = getenv("DRNA_PF_GATE_PART") ? atoi(getenv("DRNA_PF_GATE_PART")) : 0;
   bool pf_gated = false;
-  auto make_pf_args = [&]() {
-    PfArgs a;
-    a.T = e->d_pfT; a.plan = e->d_plan; a.hp_w = e->d_hp_w; a.scale = e->d_scale; a.eMLb = e->d_eMLb;
-    a.seqs = d_seqs; a.L = L; a.ld = ld;
-    a.ws = e->d_ws_pf; a.ws_stride = (long long)pf_ws_stride(ld);
-    a.Epf = d_Epf; a.status = e->d_status + e->max_R;
-    if (pf_help) { a.helper = e->helper_fault ? 2 : 1; a.hflags = e->d_pflags; a.hbase = (int)((unsigned)e->pfh_epoch << 12); }
-    return a;
-  };
   auto enqueue_pf = [&]() -> int {
-    PfArgs a = make_pf_args();
     if (pf_gated) HIP_TRY(hipStreamWaitEvent(e->s_pf, e->ev_gate, 0));
     HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
     e->last_wgs += pf_strips ? R * pf_strips : pf_help ? 2 * R : R;
-    if (pf_strips) launch_pf_strips(e, a, R, pf_strips, 0, nullptr, e->s_pf);
+    if (pf_strips) launch_pf_strips(e, pa, R, pf_strips, 0, nullptr, e->s_pf);
     else if (pf_help)
-      hipLaunchKernelGGL((pf_lds_kernel<1024, false>), dim3(pair_grid(R)), dim3(1024), 0, e->s_pf, a, ev_in_pf ? make_eval_args() : EvalArgs{}, R);
-    else if (e->lds_path && e->nt == 1024 && L <= PF_FAST_NMAX)
-      hipLaunchKernelGGL(pf_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a, EvalArgs{}, R);
-    else if (e->nt == 256) launch_pf<256>(a, R, e->s_pf);
-    else if (e->nt == 512) launch_pf<512>(a, R, e->s_pf);
-    else launch_pf<1024>(a, R, e->s_pf);
+      hipLaunchKernelGGL((pf_lds_kernel<1024, false>), dim3(pair_grid(R)), dim3(1024), 0, e->s_pf, pa, ev_in_pf ? ev : EvalArgs{}, R);
+    else if (L <= PF_FAST_NMAX)
+      hipLaunchKernelGGL(pf_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, pa, EvalArgs{}, R);
+    else hipLaunchKernelGGL(pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, pa);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_p1, e->s_pf));
     return DRNA_OK;
   };
-  auto make_mfe_args = [&]() {
-    MfeArgs a;
-    a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = d_seqs; a.L = L; a.ld = ld;
-    a.pk_rounds = want_pk ? 3 : 0;
-    a.ws = e->d_ws_mfe; a.ws_stride = (long long)mfe_ws_stride(ld);
-    a.Emfe = d_Emfe; a.ss = d_mfe_ss; a.status = e->d_status;
-    return a;
-  };
-  auto make_dual_link = [&]() {
-    DualLink lk;
-    lk.flagA = e->d_dflags; lk.flagB = e->d_dflags;
-    lk.xs = e->d_xs; lk.xa = e->d_xa_mfe; lk.xb = e->d_xb_mfe; lk.epoch = e->dual_epoch;
-    return lk;
-  };
   auto enqueue_mfe = [&]() -> int {
-    MfeArgs a = make_mfe_args();
     HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
     e->last_wgs += use_dual ? 2 * R : mfe_strips ? R * mfe_strips : R;
-    if (use_dual) {
-      DualLink lk = make_dual_link();
-      hipLaunchKernelGGL(mfe_dual_kernel<1024>, dim3(pair_grid(R)), dim3(1024), 0, e->s_mfe, a, lk, R);
-    } else if (mfe_strips && a.pk_rounds > 0 && R >= 16 * e->mfe_split && e->mfe_split > 1) {
+    if (use_dual) hipLaunchKernelGGL(mfe_dual_kernel<1024>, dim3(pair_grid(R)), dim3(1024), 0, e->s_mfe, ma, lk, R);
+    else if (mfe_strips && ma.pk_rounds > 0 && R >= 16 * e->mfe_split && e->mfe_split > 1) {
       // every round is a fill launch and a traceback launch (one wave per sequence, ~0.2 ms with the chip idle): the batch goes
       // in parts on two streams, so that one part's traceback runs under another part's fill
       const int np = e->mfe_split, per = ((R + np - 1) / np + 7) / 8 * 8;
-      pf_gate_round = pf_gate_env >= -1 ? pf_gate_env : (pf_strips && R * mfe_strips >= e->cus && a.pk_rounds >= 2) ? a.pk_rounds - 1 : -1;
-      for (int round = 0; round <= a.pk_rounds; round++) {
+      pf_gate_round = pf_gate_env >= -1 ? pf_gate_env : (pf_strips && R * mfe_strips >= e->cus && ma.pk_rounds >= 2) ? ma.pk_rounds - 1 : -1;
+      for (int round = 0; round <= ma.pk_rounds; round++) {
         for (int part = 0, r0 = 0; r0 < R; part++, r0 += per) {
           const bool gate_here = round == pf_gate_round && want_pf && part == pf_gate_part;
-          launch_mfe_strips_round(e, a, std::min(per, R - r0), mfe_strips, r0, nullptr, r0, (part & 1) ? e->s_eval : e->s_mfe, round,
+          launch_mfe_strips_round(e, ma, std::min(per, R - r0), mfe_strips, r0, nullptr, r0, (part & 1) ? e->s_eval : e->s_mfe, round,
                                   gate_here ? e->ev_gate : nullptr);
           if (gate_here) pf_gated = true;
         }
       }
       HIP_TRY(hipEventRecord(e->ev_mfe2, e->s_eval));
       HIP_TRY(hipStreamWaitEvent(e->s_mfe, e->ev_mfe2, 0));
-    } else if (mfe_strips) launch_mfe_strips(e, a, R, mfe_strips, 0, nullptr, e->s_mfe);
-    else if (e->lds_path && e->nt == 1024 && L <= MFE_FAST_NMAX)
-      hipLaunchKernelGGL(mfe_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
-    else if (e->nt == 256) launch_mfe<256>(a, R, e->s_mfe);
-    else if (e->nt == 512) launch_mfe<512>(a, R, e->s_mfe);
-    else launch_mfe<1024>(a, R, e->s_mfe);
+    } else if (mfe_strips) launch_mfe_strips(e, ma, R, mfe_strips, 0, nullptr, e->s_mfe);
+    else if (L <= MFE_FAST_NMAX) hipLaunchKernelGGL(mfe_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, ma);
+    else hipLaunchKernelGGL(mfe_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, ma);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
     return DRNA_OK;
@@ -695,8 +685,7 @@ extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char*
       e->clk_cap = grid;
     }
     HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-    hipLaunchKernelGGL(score_fused_kernel<1024>, dim3(grid), dim3(1024), 0, e->s_mfe, make_mfe_args(), make_dual_link(), make_pf_args(),
-                       want_ev ? make_eval_args() : EvalArgs{}, R, e->d_clk);
+    hipLaunchKernelGGL(score_fused_kernel<1024>, dim3(grid), dim3(1024), 0, e->s_mfe, ma, lk, pa, ev, R, e->d_clk);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
     e->last_wgs = 4 * R;
@@ -718,113 +707,95 @@ extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char*
     }
     e->timing[0] = (float)((end_mfe - t0) * 1e-5); e->timing[1] = (float)((end_pf - t0) * 1e-5);
     e->timing[2] = 0.f; e->timing[3] = tot;
-    for (int k = 0; k < 4; k++) e->timing_sum[k] += e->timing[k];
-    e->timing_sum[4] += 1.0;
-  }
-  const bool mfe_first = want_mfe && (!want_pf || e->timing[0] > e->timing[1]);
-  // the evaluation kernel (~20 us) rides in FRONT of the shorter fold on that fold's stream: one stream less to drain at the end
-  hipStream_t s_ev = e->s_eval;
-  if (want_ev && want_mfe && want_pf) s_ev = mfe_first ? e->s_pf : e->s_mfe;
-  auto enqueue_eval = [&]() -> int {
-    if (ev_in_pf) return DRNA_OK;
-    EvalArgs a = make_eval_args();
-    HIP_TRY(hipEventRecord(e->ev_e0, s_ev));
-    hipLaunchKernelGGL(eval_kernel, dim3(R * e->n_targets), dim3(WAVE), 0, s_ev, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e->ev_e1, s_ev));
-    return DRNA_OK;
-  };
-  static const bool host_profile = getenv("DRNA_HOST_PROFILE") != nullptr;      // diagnostics: where a call's host time goes (stderr, every 64 calls)
-  static double hp_acc[4] = {0, 0, 0, 0};
-  static int hp_n = 0;
-  auto hp_now = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; };
-  const double hp0 = host_profile ? hp_now() : 0.0;
-  double hp1 = 0.0, hp2 = 0.0;
-  if (!use_fused) {
-  if (mfe_first) { const int rc = enqueue_mfe(); if (rc != DRNA_OK) return rc; }
-  if (want_ev && s_ev == e->s_pf) { const int rc = enqueue_eval(); if (rc != DRNA_OK) return rc; }
-  if (want_pf) { const int rc = enqueue_pf(); if (rc != DRNA_OK) return rc; }
-  if (want_ev && s_ev == e->s_mfe) { const int rc = enqueue_eval(); if (rc != DRNA_OK) return rc; }
-  if (want_mfe && !mfe_first) { const int rc = enqueue_mfe(); if (rc != DRNA_OK) return rc; }
-  if (want_ev && s_ev == e->s_eval) { const int rc = enqueue_eval(); if (rc != DRNA_OK) return rc; }
-  // join on the host: the streams are drained one after the other (a device-side join -- stream-wait-event packets
-  // plus an end marker -- costs ~15 us after the last kernel); "total" = first start event to the latest end event
-  auto drain = [&](hipStream_t st) -> hipError_t { return hipStreamSynchronize(st); };
-  if (host_profile) hp1 = hp_now();
-  if (want_ev && !ev_in_pf && s_ev == e->s_eval) HIP_TRY(drain(e->s_eval));
-  if (mfe_first && want_pf) HIP_TRY(drain(e->s_pf));
-  if (want_mfe) HIP_TRY(drain(e->s_mfe));
-  if (!mfe_first && want_pf) HIP_TRY(drain(e->s_pf));
-  if (host_profile) hp2 = hp_now();
-  e->timing[0] = e->timing[1] = e->timing[2] = 0.f;
-  if (want_mfe) HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
-  if (want_pf) HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
-  if (want_ev && !ev_in_pf) HIP_TRY(hipEventElapsedTime(&e->timing[2], e->ev_e0, e->ev_e1));
-  {
+  } else {
+    const bool mfe_first = want_mfe && (!want_pf || e->timing[0] > e->timing[1]);
+    // the evaluation kernel (~20 us) rides in FRONT of the shorter fold on that fold's stream: one stream less to drain at the end
+    hipStream_t s_ev = e->s_eval;
+    if (want_ev && want_mfe && want_pf) s_ev = mfe_first ? e->s_pf : e->s_mfe;
+    auto enqueue_eval = [&]() -> int {
+      if (ev_in_pf) return DRNA_OK;
+      HIP_TRY(hipEventRecord(e->ev_e0, s_ev));
+      hipLaunchKernelGGL(eval_kernel, dim3(R * e->n_targets), dim3(WAVE), 0, s_ev, ev);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(e->ev_e1, s_ev));
+      return DRNA_OK;
+    };
+    if (mfe_first) { const int rc = enqueue_mfe(); if (rc != DRNA_OK) return rc; }
+    if (want_ev && s_ev == e->s_pf) { const int rc = enqueue_eval(); if (rc != DRNA_OK) return rc; }
+    if (want_pf) { const int rc = enqueue_pf(); if (rc != DRNA_OK) return rc; }
+    if (want_ev && s_ev == e->s_mfe) { const int rc = enqueue_eval(); if (rc != DRNA_OK) return rc; }
+    if (want_mfe && !mfe_first) { const int rc = enqueue_mfe(); if (rc != DRNA_OK) return rc; }
+    if (want_ev && s_ev == e->s_eval) { const int rc = enqueue_eval(); if (rc != DRNA_OK) return rc; }
+    // join on the host: the streams are drained one after the other (a device-side join -- stream-wait-event packets
+    // plus an end marker -- costs ~15 us after the last kernel); "total" = first start event to the latest end event
+    if (want_ev && !ev_in_pf && s_ev == e->s_eval) HIP_TRY(hipStreamSynchronize(e->s_eval));
+    if (mfe_first && want_pf) HIP_TRY(hipStreamSynchronize(e->s_pf));
+    if (want_mfe) HIP_TRY(hipStreamSynchronize(e->s_mfe));
+    if (!mfe_first && want_pf) HIP_TRY(hipStreamSynchronize(e->s_pf));
+    e->timing[0] = e->timing[1] = e->timing[2] = 0.f;
+    if (want_mfe) HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
+    if (want_pf) HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
+    if (want_ev && !ev_in_pf) HIP_TRY(hipEventElapsedTime(&e->timing[2], e->ev_e0, e->ev_e1));
     hipEvent_t first = mfe_first ? e->ev_m0 : want_pf ? e->ev_p0 : e->ev_e0;
     float t = 0.f, tot = 0.f;
     if (want_mfe) { HIP_TRY(hipEventElapsedTime(&t, first, e->ev_m1)); tot = t > tot ? t : tot; }
     if (want_pf) { HIP_TRY(hipEventElapsedTime(&t, first, e->ev_p1)); tot = t > tot ? t : tot; }
     if (want_ev && !ev_in_pf) { HIP_TRY(hipEventElapsedTime(&t, first, e->ev_e1)); tot = t > tot ? t : tot; }
     e->timing[3] = tot;
-    for (int k = 0; k < 4; k++) e->timing_sum[k] += e->timing[k];
-    e->timing_sum[4] += 1.0;
   }
-  if (host_profile) {
-    const double hp3 = hp_now();
-    hp_acc[0] += hp1 - hp0; hp_acc[1] += hp2 - hp1; hp_acc[2] += hp3 - hp2; hp_acc[3] += e->timing[3] * 1e3;
-    if (++hp_n == 64) {
-      fprintf(stderr, "drna_score_batch_device: host us per call: enqueue %.1f, drain %.1f (device %.1f), event queries %.1f\n",
-              hp_acc[0] / 64, hp_acc[1] / 64, hp_acc[3] / 64, hp_acc[2] / 64);
-      hp_n = 0; hp_acc[0] = hp_acc[1] = hp_acc[2] = hp_acc[3] = 0;
-    }
+  for (int k = 0; k < 4; k++) e->timing_sum[k] += e->timing[k];
+  e->timing_sum[4] += 1.0;
+  bool lost = false;
+  const int rc = fold_status(e, R, want_mfe, want_pf, nullptr, r_base, "traceback could not reproduce a table value", &lost);
+  if (lost && !e->in_fallback) {
+    for (int k = 0; k < 4; k++) e->timing_sum[k] -= e->timing[k];        // the lost attempt (up to the wait budget) is not a kernel time
+    e->timing_sum[4] -= 1.0;
+    return redo_solo(e, [&] { return score_batch_impl(e, R, L, d_seqs, flags, d_Epf, d_Emfe, d_mfe_ss, d_Ed, r_base); });
   }
-  }   // !use_fused
-  for (int r = 0; r < R; r++) {
-    const int sm = want_mfe ? e->h_status[r] : ST_OK, sp = want_pf ? e->h_status[e->max_R + r] : ST_OK;
-    const int st = sm != ST_OK ? sm : sp;
-    if (st == ST_OK) continue;
-    char buf[160];
-    if (st == ST_BAD_CHAR) {
-      snprintf(buf, sizeof buf, "sequence %d holds a character other than A C G U T", r);
-      e->err = buf;
-      return DRNA_ERR_SEQUENCE;
-    }
-    if (st == ST_PF_RANGE) {
-      snprintf(buf, sizeof buf, "sequence %d: partition function left the fp64 range (pf_scale too small/large)", r);
-      e->err = buf;
-      return DRNA_ERR_PF_RANGE;
-    }
-    if (st == ST_SYNC && !e->in_fallback) {
-      // HIP promises no dispatch order: a multi-workgroup fold whose bounded wait expired is not an error of the batch -- the
-      // whole call is redone with one workgroup per fold (general / LDS-resident kernels), which need nobody
-      const int s_strips = e->strips;
-      const bool s_dual = e->dual, s_help = e->pf_helper;
-      e->in_fallback = true; e->strips = 0; e->dual = false; e->pf_helper = false;
-      for (int k = 0; k < 4; k++) e->timing_sum[k] -= e->timing[k];        // the lost attempt (up to the wait budget) is not a kernel time
-      e->timing_sum[4] -= 1.0;
-      const int rc = drna_score_batch_device(e, R, L, d_seqs, flags, d_Epf, d_Emfe, d_mfe_ss, d_Ed);
-      e->strips = s_strips; e->dual = s_dual; e->pf_helper = s_help; e->in_fallback = false;
-      e->sync_fallbacks++;
-      if (++e->fallback_streak >= 3) { e->fallback_streak = 0; e->solo_left = SOLO_CALLS; }
-      return rc;
-    }
-    if (st == ST_SYNC) {
-      snprintf(buf, sizeof buf, "sequence %d: the workgroups of the fold lost each other (a wait expired)", r);
-      if (e->d_sdbg) {
-        std::vector<int> dbg((size_t)2 * e->max_R * 8);
-        (void)hipMemcpy(dbg.data(), e->d_sdbg, dbg.size() * sizeof(int), hipMemcpyDeviceToHost);
-        for (size_t k = 0; k < dbg.size(); k += 8)
-          if (dbg[k]) fprintf(stderr, "strip debug slot %zu: strip %d step %d saw flag %d (base %d: %d) block %d n %d\n", k / 8, dbg[k] - 1, dbg[k + 1],
-                              dbg[k + 2], dbg[k + 3], dbg[k + 2] - dbg[k + 3], dbg[k + 4], dbg[k + 5]);
-      }
-    }
-    else snprintf(buf, sizeof buf, "sequence %d: traceback could not reproduce a table value", r);
-    e->err = buf;
-    return DRNA_ERR_INTERNAL;
+  if (lost && e->d_sdbg) {
+    std::vector<int> dbg((size_t)2 * e->max_R * 8);
+    (void)hipMemcpy(dbg.data(), e->d_sdbg, dbg.size() * sizeof(int), hipMemcpyDeviceToHost);
+    for (size_t k = 0; k < dbg.size(); k += 8)
+      if (dbg[k]) fprintf(stderr, "strip debug slot %zu: strip %d step %d saw flag %d (base %d: %d) block %d n %d\n", k / 8, dbg[k] - 1, dbg[k + 1],
+                          dbg[k + 2], dbg[k + 3], dbg[k + 2] - dbg[k + 3], dbg[k + 4], dbg[k + 5]);
   }
-  if (!e->in_fallback) e->fallback_streak = 0;          // nobody lost anybody
-  return DRNA_OK;
+  if (rc == DRNA_OK && !e->in_fallback) e->fallback_streak = 0;          // nobody lost anybody
+  return rc;
+}
+
+extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char* d_seqs, uint32_t flags, double* d_Epf,
+                                       int32_t* d_Emfe, char* d_mfe_ss, int32_t* d_Ed) {
+  if (!e) return DRNA_ERR_ARG;
+  const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK), want_ev = flags & DRNA_NEED_EVAL;
+  if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || !d_seqs || (want_pf && !d_Epf) ||
+      (want_mfe && (!d_Emfe || !d_mfe_ss)) || (want_ev && !d_Ed)) {
+    e->err = "drna_score_batch: bad argument (R, L within the engine's limits; output pointers for every requested flag)";
+    return DRNA_ERR_ARG;
+  }
+  if (want_ev && (e->n_targets < 1 || e->L_targets != L)) {
+    e->err = "drna_score_batch: DRNA_NEED_EVAL needs drna_set_targets() with the same L";
+    return DRNA_ERR_ARG;
+  }
+  // more sequences than the workspaces hold (DRNA_WS_GB): one sub-batch of ws_slots after the other; last_timing = their sums
+  auto sub_batches = [&]() -> int {
+    const int nt = std::max(1, e->n_targets);
+    float sum[4] = {0, 0, 0, 0};
+    for (int r0 = 0; r0 < R; r0 += e->ws_slots) {
+      const int m = std::min(e->ws_slots, R - r0);
+      const int rc = score_batch_impl(e, m, L, d_seqs + (size_t)r0 * L, flags, d_Epf ? d_Epf + r0 : nullptr, d_Emfe ? d_Emfe + r0 : nullptr,
+                                      d_mfe_ss ? d_mfe_ss + (size_t)r0 * L : nullptr, d_Ed ? d_Ed + (size_t)r0 * nt : nullptr, r0);
+      if (rc != DRNA_OK) return rc;
+      for (int k = 0; k < 4; k++) sum[k] += e->timing[k];
+    }
+    for (int k = 0; k < 4; k++) e->timing[k] = sum[k];
+    return DRNA_OK;
+  };
+  if (e->solo_left > 0) {             // after repeated lost partners: one workgroup per fold for a while
+    const int rc = fold_solo(e, sub_batches);
+    e->solo_left--;
+    return rc;
+  }
+  return sub_batches();
 }
 
 extern "C" int drna_score_batch(drna_engine* e, int R, int L, const char* seqs, uint32_t flags, double* Epf,
@@ -838,36 +809,24 @@ extern "C" int drna_score_batch(drna_engine* e, int R, int L, const char* seqs, 
     return DRNA_ERR_ARG;
   }
   HIP_TRY(hipSetDevice(e->device));
-  if (e->zero_copy) {
-    const size_t ned = (size_t)R * (e->n_targets > 0 ? e->n_targets : 1);
-    if (want_ev && e->hm_Ed_cap < ned) {
-      if (e->hm_Ed) (void)hipHostFree(e->hm_Ed);
-      e->hm_Ed = nullptr; e->hm_Ed_cap = 0;
-      const size_t cap = (size_t)e->max_R * (e->n_targets > 0 ? e->n_targets : 1);
-      HIP_TRY(hipHostMalloc((void**)&e->hm_Ed, cap * sizeof(int32_t), hipHostMallocMapped));
-      HIP_TRY(hipHostGetDevicePointer((void**)&e->dm_Ed, e->hm_Ed, 0));
-      e->hm_Ed_cap = cap;
-    }
-    std::memcpy(e->hm_seqs, seqs, (size_t)R * L);
-    int rc = drna_score_batch_device(e, R, L, e->dm_seqs, flags, e->dm_Epf, e->dm_Emfe, e->dm_ss, e->dm_Ed);
-    if (rc != DRNA_OK) return rc;
-    if (want_pf) std::memcpy(Epf, e->hm_Epf, (size_t)R * sizeof(double));
-    if (want_mfe) {
-      std::memcpy(Emfe, e->hm_Emfe, (size_t)R * sizeof(int32_t));
-      std::memcpy(mfe_ss, e->hm_ss, (size_t)R * L);
-    }
-    if (want_ev) std::memcpy(Ed, e->hm_Ed, ned * sizeof(int32_t));
-    return DRNA_OK;
+  const size_t ned = (size_t)R * (e->n_targets > 0 ? e->n_targets : 1);
+  if (want_ev && e->hm_Ed_cap < ned) {
+    if (e->hm_Ed) (void)hipHostFree(e->hm_Ed);
+    e->hm_Ed = nullptr; e->hm_Ed_cap = 0;
+    const size_t cap = (size_t)e->max_R * (e->n_targets > 0 ? e->n_targets : 1);
+    HIP_TRY(hipHostMalloc((void**)&e->hm_Ed, cap * sizeof(int32_t), hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer((void**)&e->dm_Ed, e->hm_Ed, 0));
+    e->hm_Ed_cap = cap;
   }
-  HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
-  int rc = drna_score_batch_device(e, R, L, e->d_seqs, flags, e->d_Epf, e->d_Emfe, e->d_ss, e->d_Ed);
+  std::memcpy(e->hm_seqs, seqs, (size_t)R * L);
+  int rc = drna_score_batch_device(e, R, L, e->dm_seqs, flags, e->dm_Epf, e->dm_Emfe, e->dm_ss, e->dm_Ed);
   if (rc != DRNA_OK) return rc;
-  if (want_pf) HIP_TRY(hipMemcpy(Epf, e->d_Epf, (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
+  if (want_pf) std::memcpy(Epf, e->hm_Epf, (size_t)R * sizeof(double));
   if (want_mfe) {
-    HIP_TRY(hipMemcpy(Emfe, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(mfe_ss, e->d_ss, (size_t)R * L, hipMemcpyDeviceToHost));
+    std::memcpy(Emfe, e->hm_Emfe, (size_t)R * sizeof(int32_t));
+    std::memcpy(mfe_ss, e->hm_ss, (size_t)R * L);
   }
-  if (want_ev) HIP_TRY(hipMemcpy(Ed, e->d_Ed, (size_t)R * e->n_targets * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (want_ev) std::memcpy(Ed, e->hm_Ed, ned * sizeof(int32_t));
   return DRNA_OK;
 }
 
@@ -886,15 +845,42 @@ extern "C" int drna_timing_sums(drna_engine* e, double out[5], int reset) {
 
 extern "C" int drna_info(const drna_engine* e, int64_t out[6]) {
   if (!e || !out) return DRNA_ERR_ARG;
-  out[0] = e->device; out[1] = e->max_R; out[2] = e->max_L; out[3] = e->nt; out[4] = e->cus; out[5] = (int64_t)e->ws_bytes;
+  out[0] = e->device; out[1] = e->max_R; out[2] = e->max_L; out[3] = 1024; out[4] = e->cus; out[5] = (int64_t)e->ws_bytes;
   return DRNA_OK;
 }
 
 // ---------------------------------------------------------------- ensemble defect (inside + outside recursion)
 
-template <int NT>
-static void launch_outside(const OutArgs& a, int R, hipStream_t s) {
-  hipLaunchKernelGGL(outside_kernel<NT>, dim3(R), dim3(NT), 0, s, a);
+// one batch that fits the workspaces; its sequences are the caller's r_base, r_base + 1, ...
+static int ensemble_defect_impl(drna_engine* e, int R, int L, const char* d_seqs, double* d_edef, double* d_bpp, int r_base) {
+  HIP_TRY(hipSetDevice(e->device));
+  const int ldmax = e->max_L + 2, ld = L + 2;
+  if (!e->d_ws_out) {
+    HIP_TRY(hipMalloc((void**)&e->d_ws_out, (size_t)outside_ws_stride(ldmax) * sizeof(double) * e->ws_slots));
+    e->ws_bytes += (size_t)outside_ws_stride(ldmax) * sizeof(double) * e->ws_slots;
+  }
+  for (int k = 0; k < R; k++) e->h_status[e->max_R + k] = ST_OK;
+  // the general inside kernel: it leaves qb / qm / qm1 in the workspace (the LDS kernel keeps only rings)
+  PfArgs a = pf_args(e, d_seqs, L, ld, e->d_Epf);
+  a.q5_stride = outside_ws_stride(ld);
+  a.q5out = e->d_ws_out + (size_t)4 * ld * ld;
+  OutArgs o;
+  o.T = e->d_pfT; o.plan = e->d_plan; o.scale = e->d_scale; o.eMLb = e->d_eMLb;
+  o.seqs = d_seqs; o.L = L; o.ld = ld;
+  o.ws = e->d_ws_pf; o.ws_stride = a.ws_stride;
+  o.wo = e->d_ws_out; o.wo_stride = outside_ws_stride(ld);
+  o.pt = e->d_pt; o.edef = d_edef; o.bpp = d_bpp; o.pf_status = e->d_status + e->max_R;
+  HIP_TRY(hipEventRecord(e->ev_o0, e->s_pf));
+  hipLaunchKernelGGL(pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_o1, e->s_pf));
+  hipLaunchKernelGGL(outside_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, o);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_o2, e->s_pf));
+  HIP_TRY(hipStreamSynchronize(e->s_pf));
+  HIP_TRY(hipEventElapsedTime(&e->timing_edef[0], e->ev_o0, e->ev_o1));
+  HIP_TRY(hipEventElapsedTime(&e->timing_edef[1], e->ev_o1, e->ev_o2));
+  return fold_status(e, R, false, true, nullptr, r_base, "unexpected status of the partition function");
 }
 
 extern "C" int drna_ensemble_defect_batch_device(drna_engine* e, int R, int L, const char* d_seqs, double* d_edef,
@@ -908,64 +894,16 @@ extern "C" int drna_ensemble_defect_batch_device(drna_engine* e, int R, int L, c
     e->err = "drna_ensemble_defect_batch: needs drna_set_targets() with the same L (targets[0] is the reference structure)";
     return DRNA_ERR_ARG;
   }
-  if (R > e->ws_slots) {
-    // more sequences than the workspaces hold (DRNA_WS_GB): one sub-batch of ws_slots after the other, as drna_score_batch_device does
-    for (int r0 = 0; r0 < R; r0 += e->ws_slots) {
-      const int m = std::min(e->ws_slots, R - r0);
-      const int rc = drna_ensemble_defect_batch_device(e, m, L, d_seqs + (size_t)r0 * L, d_edef + r0,
-                                                       d_bpp ? d_bpp + (size_t)r0 * (L + 1) * (L + 1) : nullptr);
-      if (rc != DRNA_OK) return rc;
-    }
-    return DRNA_OK;
+  // more sequences than the workspaces hold (DRNA_WS_GB): one sub-batch of ws_slots after the other; last_edef_timing = their sums
+  float sum[2] = {0, 0};
+  for (int r0 = 0; r0 < R; r0 += e->ws_slots) {
+    const int m = std::min(e->ws_slots, R - r0);
+    const int rc = ensemble_defect_impl(e, m, L, d_seqs + (size_t)r0 * L, d_edef + r0,
+                                        d_bpp ? d_bpp + (size_t)r0 * (L + 1) * (L + 1) : nullptr, r0);
+    if (rc != DRNA_OK) return rc;
+    sum[0] += e->timing_edef[0]; sum[1] += e->timing_edef[1];
   }
-  HIP_TRY(hipSetDevice(e->device));
-  const int ldmax = e->max_L + 2, ld = L + 2;
-  if (!e->d_ws_out) {
-    HIP_TRY(hipMalloc((void**)&e->d_ws_out, (size_t)outside_ws_stride(ldmax) * sizeof(double) * e->ws_slots));
-    e->ws_bytes += (size_t)outside_ws_stride(ldmax) * sizeof(double) * e->ws_slots;
-  }
-  for (int k = 0; k < R; k++) e->h_status[e->max_R + k] = ST_OK;
-  // the general inside kernel: it leaves qb / qm / qm1 in the workspace (the LDS kernel keeps only rings)
-  PfArgs a;
-  a.T = e->d_pfT; a.plan = e->d_plan; a.hp_w = e->d_hp_w; a.scale = e->d_scale; a.eMLb = e->d_eMLb;
-  a.seqs = d_seqs; a.L = L; a.ld = ld;
-  a.ws = e->d_ws_pf; a.ws_stride = (long long)pf_ws_stride(ld);
-  a.Epf = e->d_Epf; a.status = e->d_status + e->max_R;
-  a.q5_stride = outside_ws_stride(ld);
-  a.q5out = e->d_ws_out + (size_t)4 * ld * ld;
-  OutArgs o;
-  o.T = e->d_pfT; o.plan = e->d_plan; o.scale = e->d_scale; o.eMLb = e->d_eMLb;
-  o.seqs = d_seqs; o.L = L; o.ld = ld;
-  o.ws = e->d_ws_pf; o.ws_stride = a.ws_stride;
-  o.wo = e->d_ws_out; o.wo_stride = outside_ws_stride(ld);
-  o.pt = e->d_pt; o.edef = d_edef; o.bpp = d_bpp; o.pf_status = e->d_status + e->max_R;
-  HIP_TRY(hipEventRecord(e->ev_o0, e->s_pf));
-  if (e->nt == 256) launch_pf<256>(a, R, e->s_pf);
-  else if (e->nt == 512) launch_pf<512>(a, R, e->s_pf);
-  else launch_pf<1024>(a, R, e->s_pf);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->ev_o1, e->s_pf));
-  if (e->nt == 256) launch_outside<256>(o, R, e->s_pf);
-  else if (e->nt == 512) launch_outside<512>(o, R, e->s_pf);
-  else launch_outside<1024>(o, R, e->s_pf);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->ev_o2, e->s_pf));
-  HIP_TRY(hipStreamSynchronize(e->s_pf));
-  HIP_TRY(hipEventElapsedTime(&e->timing_edef[0], e->ev_o0, e->ev_o1));
-  HIP_TRY(hipEventElapsedTime(&e->timing_edef[1], e->ev_o1, e->ev_o2));
-  for (int r = 0; r < R; r++) {
-    const int st = e->h_status[e->max_R + r];
-    if (st == ST_OK) continue;
-    char buf[160];
-    if (st == ST_BAD_CHAR) {
-      snprintf(buf, sizeof buf, "sequence %d holds a character other than A C G U T", r);
-      e->err = buf;
-      return DRNA_ERR_SEQUENCE;
-    }
-    snprintf(buf, sizeof buf, "sequence %d: partition function left the fp64 range (pf_scale too small/large)", r);
-    e->err = buf;
-    return DRNA_ERR_PF_RANGE;
-  }
+  e->timing_edef[0] = sum[0]; e->timing_edef[1] = sum[1];
   return DRNA_OK;
 }
 
@@ -1014,20 +952,9 @@ extern "C" int drna_set_targets_ragged(drna_engine* e, int n_targets, const int3
     total += (size_t)lens[t] + 2;
   }
   std::vector<short> pt(total, 0);
-  std::vector<int> stk;
   for (int t = 0; t < n_targets; t++) {
-    stk.clear();
-    const char* s = targets + chars;
-    short* p = pt.data() + off[t];
-    for (int i = 1; i <= lens[t]; i++) {
-      if (s[i - 1] == '(') stk.push_back(i);
-      else if (s[i - 1] == ')') {
-        if (stk.empty()) { e->err = "drna_set_targets_ragged: unbalanced ')'"; return DRNA_ERR_STRUCTURE; }
-        const int o = stk.back(); stk.pop_back();
-        p[o] = (short)i; p[i] = (short)o;
-      }
-    }
-    if (!stk.empty()) { e->err = "drna_set_targets_ragged: unbalanced '('"; return DRNA_ERR_STRUCTURE; }
+    const int rc = target_pairs(e, "drna_set_targets_ragged", targets + chars, lens[t], pt.data() + off[t]);
+    if (rc != DRNA_OK) return rc;
     chars += (size_t)lens[t];
   }
   HIP_TRY(hipSetDevice(e->device));
@@ -1050,11 +977,9 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
     return DRNA_ERR_ARG;
   }
   e->cur_with_pf = want_pf;
+  auto again = [&] { return drna_score_ragged(e, R, lens, seqs, target_of, flags, Epf, Emfe, mfe_ss, Ed); };
   if (!e->in_fallback && e->solo_left > 0) {             // (see drna_score_batch_device)
-    const int s_strips = e->strips;
-    e->in_fallback = true; e->strips = 0;
-    const int rc = drna_score_ragged(e, R, lens, seqs, target_of, flags, Epf, Emfe, mfe_ss, Ed);
-    e->strips = s_strips; e->in_fallback = false;
+    const int rc = fold_solo(e, again);
     e->solo_left--;
     return rc;
   }
@@ -1096,13 +1021,12 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
       if (want_ev) h[(size_t)2 * R + q] = target_of[r];
     }
   }
-  const bool fast_ok = e->lds_path && e->nt == 1024;
   int nA = 0, nC = 0, nD = 0;
   int *idxA = h.data() + (size_t)3 * R, *idxC = h.data() + (size_t)5 * R, *idxD = h.data() + (size_t)6 * R;
   const int ld = e->max_L + 2;
   for (int q = 0; q < R; q++) {
     const int len = h[q];
-    if (fast_ok && len <= MFE_FAST_NMAX && len <= PF_FAST_NMAX) idxA[nA++] = q;
+    if (len <= MFE_FAST_NMAX && len <= PF_FAST_NMAX) idxA[nA++] = q;
     else if (strips_for(e, len, ld) && len > PF_FAST_NMAX) idxC[nC++] = q;
     else idxD[nD++] = q;
   }
@@ -1127,11 +1051,7 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
   HIP_TRY(hipStreamWaitEvent(e->s_pf, e->ev_start, 0));
   HIP_TRY(hipStreamWaitEvent(e->s_eval, e->ev_start, 0));
   if (want_mfe) {
-    MfeArgs a;
-    a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = e->d_seqs; a.L = 0; a.ld = ld;
-    a.pk_rounds = want_pk ? 3 : 0;
-    a.ws_stride = (long long)mfe_ws_stride(ld);
-    a.Emfe = e->d_Emfe; a.ss = e->d_ss; a.status = e->d_status;
+    MfeArgs a = mfe_args(e, e->d_seqs, 0, ld, want_pk ? 3 : 0, e->d_Emfe, e->d_ss);
     a.rg = rg;
     HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
     for (int c0 = 0; c0 < R; c0 += slots) {
@@ -1150,9 +1070,7 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
       part(idxD, nD, c0, c1, f, m);
       if (m) {
         a.rg.idx = e->d_rg + (size_t)6 * R + f;
-        if (e->nt == 256) launch_mfe<256>(a, m, e->s_mfe);
-        else if (e->nt == 512) launch_mfe<512>(a, m, e->s_mfe);
-        else launch_mfe<1024>(a, m, e->s_mfe);
+        hipLaunchKernelGGL(mfe_kernel<1024>, dim3(m), dim3(1024), 0, e->s_mfe, a);
       }
       part(idxA, nA, c0, c1, f, m);
       if (m) {
@@ -1164,11 +1082,7 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
     HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
   }
   if (want_pf) {
-    PfArgs a;
-    a.T = e->d_pfT; a.plan = e->d_plan; a.hp_w = e->d_hp_w; a.scale = e->d_scale; a.eMLb = e->d_eMLb;
-    a.seqs = e->d_seqs; a.L = 0; a.ld = ld;
-    a.ws_stride = (long long)pf_ws_stride(ld);
-    a.Epf = e->d_Epf; a.status = e->d_status + e->max_R;
+    PfArgs a = pf_args(e, e->d_seqs, 0, ld, e->d_Epf);
     a.rg = rg;
     HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
     for (int c0 = 0; c0 < R; c0 += slots) {
@@ -1187,9 +1101,7 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
       part(idxD, nD, c0, c1, f, m);
       if (m) {
         a.rg.idx = e->d_rg + (size_t)6 * R + f;
-        if (e->nt == 256) launch_pf<256>(a, m, e->s_pf);
-        else if (e->nt == 512) launch_pf<512>(a, m, e->s_pf);
-        else launch_pf<1024>(a, m, e->s_pf);
+        hipLaunchKernelGGL(pf_kernel<1024>, dim3(m), dim3(1024), 0, e->s_pf, a);
       }
       part(idxA, nA, c0, c1, f, m);
       if (m) {
@@ -1202,9 +1114,8 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
     HIP_TRY(hipStreamWaitEvent(e->s_mfe, e->ev_p1, 0));
   }
   if (want_ev) {
-    EvalArgs a;
-    a.T = e->d_mfeT; a.hp_len = e->d_hp_len; a.bulge_len = e->d_bulge_len; a.int_len = e->d_int_len;
-    a.seqs = e->d_seqs; a.pt = e->d_rpt; a.L = 0; a.n_targets = 1; a.Ed = e->d_Ed;
+    EvalArgs a = eval_args(e, e->d_seqs, 0, e->d_Ed);
+    a.pt = e->d_rpt; a.n_targets = 1;
     a.rg = rg; a.target_of = e->d_rg + (size_t)2 * R; a.pt_off = e->d_rpt_off;
     HIP_TRY(hipEventRecord(e->ev_e0, e->s_eval));
     hipLaunchKernelGGL(eval_kernel, dim3(R), dim3(WAVE), 0, e->s_eval, a);
@@ -1219,26 +1130,11 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
   if (want_pf) HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
   if (want_ev) HIP_TRY(hipEventElapsedTime(&e->timing[2], e->ev_e0, e->ev_e1));
   HIP_TRY(hipEventElapsedTime(&e->timing[3], e->ev_start, e->ev_end));
-  for (int q = 0; q < R; q++) {
-    const int sm = want_mfe ? e->h_status[q] : ST_OK, sp = want_pf ? e->h_status[e->max_R + q] : ST_OK;
-    const int st = sm != ST_OK ? sm : sp;
-    if (st == ST_OK) continue;
-    if (st == ST_SYNC && !e->in_fallback) {               // (see drna_score_batch_device)
-      const int s_strips = e->strips;
-      e->in_fallback = true; e->strips = 0;
-      const int rc = drna_score_ragged(e, R, lens, seqs, target_of, flags, Epf, Emfe, mfe_ss, Ed);
-      e->strips = s_strips; e->in_fallback = false;
-      e->sync_fallbacks++;
-      if (++e->fallback_streak >= 3) { e->fallback_streak = 0; e->solo_left = SOLO_CALLS; }
-      return rc;
-    }
-    char buf[160];
-    snprintf(buf, sizeof buf, st == ST_BAD_CHAR ? "sequence %d holds a character other than A C G U T"
-                              : st == ST_PF_RANGE ? "sequence %d: partition function left the fp64 range"
-                              : st == ST_SYNC ? "sequence %d: the two workgroups of the fold lost each other (wait expired)"
-                                                  : "sequence %d: traceback could not reproduce a table value", order[q]);
-    e->err = buf;
-    return st == ST_BAD_CHAR ? DRNA_ERR_SEQUENCE : st == ST_PF_RANGE ? DRNA_ERR_PF_RANGE : DRNA_ERR_INTERNAL;
+  {
+    bool lost = false;
+    const int rc = fold_status(e, R, want_mfe, want_pf, order.data(), 0, "traceback could not reproduce a table value", &lost);
+    if (lost && !e->in_fallback) return redo_solo(e, again);      // (see score_batch_impl)
+    if (rc != DRNA_OK) return rc;
   }
   if (!e->in_fallback) e->fallback_streak = 0;
   // results back in the caller's order
@@ -1264,11 +1160,6 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
 
 // ---------------------------------------------------------------- second-best structure energy (-nd on)
 
-template <int NT>
-static void launch_subopt(const SubArgs& a, int R, hipStream_t s) {
-  hipLaunchKernelGGL(subopt_kernel<NT>, dim3(R), dim3(NT), 0, s, a);
-}
-
 extern "C" int drna_subopt_energy_batch(drna_engine* e, int R, int L, const char* seqs, int32_t* E2, int32_t* E12) {
   if (!e) return DRNA_ERR_ARG;
   if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || !seqs || !E2) {
@@ -1285,29 +1176,16 @@ extern "C" int drna_subopt_energy_batch(drna_engine* e, int R, int L, const char
   a.ws = reinterpret_cast<int32_t*>(e->d_ws_pf); a.ws_stride = 2 * (long long)pf_ws_stride(ld);   // int32 units of the PF workspace
   a.E2 = e->d_Emfe; a.E12 = reinterpret_cast<int32_t*>(e->d_Epf); a.status = e->d_status;
   HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-  if (e->nt == 256) launch_subopt<256>(a, R, e->s_mfe);
-  else if (e->nt == 512) launch_subopt<512>(a, R, e->s_mfe);
-  else launch_subopt<1024>(a, R, e->s_mfe);
+  hipLaunchKernelGGL(subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
   HIP_TRY(hipStreamSynchronize(e->s_mfe));
   HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
   e->timing[1] = e->timing[2] = 0.f; e->timing[3] = e->timing[0];
-  for (int r = 0; r < R; r++)
-    if (e->h_status[r] == ST_BAD_CHAR) {
-      char buf[96];
-      snprintf(buf, sizeof buf, "sequence %d holds a character other than A C G U T", r);
-      e->err = buf;
-      return DRNA_ERR_SEQUENCE;
-    }
+  { const int rc = fold_status(e, R, true, false, nullptr, 0, "unexpected status of the second-best fold"); if (rc != DRNA_OK) return rc; }
   HIP_TRY(hipMemcpy(E2, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (E12) HIP_TRY(hipMemcpy(E12, e->d_Epf, (size_t)2 * R * sizeof(int32_t), hipMemcpyDeviceToHost));
   return DRNA_OK;
-}
-
-template <int NT, int K>
-static void launch_kbest(const KbArgs& a, int R, hipStream_t s) {
-  hipLaunchKernelGGL((kbest_kernel<NT, K>), dim3(R), dim3(NT), 0, s, a);
 }
 
 extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const char* seqs, int K, int32_t* E, char* ss) {
@@ -1340,35 +1218,15 @@ extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const cha
     a.ws = e->d_ws_kb; a.ws_stride = (long long)3 * KT * ld * ld;
     a.E = e->d_kbE; a.ss = e->d_kbss; a.status = e->d_status;
     HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-    if (KT == 4) {
-      if (e->nt == 256) launch_kbest<256, 4>(a, rc, e->s_mfe);
-      else if (e->nt == 512) launch_kbest<512, 4>(a, rc, e->s_mfe);
-      else launch_kbest<1024, 4>(a, rc, e->s_mfe);
-    } else {
-      if (e->nt == 256) launch_kbest<256, 8>(a, rc, e->s_mfe);
-      else if (e->nt == 512) launch_kbest<512, 8>(a, rc, e->s_mfe);
-      else launch_kbest<1024, 8>(a, rc, e->s_mfe);
-    }
+    if (KT == 4) hipLaunchKernelGGL((kbest_kernel<1024, 4>), dim3(rc), dim3(1024), 0, e->s_mfe, a);
+    else hipLaunchKernelGGL((kbest_kernel<1024, 8>), dim3(rc), dim3(1024), 0, e->s_mfe, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
     HIP_TRY(hipStreamSynchronize(e->s_mfe));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, e->ev_m0, e->ev_m1));
     ms_total += ms;
-    for (int r = 0; r < rc; r++) {
-      if (e->h_status[r] == ST_BAD_CHAR) {
-        char buf[96];
-        snprintf(buf, sizeof buf, "sequence %d holds a character other than A C G U T", r0 + r);
-        e->err = buf;
-        return DRNA_ERR_SEQUENCE;
-      }
-      if (e->h_status[r] != ST_OK) {
-        char buf[96];
-        snprintf(buf, sizeof buf, "sequence %d: traceback of a ranked structure failed (internal error)", r0 + r);
-        e->err = buf;
-        return DRNA_ERR_INTERNAL;
-      }
-    }
+    { const int st = fold_status(e, rc, true, false, nullptr, r0, "traceback of a ranked structure failed (internal error)"); if (st != DRNA_OK) return st; }
     HIP_TRY(hipMemcpy(hE.data(), e->d_kbE, (size_t)KT * rc * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(hs.data(), e->d_kbss, (size_t)KT * rc * L, hipMemcpyDeviceToHost));
     for (int r = 0; r < rc; r++)
@@ -1382,12 +1240,6 @@ extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const cha
 }
 
 // ---------------------------------------------------------------- two strands (co-fold)
-
-template <int NT>
-static void launch_cofold(const CoArgs& a, int R, bool mfe, bool pf, hipStream_t sm, hipStream_t sp) {
-  if (pf) hipLaunchKernelGGL(cofold_pf_kernel<NT>, dim3(R), dim3(NT), 0, sp, a);
-  if (mfe) hipLaunchKernelGGL(cofold_mfe_kernel<NT>, dim3(R), dim3(NT), 0, sm, a);
-}
 
 extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const char* seqs, uint32_t flags, double* F4,
                                  int32_t* Emfe, char* mfe_ss, int32_t* Ed) {
@@ -1418,16 +1270,13 @@ extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const ch
   a.Emfe = e->d_Emfe; a.ss = e->d_ss; a.F4 = e->d_F4; a.status = e->d_status; a.status_pf = e->d_status + e->max_R;
   HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
   HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-  if (e->nt == 256) launch_cofold<256>(a, R, want_mfe, want_pf, e->s_mfe, e->s_pf);
-  else if (e->nt == 512) launch_cofold<512>(a, R, want_mfe, want_pf, e->s_mfe, e->s_pf);
-  else launch_cofold<1024>(a, R, want_mfe, want_pf, e->s_mfe, e->s_pf);
+  if (want_pf) hipLaunchKernelGGL(cofold_pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a);
+  if (want_mfe) hipLaunchKernelGGL(cofold_mfe_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(e->ev_p1, e->s_pf));
   HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
   if (want_ev) {
-    EvalArgs v;
-    v.T = e->d_mfeT; v.hp_len = e->d_hp_len; v.bulge_len = e->d_bulge_len; v.int_len = e->d_int_len;
-    v.seqs = e->d_seqs; v.pt = e->d_pt; v.L = L; v.n_targets = e->n_targets; v.Ed = e->d_Ed;
+    EvalArgs v = eval_args(e, e->d_seqs, L, e->d_Ed);
     v.cut = cut; v.DuplexInit = e->H.DuplexInit;
     hipLaunchKernelGGL(eval_kernel, dim3(R * e->n_targets), dim3(WAVE), 0, e->s_eval, v);
     HIP_TRY(hipGetLastError());
@@ -1438,18 +1287,7 @@ extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const ch
   HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
   HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
   e->timing[2] = 0.f; e->timing[3] = e->timing[0] > e->timing[1] ? e->timing[0] : e->timing[1];
-  for (int r = 0; r < R; r++) {
-    const int sm = want_mfe ? e->h_status[r] : ST_OK, sp = want_pf ? e->h_status[e->max_R + r] : ST_OK;
-    const int st = sm != ST_OK ? sm : sp;
-    if (st == ST_OK) continue;
-    char buf[160];
-    snprintf(buf, sizeof buf, st == ST_BAD_CHAR ? "sequence %d holds a character other than A C G U T"
-                              : st == ST_PF_RANGE ? "sequence %d: partition function left the fp64 range"
-                              : st == ST_SYNC ? "sequence %d: the two workgroups of the fold lost each other (wait expired)"
-                                                  : "sequence %d: traceback could not reproduce a table value", r);
-    e->err = buf;
-    return st == ST_BAD_CHAR ? DRNA_ERR_SEQUENCE : st == ST_PF_RANGE ? DRNA_ERR_PF_RANGE : DRNA_ERR_INTERNAL;
-  }
+  { const int rc = fold_status(e, R, want_mfe, want_pf, nullptr, 0, "traceback could not reproduce a table value"); if (rc != DRNA_OK) return rc; }
   if (want_pf) HIP_TRY(hipMemcpy(F4, e->d_F4, (size_t)4 * R * sizeof(double), hipMemcpyDeviceToHost));
   if (want_mfe) {
     HIP_TRY(hipMemcpy(Emfe, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1708,35 +1546,26 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
   // structure equals the current one (most single mutations of a converged replica) reuses all three
   std::vector<int> cur_pq((size_t)R * L), prop_pq((size_t)R * L), cur_pool((size_t)R * L), cur_np(R, -1);
   std::vector<SimMetrics> cur_m(R);
-  // host work per replica may be dealt to worker threads (McPool, host_driver.hpp; option "mc_threads", default 1: at ~0.4 us per
-  // replica the hand-off to spinning workers costs what it saves, measured on the GPU box); replicas own their random streams and state
-  const int T = std::max(1, std::min(e->mc_threads > 0 ? e->mc_threads : 1, (R + 3) / 4));
-  e->mc_threads_used = T;
-  McPool workers(T);
-  std::vector<std::vector<char>> mark(T, std::vector<char>(L));
-  std::atomic<int> fail{DRNA_OK};
-  auto range = [&](int w, int& r0, int& r1) { r0 = (int)((long long)R * w / T); r1 = (int)((long long)R * (w + 1) / T); };
-  auto refresh_pool = [&](int w, int r) {
-    if (targeted) cur_np[r] = targeted_pool(ctx, cur_pq.data() + (size_t)r * L, mark[w].data(), cur_pool.data() + (size_t)r * L);
+  std::vector<char> mark(L);
+  int fail = DRNA_OK;              // the last failure; the other replicas go on, as without it
+  auto refresh_pool = [&](int r) {
+    if (targeted) cur_np[r] = targeted_pool(ctx, cur_pq.data() + (size_t)r * L, mark.data(), cur_pool.data() + (size_t)r * L);
   };
-  auto propose_range = [&](int r0, int r1) {
-    for (int r = r0; r < r1; r++) {
+  auto propose_all = [&] {         // the next proposal of every replica, each from its own random stream
+    for (int r = 0; r < R; r++) {
       const int rc = propose_one(ctx, seqs + (size_t)r * L, cur_pool.data() + (size_t)r * L, cur_np[r], p_shelf[r],
                                  Mt{rng_state + (size_t)r * RNG_WORDS}, prop.data() + (size_t)r * L);
-      if (rc != DRNA_OK) fail.store(rc);
+      if (rc != DRNA_OK) fail = rc;
     }
   };
-  workers.run([&](int w) {
-    int r0, r1; range(w, r0, r1);
-    for (int r = r0; r < r1; r++) {
-      if (targeted) p_shelf[r] = shelf_probability(ctx, shelf_index[r]);
-      if (!pair_table(mfe_ss + (size_t)r * L, L, cur_pq.data() + (size_t)r * L)) { fail.store(DRNA_ERR_STRUCTURE); continue; }
-      cur_m[r] = sim_metrics(pr, cur_pq.data() + (size_t)r * L, L);
-      refresh_pool(w, r);
-    }
-    if (n_iter > 0 && fail.load() == DRNA_OK) propose_range(r0, r1);
-  });
-  if (fail.load() != DRNA_OK) { e->err = "drna_mc_run: proposal failed (unbalanced structure in the state, or a bad design problem)"; return fail.load(); }
+  for (int r = 0; r < R; r++) {
+    if (targeted) p_shelf[r] = shelf_probability(ctx, shelf_index[r]);
+    if (!pair_table(mfe_ss + (size_t)r * L, L, cur_pq.data() + (size_t)r * L)) { fail = DRNA_ERR_STRUCTURE; continue; }
+    cur_m[r] = sim_metrics(pr, cur_pq.data() + (size_t)r * L, L);
+    refresh_pool(r);
+  }
+  if (n_iter > 0 && fail == DRNA_OK) propose_all();
+  if (fail != DRNA_OK) { e->err = "drna_mc_run: proposal failed (unbalanced structure in the state, or a bad design problem)"; return fail; }
   static const bool mc_profile = getenv("DRNA_MC_PROFILE") != nullptr;     // diagnostics: where an iteration's host time goes (stderr)
   double prof[3] = {0, 0, 0};
   auto now_us = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; };
@@ -1750,57 +1579,53 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
       rc = drna_ensemble_defect_batch(e, R, L, prop.data(), pEdef.data(), nullptr);
       if (rc != DRNA_OK) return rc;
     }
-    const bool more = it + 1 < n_iter;
-    workers.run([&](int w) {
-      int r0, r1; range(w, r0, r1);
-      for (int r = r0; r < r1; r++) {
-        // SimScore of the proposal's structure against the target (utils/sim_score.py:62-147)
-        int* ppq = prop_pq.data() + (size_t)r * L;
-        const bool same_ss = std::memcmp(pss.data() + (size_t)r * L, mfe_ss + (size_t)r * L, (size_t)L) == 0;
-        SimMetrics m = cur_m[r];
-        if (!same_ss) {
-          if (!pair_table(pss.data() + (size_t)r * L, L, ppq)) { fail.store(DRNA_ERR_STRUCTURE); continue; }
-          m = sim_metrics(pr, ppq, L);
-        }
-        const double ed = pEd[(size_t)r * nt] / 100.0;
-        // -sf terms (utils/energy_scores.py:376-398): 0 Ed-Epf, 1 1-MCC, 2 sln_Epf, 3 Ed-MFE, 4 1-precision, 5 1-recall, 6 Edef
-        double tot = 0.0;
-        for (int k = 0; k < n_terms; k++) {
-          double v = 0.0;
-          switch (term_id[k]) {
-            case 0: v = ed - pEpf[r]; break;
-            case 1: v = (1 - m.mcc) * 10; break;
-            case 2: v = (pEpf[r] + 0.3759 * L + 5.7534) / 10; break;
-            case 3: v = ed - pEmfe[r] / 100.0; break;
-            case 4: v = (1 - m.precision) * 10; break;
-            case 5: v = (1 - m.recall) * 10; break;
-            case 6: v = pEdef[r]; break;
-          }
-          tot += v * term_w[k];
-        }
-        if (nt > 1) {                                           // alternative structures (:98-102)
-          double sum = 0.0;
-          for (int t = 1; t < nt; t++) sum += pEd[(size_t)r * nt + t] / 100.0;
-          tot += sum / (nt - 1) - pEpf[r];
-        }
-        pscore[r] = tot; pmcc[r] = 1 - m.mcc;
-        // Metropolis (utils/replica_exchange_monte_carlo.py:26-57): one draw from the replica's stream, only when the mutant is worse
-        (void)drna_metropolis_batch(1, score + r, pscore.data() + r, temps + r, Lconst, rng_state + (size_t)r * RNG_WORDS, acc.data() + r,
-                                    better.data() + r);
-        if (acc[r]) {
-          std::memcpy(seqs + (size_t)r * L, prop.data() + (size_t)r * L, (size_t)L);
-          if (!same_ss) {
-            std::memcpy(mfe_ss + (size_t)r * L, pss.data() + (size_t)r * L, (size_t)L);
-            std::memcpy(cur_pq.data() + (size_t)r * L, ppq, (size_t)L * sizeof(int));
-            cur_m[r] = m;
-            refresh_pool(w, r);
-          }
-          score[r] = pscore[r]; mcc1[r] = pmcc[r]; Epf[r] = pEpf[r]; Ed[r] = ed;
-        }
+    for (int r = 0; r < R; r++) {
+      // SimScore of the proposal's structure against the target (utils/sim_score.py:62-147)
+      int* ppq = prop_pq.data() + (size_t)r * L;
+      const bool same_ss = std::memcmp(pss.data() + (size_t)r * L, mfe_ss + (size_t)r * L, (size_t)L) == 0;
+      SimMetrics m = cur_m[r];
+      if (!same_ss) {
+        if (!pair_table(pss.data() + (size_t)r * L, L, ppq)) { fail = DRNA_ERR_STRUCTURE; continue; }
+        m = sim_metrics(pr, ppq, L);
       }
-      if (more && fail.load() == DRNA_OK) propose_range(r0, r1);          // the next iteration's proposals (same streams, after the Metropolis draw)
-    });
-    if (fail.load() != DRNA_OK) { e->err = "drna_mc_run: unbalanced MFE structure from the engine, or a failed proposal"; return fail.load(); }
+      const double ed = pEd[(size_t)r * nt] / 100.0;
+      // -sf terms (utils/energy_scores.py:376-398): 0 Ed-Epf, 1 1-MCC, 2 sln_Epf, 3 Ed-MFE, 4 1-precision, 5 1-recall, 6 Edef
+      double tot = 0.0;
+      for (int k = 0; k < n_terms; k++) {
+        double v = 0.0;
+        switch (term_id[k]) {
+          case 0: v = ed - pEpf[r]; break;
+          case 1: v = (1 - m.mcc) * 10; break;
+          case 2: v = (pEpf[r] + 0.3759 * L + 5.7534) / 10; break;
+          case 3: v = ed - pEmfe[r] / 100.0; break;
+          case 4: v = (1 - m.precision) * 10; break;
+          case 5: v = (1 - m.recall) * 10; break;
+          case 6: v = pEdef[r]; break;
+        }
+        tot += v * term_w[k];
+      }
+      if (nt > 1) {                                           // alternative structures (:98-102)
+        double sum = 0.0;
+        for (int t = 1; t < nt; t++) sum += pEd[(size_t)r * nt + t] / 100.0;
+        tot += sum / (nt - 1) - pEpf[r];
+      }
+      pscore[r] = tot; pmcc[r] = 1 - m.mcc;
+      // Metropolis (utils/replica_exchange_monte_carlo.py:26-57): one draw from the replica's stream, only when the mutant is worse
+      (void)drna_metropolis_batch(1, score + r, pscore.data() + r, temps + r, Lconst, rng_state + (size_t)r * RNG_WORDS, acc.data() + r,
+                                  better.data() + r);
+      if (acc[r]) {
+        std::memcpy(seqs + (size_t)r * L, prop.data() + (size_t)r * L, (size_t)L);
+        if (!same_ss) {
+          std::memcpy(mfe_ss + (size_t)r * L, pss.data() + (size_t)r * L, (size_t)L);
+          std::memcpy(cur_pq.data() + (size_t)r * L, ppq, (size_t)L * sizeof(int));
+          cur_m[r] = m;
+          refresh_pool(r);
+        }
+        score[r] = pscore[r]; mcc1[r] = pmcc[r]; Epf[r] = pEpf[r]; Ed[r] = ed;
+      }
+    }
+    if (it + 1 < n_iter && fail == DRNA_OK) propose_all();          // the next iteration's proposals (same streams, after the Metropolis draw)
+    if (fail != DRNA_OK) { e->err = "drna_mc_run: unbalanced MFE structure from the engine, or a failed proposal"; return fail; }
     const double tp2 = mc_profile ? now_us() : 0.0;
     // counters and the best state, replica by replica in replica order (first strictly better wins)
     for (int r = 0; r < R; r++) {
@@ -1817,8 +1642,8 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
     if (mc_profile) { prof[0] += tp1 - tp0 - e->timing[3] * 1e3; prof[1] += tp2 - tp1; prof[2] += now_us() - tp2; }
   }
   if (mc_profile && n_iter > 0)
-    fprintf(stderr, "drna_mc_run: per iteration, host us: score call beyond device time %.1f, per-replica work (%d threads) %.1f, bookkeeping %.1f\n",
-            prof[0] / n_iter, T, prof[1] / n_iter, prof[2] / n_iter);
+    fprintf(stderr, "drna_mc_run: per iteration, host us: score call beyond device time %.1f, per-replica work %.1f, bookkeeping %.1f\n",
+            prof[0] / n_iter, prof[1] / n_iter, prof[2] / n_iter);
   return DRNA_OK;
 }
 

@@ -22,11 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
-#include <functional>
-#include <thread>
 #include <vector>
-#include <sched.h>
 
 namespace drna_host {
 
@@ -178,63 +174,6 @@ static inline SimMetrics sim_metrics(const int* pr, const int* pq, int n) {
   }
   return SimMetrics{py_round3(num / (den + 0.00001)), py_round3((double)tp / ((double)(tp + fn) + 0.001)),
                     py_round3((double)tp / ((double)(tp + fp) + 0.001))};
-}
-
-// ---- worker threads of the Monte-Carlo inner loop (drna_mc_run).  The per-replica host work of an iteration (SimScore,
-// Metropolis, state update, next proposal: ~2 us per replica) sits between two kernel launches, i.e. on the critical path of
-// every iteration, and replicas are independent (own random stream, own state), so it is dealt to T threads in contiguous
-// replica ranges.  The workers live for one drna_mc_run call and SPIN between jobs (a futex wake-up costs more than the job);
-// the calling thread is worker 0.
-struct McPool {
-  int T = 1;
-  std::vector<std::thread> th;
-  std::atomic<int> gen{0}, left{0};
-  std::atomic<bool> quit{false};
-  std::function<void(int)> job;                  // job(worker index)
-  explicit McPool(int threads) : T(threads < 1 ? 1 : threads) {
-    for (int w = 1; w < T; w++)
-      th.emplace_back([this, w] {
-        int seen = 0;
-        for (;;) {
-          int spins = 0;
-          while (gen.load(std::memory_order_acquire) == seen) {
-            if (quit.load(std::memory_order_relaxed)) return;
-            if (++spins > 4096) { sched_yield(); spins = 0; } else __builtin_ia32_pause();
-          }
-          seen++;
-          job(w);
-          left.fetch_sub(1, std::memory_order_acq_rel);
-        }
-      });
-  }
-  template <class F> void run(F&& f) {
-    if (T == 1) { f(0); return; }
-    job = std::forward<F>(f);
-    left.store(T - 1, std::memory_order_relaxed);
-    gen.fetch_add(1, std::memory_order_release);
-    job(0);
-    while (left.load(std::memory_order_acquire) != 0) __builtin_ia32_pause();
-  }
-  ~McPool() {
-    quit.store(true);
-    for (auto& t : th) t.join();
-  }
-};
-// CPUs this process may really use: the affinity mask capped by the cgroup CPU quota (a GPU lease shows the host's 256 hardware
-// threads and allows a share of them)
-static inline int usable_cpus() {
-  cpu_set_t set;
-  int n = 1;
-  if (sched_getaffinity(0, sizeof set, &set) == 0) n = CPU_COUNT(&set);
-  if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-    char q[32]; double per = 0;
-    if (fscanf(f, "%31s %lf", q, &per) == 2 && strcmp(q, "max") != 0 && per > 0) {
-      const int c = (int)(atof(q) / per + 0.5);
-      if (c >= 1 && c < n) n = c;
-    }
-    fclose(f);
-  }
-  return n < 1 ? 1 : n;
 }
 
 }  // namespace drna_host

@@ -915,6 +915,13 @@ def test_batches_larger_than_the_workspace_go_in_chunks(eng400, oracle, monkeypa
         small.set_targets([tg130]); eng400.set_targets([tg130])
         ea, eb = small.ensemble_defect(uni), eng400.ensemble_defect(uni)
         assert (ea.view(np.int64) == eb.view(np.int64)).all() and abs(ea[-1] - oracle.ensemble_defect(uni[-1], tg130)) < 1e-10
+        # an error in a later sub-batch names the caller's sequence, not its position within the sub-batch
+        bad = list(uni)
+        bad[slots + 3] = bad[slots + 3][:60] + "N" + bad[slots + 3][61:]
+        for call in (lambda: small.score_batch(bad, flags), lambda: small.ensemble_defect(bad)):
+            with pytest.raises(E.EngineError) as ei:
+                call()
+            assert ei.value.code == -4 and "sequence %d " % (slots + 3) in str(ei.value), str(ei.value)
     finally:
         small.close()
     k = 4

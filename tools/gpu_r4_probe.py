@@ -1,5 +1,5 @@
-"""GPU box, round 4 probe: (1) end-to-end Monte-Carlo loop rate by host thread count, (2) replicas-per-call sweep of the headline shape
-with and without the strip kernels for n <= 200, (3) kernel times of every prebuilt variant in build/var/."""
+"""GPU box, round 4 probe: (1) replicas-per-call sweep of the headline shape with and without the strip kernels for n <= 200,
+(2) kernel times of every prebuilt variant in build/var/."""
 import glob, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,19 +23,6 @@ def time_batch(eng, seqs, flags, reps=12):
     ts = ts[3:]
     return {"wall_ms": 1e3 * min(t[0] for t in ts), "mfe": min(t[1]["mfe"] for t in ts), "pf": min(t[1]["pf"] for t in ts),
             "total": min(t[1]["total"] for t in ts)}
-
-if "mc" in sys.argv[1:] or len(sys.argv) == 1:
-    eng = E.Engine(max_R=64, max_L=L)
-    eng.set_targets([tg])
-    base = time_batch(eng, seqs_for(64), E.NEED_PF | E.NEED_MFE | E.NEED_EVAL)
-    out["kernel_only"] = base
-    print("kernel only", base, flush=True)
-    for T in (1, 2, 4, 8, 12):
-        eng.set_option("mc_threads", T)
-        r = bench.mc_loop_block(eng, tg, 64, 100, 64 / (base["wall_ms"] * 1e-3))
-        out["mc_T%d" % T] = r
-        print("mc_threads", T, {k: r[k] for k in ("scored_sequences_per_s", "ms_per_iteration", "kernel_ms_per_iteration", "host_us_per_iteration", "frac_of_kernel_only_rate", "host_threads")}, flush=True)
-    eng.close()
 
 if "sweep" in sys.argv[1:] or len(sys.argv) == 1:
     for R in (32, 64, 128, 256):
