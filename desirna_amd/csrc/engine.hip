@@ -28,6 +28,7 @@
 #include "fold_pf_lds.hpp"
 #include "fold_pf_strip.hpp"
 #include "fold_subopt.hpp"
+#include "fold_cofold_subopt.hpp"
 #include "host_driver.hpp"
 #include "tables.hpp"
 
@@ -1294,6 +1295,37 @@ extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const ch
     HIP_TRY(hipMemcpy(mfe_ss, e->d_ss, (size_t)R * L, hipMemcpyDeviceToHost));
   }
   if (want_ev) HIP_TRY(hipMemcpy(Ed, e->d_Ed, (size_t)R * e->n_targets * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return DRNA_OK;
+}
+
+// ---------------------------------------------------------------- second-best co-fold energy (two strands, -nd on)
+
+extern "C" int drna_cofold_subopt_energy_batch(drna_engine* e, int R, int L, int cut, const char* seqs, int32_t* E2, int32_t* E12) {
+  if (!e) return DRNA_ERR_ARG;
+  if (R < 1 || R > e->max_R || L < 2 || L > e->max_L || cut < 1 || cut >= L || !seqs || !E2) {
+    e->err = "drna_cofold_subopt_energy_batch: bad argument (R, L within the engine's limits, 1 <= cut < L; seqs and E2 required)";
+    return DRNA_ERR_ARG;
+  }
+  if (R > e->ws_slots) { e->err = "drna_cofold_subopt_energy_batch: batch larger than the workspace (raise DRNA_WS_GB or split the batch)"; return DRNA_ERR_ARG; }
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
+  const int ld = L + 2;
+  for (int k = 0; k < e->max_R; k++) e->h_status[k] = ST_OK;
+  CoSubArgs a;
+  a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = e->d_seqs; a.L = L; a.cut = cut; a.ld = ld;
+  a.DuplexInit = e->H.DuplexInit;
+  a.ws = reinterpret_cast<int32_t*>(e->d_ws_pf); a.ws_stride = 2 * (long long)pf_ws_stride(ld);   // int32 units of the PF workspace
+  a.E2 = e->d_Emfe; a.E12 = reinterpret_cast<int32_t*>(e->d_Epf); a.status = e->d_status;
+  HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
+  hipLaunchKernelGGL(cofold_subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
+  HIP_TRY(hipStreamSynchronize(e->s_mfe));
+  HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
+  e->timing[1] = e->timing[2] = 0.f; e->timing[3] = e->timing[0];
+  { const int rc = fold_status(e, R, true, false, nullptr, 0, "unexpected status of the second-best co-fold"); if (rc != DRNA_OK) return rc; }
+  HIP_TRY(hipMemcpy(E2, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (E12) HIP_TRY(hipMemcpy(E12, e->d_Epf, (size_t)2 * R * sizeof(int32_t), hipMemcpyDeviceToHost));
   return DRNA_OK;
 }
 

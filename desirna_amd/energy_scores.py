@@ -16,7 +16,8 @@ Two strands (``oligo_state`` heterodimer / homodimer, and ``avoid`` = ``-o on``)
 ``utils/dimer_multichain_energy.py`` are computed here from its free energies.
 
 ``-nd on`` (negative design): the energy of the second-best structure comes from ``Engine.subopt_energy`` (two-best
-dynamic programme on the GPU; no golden in the reference: checked against exhaustive enumeration).
+dynamic programme on the GPU; no golden in the reference: checked against exhaustive enumeration), for two strands from
+``Engine.cofold_subopt_energy`` (the same programme under the co-fold rules).
 """
 from . import engine as _engine
 from .sim_score import batch_metrics
@@ -158,8 +159,6 @@ class ReplicaScorer:
         if self.oligo_state not in ("none", "avoid", "heterodimer", "homodimer"):
             raise ValueError("unknown oligo_state %r" % self.oligo_state)
         self.subopt = getattr(sim_options, "subopt", "off") == "on"
-        if self.subopt and self.oligo_state in ("heterodimer", "homodimer"):
-            raise NotImplementedError("-nd on with two-strand inputs")
         self.input_file = input_file
         self.sim_options = sim_options
         self.target = input_file.sec_struct.replace("&", "")
@@ -243,8 +242,9 @@ class ReplicaScorer:
 
     def _score_two_strands(self, seqs):
         """reference score_sequence() for oligo_state heterodimer / homodimer (:70-118): Epf = pf_dimer()[-1] (FAB), MFE
-        structure of mfe_dimer() with the '&' re-inserted, E(target) of the two-strand evaluation, then the oligomer bonus
-        (hetero-dimer, or homodimer with two different structures) or the monomer-fraction term (two equal structures)."""
+        structure of mfe_dimer() with the '&' re-inserted, E(target) of the two-strand evaluation, with -nd on the second-best
+        co-fold energy of the solved candidates, then the oligomer bonus (hetero-dimer, or homodimer with two different
+        structures) or the monomer-fraction term (two equal structures), then the motifs -- the reference's order of additions."""
         out = self.engine.cofold_batch(seqs, _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL)
         metrics = batch_metrics(self.input_file.sec_struct.replace("&", "Ee"),
                                 [s.replace("&", "Ee") for s in out["mfe_ss"]])
@@ -271,10 +271,21 @@ class ReplicaScorer:
                 sc.oligomer_bonus = float(kTlog_oligo_fraction(sc.oligo_fraction))
             else:
                 sc.oligomer_bonus = float(kTlog_monomer_fraction(sc.oligo_fraction))
+            res.append(sc)
+        if self.subopt:
+            # reference :105-108 (-nd on) on the dimer fold compound: for solved candidates (1-MCC == 0) the energy of the
+            # first sub-optimal co-fold structure, before the oligomer / monomer bonus
+            hit = [k for k, sc in enumerate(res) if sc.mcc == 0]
+            if hit:
+                e2 = self.engine.cofold_subopt_energy([seqs[k] for k in hit])
+                for k, v in zip(hit, e2):
+                    res[k].get_subopt_e(int(v) / 100.0)
+                    res[k].get_esubopt_minus_Epf(res[k].Epf, res[k].subopt_e)
+                    res[k].get_scoring_function_w_subopt()
+        for seq, sc in zip(seqs, res):
             sc.scoring_function = sc.scoring_function + sc.oligomer_bonus
             if getattr(self.sim_options, "motifs", None):
                 sc.update_scoring_function_w_motifs(score_motifs(seq, self.sim_options))
-            res.append(sc)
         return res
 
 

@@ -25,6 +25,7 @@ EXPORTS = ("drna_create", "drna_destroy", "drna_last_error", "drna_set_targets",
            "drna_score_batch_device", "drna_last_timing", "drna_info", "drna_simscore_batch", "drna_propose_batch",
            "drna_metropolis_batch", "drna_ensemble_defect_batch", "drna_ensemble_defect_batch_device",
            "drna_last_edef_timing", "drna_propose_batch_alt", "drna_set_targets_ragged", "drna_score_ragged", "drna_cofold_batch", "drna_mc_run", "drna_subopt_energy_batch",
+           "drna_cofold_subopt_energy_batch",
            "drna_subopt_structs_batch", "drna_rng_seed", "drna_rng_random", "drna_set_option", "drna_timing_sums", "drna_debug_strip_clocks", "drna_get_option", "drna_abi_version")
 
 ABI_VERSION = 3        # DRNA_ABI_VERSION this binding was written against (include/desirna_amd.h)
@@ -90,6 +91,8 @@ def load_library(path=None):
                               C.c_double, ci, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.drna_subopt_energy_batch.restype = ci
     L.drna_subopt_energy_batch.argtypes = [vp, ci, ci, C.c_char_p, vp, vp]
+    L.drna_cofold_subopt_energy_batch.restype = ci
+    L.drna_cofold_subopt_energy_batch.argtypes = [vp, ci, ci, ci, C.c_char_p, vp, vp]
     L.drna_subopt_structs_batch.restype = ci
     L.drna_subopt_structs_batch.argtypes = [vp, ci, ci, C.c_char_p, ci, vp, vp]
     L.drna_simscore_batch.restype = ci
@@ -305,6 +308,25 @@ class Engine:
         E12 = np.zeros((R, 2), dtype=np.int32) if want_both else None
         self._check(self._L.drna_subopt_energy_batch(self._h, R, L, "".join(seqs).encode("ascii"), E2.ctypes.data,
                                                      E12.ctypes.data if want_both else None))
+        return (E2, E12) if want_both else E2
+
+    def cofold_subopt_energy(self, seqs, want_both=False):
+        """Two strands: energy (dcal/mol) of the second-best co-fold structure of each 'AAAA&BBBB' pair as the reference's -nd on
+        path takes it from ViennaRNA's subopt on the dimer fold compound (0 if none within 49 kcal/mol); with want_both also
+        the (R, 2) array of the two lowest energies (second = 10000000 if there is one structure only)."""
+        a0, b0 = seqs[0].split("&")
+        cut, L = len(a0), len(a0) + len(b0)
+        flat = []
+        for s in seqs:
+            a, b = s.split("&")
+            if len(a) != cut or len(a) + len(b) != L:
+                raise ValueError("all pairs of a batch must have the same strand lengths")
+            flat.append(a + b)
+        R = len(flat)
+        E2 = np.zeros(R, dtype=np.int32)
+        E12 = np.zeros((R, 2), dtype=np.int32) if want_both else None
+        self._check(self._L.drna_cofold_subopt_energy_batch(self._h, R, L, cut, "".join(flat).encode("ascii"), E2.ctypes.data,
+                                                            E12.ctypes.data if want_both else None))
         return (E2, E12) if want_both else E2
 
     def subopt_structs(self, seqs, K):

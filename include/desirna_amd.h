@@ -138,6 +138,18 @@ int drna_cofold_batch(drna_engine *e, int R, int L, int cut, const char *seqs, u
 int drna_subopt_energy_batch(drna_engine *e, int R, int L, const char *seqs, int32_t *E2, int32_t *E12);
 
 /*
+ * Energy of the second-best CO-FOLD structure of R sequence pairs (negative design with two strands, -nd on with an '&'
+ * target).  Replaces get_first_suboptimal_structure_and_energy(seq, fc, 1)[1] on the dimer fold compound of the reference's
+ * two-strand branch (utils/energy_scores.py:105-108, :453-488).  Pairs as for drna_cofold_batch: total length L, both
+ * strands concatenated WITHOUT the '&', the first strand `cut` nucleotides long (1 <= cut < L).  The structures are those
+ * of drna_cofold_batch's MFE (DuplexInit iff a pair joins the strands); two equal strands are not reduced by symmetry (a
+ * structure and its rotation are two structures).
+ *   E2   R int32, dcal/mol; 0 when no second structure lies within 4900 dcal/mol of the co-fold MFE (the reference's fallback)
+ *   E12  R*2 int32, may be NULL: the two lowest structure energies (second = 10000000 if there is one structure only)
+ */
+int drna_cofold_subopt_energy_batch(drna_engine *e, int R, int L, int cut, const char *seqs, int32_t *E2, int32_t *E12);
+
+/*
  * The K lowest-energy structures of R sequences, energies and dot-bracket strings.  Replaces
  * get_first_suboptimal_structure_and_energy(seq, fc, k)[0] for k = 1 .. #alternative structures, the call behind
  * get_alt_mcc() (utils/sequence_utils.py:766-793, utils/energy_scores.py:453-488): entry k of ViennaRNA's energy-sorted
