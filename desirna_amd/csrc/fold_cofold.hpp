@@ -74,27 +74,11 @@ __global__ __launch_bounds__(NT) void cofold_mfe_kernel(CoArgs A) {
   int32_t* FML = base + tab;
   int32_t* EXT = base + 2 * tab;
 
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
-  for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
-  }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
-  if (tid == 0) sm.flag = 0;
-  __syncthreads();
-  const char* seq = A.seqs + (long long)r * n;
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-    sm.ssw[k] = '.';
-  }
+  stage_energy_tables<NT>(sm, T, tid);
+  for (int k = tid; k < n; k += NT) sm.ssw[k] = '.';
   for (int k = tid; k < ld; k += NT) FML[k] = INF;           // row 0: empty segments
   for (int k = tid; k <= n + 2; k += NT) { sm.fcA[k] = 0; sm.fcB[k] = 0; }
-  __syncthreads();
-  if (tid == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
-  __syncthreads();
+  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.Emfe[r] = 0; }
     for (int k = tid; k < n; k += NT) A.ss[(long long)r * n + k] = '.';
@@ -421,31 +405,14 @@ __global__ __launch_bounds__(NT) void cofold_pf_kernel(CoArgs A) {
   unsigned char* INFO = reinterpret_cast<unsigned char*>(base + 3 * tab);
   int32_t* status = A.status_pf;
 
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
-  for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
-  }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
-  if (tid == 0) sm.flag = 0;
-  __syncthreads();
-  const char* seq = A.seqs + (long long)r * n;
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-  }
+  stage_energy_tables<NT>(sm, T, tid);
   for (int k = tid; k < ld; k += NT) { QM[k] = 0.0; QM1[k] = 0.0; QB[k] = 0.0; INFO[k] = 0; }   // row 0
-  for (int k = tid; k <= n + 2; k += NT) { sm.qA3[k] = 1.0; sm.qB5[k] = 1.0; }
-  __syncthreads();
-  if (tid == 0) {
-    sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1];
-    // one-nucleotide segments next to the nick (the sweep advances these arrays from diagonal 1 on)
-    if (cut >= 1) sm.qA3[cut] = A.scale[1];
-    if (cut >= 1 && cut + 1 <= n) sm.qB5[cut + 1] = A.scale[1];
+  // empty segments, and the one-nucleotide segments next to the nick (the sweep advances these arrays from diagonal 1 on)
+  for (int k = tid; k <= n + 2; k += NT) {
+    sm.qA3[k] = cut >= 1 && k == cut ? A.scale[1] : 1.0;
+    sm.qB5[k] = cut >= 1 && k == cut + 1 && k <= n ? A.scale[1] : 1.0;
   }
-  __syncthreads();
+  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
   if (sm.flag) {
     if (tid == 0) { status[r] = ST_BAD_CHAR; for (int k = 0; k < 4; k++) A.F4[r * 4 + k] = 0.0; }
     return;

@@ -61,27 +61,11 @@ __global__ __launch_bounds__(NT) void cofold_subopt_kernel(CoSubArgs A) {
   Top2* M = reinterpret_cast<Top2*>(base + 2 * tab);
   Top2* M2 = reinterpret_cast<Top2*>(base + 4 * tab);
 
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
-  for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
-  }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
-  if (tid == 0) sm.flag = 0;
-  __syncthreads();
-  const char* seq = A.seqs + (long long)r * n;
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-  }
+  stage_energy_tables<NT>(sm, T, tid);
   // row 0 (single nucleotides): no pair, no multiloop content
   for (int k = tid; k < ld; k += NT) { C[k] = Top2{INF, INF}; M[k] = Top2{INF, INF}; M2[k] = Top2{INF, INF}; }
   for (int k = tid; k <= n + 2; k += NT) { sm.fcA[k] = Top2{0, INF}; sm.fcB[k] = Top2{0, INF}; }   // empty / one-nt segments
-  __syncthreads();
-  if (tid == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
-  __syncthreads();
+  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.E2[r] = 0; if (A.E12) { A.E12[2 * r] = 0; A.E12[2 * r + 1] = INF_REF; } }
     return;

@@ -31,6 +31,9 @@ struct Ragged {
   const int* idx = nullptr;
   const int* len = nullptr;
   const int* off = nullptr;
+  __device__ int seq_of(int b) const { return idx ? idx[b] : b; }                      // workgroup slot b -> sequence
+  __device__ int len_of(int r, int L) const { return len ? len[r] : L; }               // L: the uniform batch's length
+  __device__ long long off_of(int r, int L) const { return off ? (long long)off[r] : (long long)r * L; }
 };
 
 // ---- two-workgroup kernel (fold_mfe_dual.hpp): one sequence is folded by a MAIN workgroup (finalize,
@@ -221,6 +224,96 @@ __device__ __forceinline__ int rtype_of(int t) {
   // {0,2,1,4,3,6,5,7}
   const unsigned lut = 0x75634120u;
   return (int)((lut >> (t * 4)) & 15u);
+}
+
+// ---- kernel prologues
+
+// the energy tables every fold kernel keeps in LDS, from MfeTables (int) or PfTables (double): the members have the same names
+template <int NT, class SM, class TAB>
+__device__ __forceinline__ void stage_energy_tables(SM& sm, const TAB& T, int tid) {
+  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
+  for (int k = tid; k < 128; k += NT) {
+    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
+    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
+  }
+  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
+  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
+}
+
+// S[1..n] = nucleotide codes of seq, S[0] = S[n], S[n+1] = S[1].  sm.flag ends as 1 if seq holds a bad character (coded as A),
+// else 0; the barriers order everything written before the call, too.  The caller takes its own exit on sm.flag.
+template <int NT, class SM>
+__device__ __forceinline__ void load_sequence(SM& sm, const char* seq, int n, int tid) {
+  if (tid == 0) sm.flag = 0;
+  __syncthreads();
+  for (int k = tid; k < n; k += NT) {
+    const int c = enc_nt(seq[k]);
+    if (c < 0) sm.flag = 1;
+    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
+  }
+  __syncthreads();
+  if (tid == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
+  __syncthreads();
+}
+
+// one wave: list of the cells (i, i+d) whose codes can pair (ascending i), and the inverse map; double-buffered by diagonal parity.
+// codes: sm.S, or the pairing codes sm.Sp of a pseudoknot round (4 = must stay unpaired)
+template <class SM>
+__device__ __forceinline__ void build_plist(SM& sm, const unsigned char* codes, int d, int n, int lane) {
+  const int par = d & 1;
+  int cnt = 0;
+  for (int i0 = 1; i0 <= n - d; i0 += WAVE) {
+    const int i = i0 + lane;
+    const bool on = i <= n - d && pair_type(codes[i], codes[i + d]) != 0;
+    const unsigned long long m = __ballot(on);
+    if (on) {
+      const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
+      sm.plist[par][pos] = (unsigned short)i;
+      sm.cpos[par][i] = (unsigned short)pos;
+    }
+    cnt += __popcll(m);
+  }
+  if (lane == 0) sm.pcnt[par] = cnt;
+}
+
+// ---- pseudoknot rounds of the MFE kernels: round k pairs what earlier rounds left unpaired and is written with bracket pair k
+
+__device__ __forceinline__ void pk_brackets(int round, char& op, char& cl) {
+  op = round == 0 ? '(' : round == 1 ? '[' : round == 2 ? '<' : '{';
+  cl = round == 0 ? ')' : round == 1 ? ']' : round == 2 ? '>' : '}';
+}
+
+// before round 0: every nucleotide may pair (Sp = S; both wrap ends 4), nothing is annotated yet
+template <int NT, class SM>
+__device__ __forceinline__ void pk_start(SM& sm, int n, int tid) {
+  for (int k = tid; k <= n + 1; k += NT) sm.Sp[k] = k >= 1 && k <= n ? sm.S[k] : 4;
+  for (int k = tid; k < n; k += NT) sm.sspk[k] = '.';
+  __syncthreads();
+}
+
+// merge the structure of this round (ssw) into the annotated one (sspk); positions paired so far may not pair in the next round.
+// Returns whether another round follows (reference sequence_utils.py:1194,1210: the next re-fold happens only if this one found a
+// pair).  sm.flag is 0 again on return.
+template <int NT, class SM>
+__device__ __forceinline__ bool pk_merge_round(SM& sm, int n, int round) {
+  const int tid = threadIdx.x;
+  char op, cl;
+  pk_brackets(round, op, cl);
+  __syncthreads();
+  int any = 0;
+  for (int k = tid; k < n; k += NT) {
+    const char ch = sm.ssw[k];
+    if (ch == '(') { sm.sspk[k] = op; any = 1; }
+    else if (ch == ')') sm.sspk[k] = cl;
+    if (sm.sspk[k] != '.') sm.Sp[k + 1] = 4;      // hc 'x': already paired positions stay unpaired
+  }
+  if (any) sm.flag = 2;
+  __syncthreads();
+  const bool more = (round == 0) || (sm.flag == 2);
+  __syncthreads();
+  if (tid == 0) sm.flag = 0;
+  __syncthreads();
+  return more;
 }
 
 // ---- strip kernels (fold_pf_strip.hpp, fold_mfe_strip.hpp): one sequence folded by several workgroups, each owning a strip

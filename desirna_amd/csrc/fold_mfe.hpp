@@ -67,24 +67,6 @@ struct MfeSmem : MfeSmemCore<MAXN> {
   i32x4 plan_qL[NPAIR_MAX];
 };
 
-// one wave: list of the cells (i, i+d) that can pair (hard constraints of the pseudoknot rounds included)
-__device__ __forceinline__ void mfe_build_plist(MfeSmem& sm, int d, int n, int lane) {
-  const int par = d & 1;
-  int cnt = 0;
-  for (int i0 = 1; i0 <= n - d; i0 += WAVE) {
-    const int i = i0 + lane;
-    const bool on = i <= n - d && pair_type(sm.Sp[i], sm.Sp[i + d]) != 0;
-    const unsigned long long m = __ballot(on);
-    if (on) {
-      const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
-      sm.plist[par][pos] = (unsigned short)i;
-      sm.cpos[par][i] = (unsigned short)pos;
-    }
-    cnt += __popcll(m);
-  }
-  if (lane == 0) sm.pcnt[par] = cnt;
-}
-
 // ---- loop energies on the device (per-lane arguments; used by finalize and traceback)
 
 // ViennaRNA E_Hairpin for the pair (i,j) of type t; e = size term hairpin[u] (log-extrapolated beyond 30)
@@ -187,7 +169,7 @@ __device__ void mfe_fill(MfeSmem& sm, const MfeArgs& A, int32_t* __restrict__ Wc
     sm.plan_q[p] = P.u1[e] | (P.u2[e] << 8);
     sm.plan_qL[p] = i32x4{P.L[e], c > 1 ? P.L[e + 1] : INF, c > 2 ? P.L[e + 2] : INF, c > 3 ? P.L[e + 3] : INF};
   }
-  if (wave == 0 && TURN + 1 < n) mfe_build_plist(sm, TURN + 1, n, lane);
+  if (wave == 0 && TURN + 1 < n) build_plist(sm, sm.Sp, TURN + 1, n, lane);
   __syncthreads();
   const auto rsF = __builtin_amdgcn_make_buffer_rsrc((void*)FML, (short)0, (int)((long long)ld * ld * 4), 0x00020000);
   const auto rsC = __builtin_amdgcn_make_buffer_rsrc((void*)CI, (short)0, (int)((long long)ld * ld * 4), 0x00020000);
@@ -356,7 +338,7 @@ __device__ void mfe_fill(MfeSmem& sm, const MfeArgs& A, int32_t* __restrict__ Wc
       DML[d * ld + i] = dec;
       FML[d * ld + i] = min(f, dec);
     }
-    if (wave == NW - 1 && d + 1 < n) mfe_build_plist(sm, d + 1, n, lane);     // list of the next diagonal
+    if (wave == NW - 1 && d + 1 < n) build_plist(sm, sm.Sp, d + 1, n, lane);     // list of the next diagonal
     __syncthreads();
   }
 
@@ -655,9 +637,9 @@ __device__ inline bool mfe_traceback(SM& sm, const MfeArgs& A, const int32_t* __
 template <int NT>
 __global__ __launch_bounds__(NT) void mfe_kernel(MfeArgs A) {
   __shared__ MfeSmem sm;
-  const int r = A.rg.idx ? A.rg.idx[blockIdx.x] : blockIdx.x;
-  if (A.rg.len) A.L = A.rg.len[r];
-  const long long so = A.rg.off ? (long long)A.rg.off[r] : (long long)r * A.L;      // offset in seqs / ss
+  const int r = A.rg.seq_of(blockIdx.x);
+  A.L = A.rg.len_of(r, A.L);
+  const long long so = A.rg.off_of(r, A.L);      // offset in seqs / ss
   const int n = A.L, ld = A.ld, tid = threadIdx.x;
   const MfeTables& T = *A.T;
   int32_t* base = A.ws + (long long)r * A.ws_stride;
@@ -668,34 +650,14 @@ __global__ __launch_bounds__(NT) void mfe_kernel(MfeArgs A) {
   int32_t* DML = base + 3 * tab;
   int32_t* EXT = base + 4 * tab;
 
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
-  for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
-  }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
-  if (tid == 0) sm.flag = 0;
-  __syncthreads();
-  const char* seq = A.seqs + so;
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-    sm.Sp[k + 1] = (unsigned char)(c < 0 ? 4 : c);
-    sm.sspk[k] = '.';
-  }
-  __syncthreads();
-  if (tid == 0) {
-    sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1];
-    sm.Sp[0] = 4; sm.Sp[n + 1] = 4;
-  }
-  __syncthreads();
+  stage_energy_tables<NT>(sm, T, tid);
+  load_sequence<NT>(sm, A.seqs + so, n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.Emfe[r] = 0; }
     for (int k = tid; k < n; k += NT) A.ss[so + k] = '.';
     return;
   }
+  pk_start<NT>(sm, n, tid);
 
   int status = ST_OK;
   for (int round = 0; round <= A.pk_rounds; round++) {
@@ -710,25 +672,7 @@ __global__ __launch_bounds__(NT) void mfe_kernel(MfeArgs A) {
     }
     __syncthreads();
     if (sm.flag) { status = ST_TRACEBACK; break; }
-    // merge this round into the annotated structure; bracket family of round k: () [] <> {}
-    const char op = round == 0 ? '(' : round == 1 ? '[' : round == 2 ? '<' : '{';
-    const char cl = round == 0 ? ')' : round == 1 ? ']' : round == 2 ? '>' : '}';
-    __syncthreads();
-    int any = 0;
-    for (int k = tid; k < n; k += NT) {
-      const char ch = sm.ssw[k];
-      if (ch == '(') { sm.sspk[k] = op; any = 1; }
-      else if (ch == ')') sm.sspk[k] = cl;
-      if (sm.sspk[k] != '.') sm.Sp[k + 1] = 4;      // hc 'x': already paired positions stay unpaired
-    }
-    if (any) sm.flag = 2;
-    __syncthreads();
-    // reference sequence_utils.py:1194,1210: the next re-fold happens only if this one found a pair
-    const bool more = (round == 0) || (sm.flag == 2);
-    __syncthreads();
-    if (tid == 0) sm.flag = 0;
-    __syncthreads();
-    if (!more) break;
+    if (!pk_merge_round<NT>(sm, n, round)) break;
   }
   for (int k = tid; k < n; k += NT) A.ss[so + k] = sm.sspk[k];
   if (tid == 0) A.status[r] = status;

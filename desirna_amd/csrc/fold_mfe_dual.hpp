@@ -65,17 +65,9 @@ __device__ __forceinline__ void mfe_helper(MfeHelperSmem<NT>& sm, MfeArgs A, int
   for (int k = tid; k < 33 * RS; k += NT) sm.wring[k] = INF * 256;
   for (int k = tid; k < SM::NSLOT; k += NT)
     for (int p = 0; p < 2; p++) { sm.accK[p][k] = INF; sm.accI[p][k] = INF; }
-  if (tid == 0) { sm.flag = 0; sm.fail = 0; sm.failr[0] = 0; sm.failr[1] = 0; }
-  __syncthreads();
-  const char* seq = A.seqs + (long long)r * n;
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-  }
-  __syncthreads();
+  if (tid == 0) { sm.fail = 0; sm.failr[0] = 0; sm.failr[1] = 0; }
+  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
   if (sm.flag) return;                               // the main workgroup reports the bad character
-  if (tid == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
   const int e_bulge1 = keep_i32(T.bulge[1]), e_int23 = keep_i32(T.interior[5] + T.ninio);
 
   // pairable cells of diagonal dn (i | pair info << 8, as in the main workgroup's list) and the far-shape table, rebuilt here

@@ -428,6 +428,40 @@ __device__ __forceinline__ void mfe_init_eshape(SM& sm, const MfeTables& T, int 
   }
 }
 
+// Shape slots of the 16-lane-row E items (mfe_e_item_rows): lane l of a row takes the eight shape slots 16 k + l of its cell.
+// Slots < 64 bulges (x < 29: (0,u) u = x+2; x < 58: (u,0) u = x-27), slots >= 64 1xn loops (y = x-64 < 27: (1,u) u = y+3;
+// y < 54: (u,1) u = y-24).  The spare slots carry the nine small shapes with tables of their own, told apart by a
+// kind field: x = 58..60 the (1,2) (2,1) (2,2) loops (kinds 5..7: energy staged per cell), y = 54..59 stack (1),
+// the two 1-bulges (2), 1x1 (3), (2,3) and (3,2) (4); what is left is padding with an unreachable size term
+template <int NT, class SM>
+__device__ __forceinline__ void mfe_init_eshape_rows(SM& sm, const MfeTables& T, int tid) {
+  for (int x = tid; x < 128; x += NT) {
+    int s_, u1_, L_, kind_ = 0;
+    if (x < 64) {
+      const bool on = x < 58;
+      u1_ = (x < 29 || !on) ? 0 : x - 27;
+      s_ = !on ? 2 : x < 29 ? x + 2 : x - 27;
+      L_ = on ? T.bulge[s_] : 0x3fff;
+      if (x >= 58 && x <= 60) { kind_ = x - 53; s_ = x == 60 ? 4 : 3; u1_ = x == 58 ? 1 : 2; L_ = 0; }
+    } else {
+      const int y = x - 64;
+      const bool on = y < 54;
+      u1_ = (y < 27 || !on) ? 1 : y - 24;
+      s_ = !on ? 4 : y < 27 ? y + 4 : y - 23;
+      const int nl = s_ - 1;
+      L_ = on ? T.interior[nl + 1] + min(T.max_ninio, (nl - 1) * T.ninio) : 0x3fff;
+      if (y >= 54 && y <= 59) {
+        const int z = y - 54;                 // (0,0) (0,1) (1,0) (1,1) (2,3) (3,2)
+        kind_ = z == 0 ? 1 : z <= 2 ? 2 : z == 3 ? 3 : 4;
+        s_ = z == 0 ? 0 : z <= 2 ? 1 : z == 3 ? 2 : 5;
+        u1_ = z <= 1 ? 0 : z <= 3 ? 1 : z - 2;
+        L_ = 0;
+      }
+    }
+    sm.eshape_rows[x] = s_ | (kind_ << 5) | (u1_ << 8) | (L_ << 16);
+  }
+}
+
 // E item of the one-workgroup kernel: four pairable cells per item, one per 16-lane row; a lane folds its eight shape slots in
 // registers, the row minimum takes four DPP steps for all four cells at once, lane 15 of each row is the only writer.  Slots
 // 3 and 7 of some lanes are the nine small shapes (see eshape_rows): same ring read, but the energy comes from the cell's
@@ -630,36 +664,7 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
   for (int k = tid; k < MfeFastSmem<NT>::NSLOT; k += NT)
     for (int p = 0; p < 2; p++) { sm.accG[p][k] = INF; sm.accI[p][k] = INF; sm.accK[p][k] = INF; }
   mfe_init_eshape(sm, T, tid, NT);
-  for (int x = tid; x < 128; x += NT) {
-    // E items: a 16-lane row works on one pairable cell; lane l of the row takes the eight shape slots 16 k + l:
-    // slots < 64 bulges (x < 29: (0,u) u = x+2; x < 58: (u,0) u = x-27), slots >= 64 1xn loops (y = x-64 < 27: (1,u) u = y+3;
-    // y < 54: (u,1) u = y-24).  The spare slots carry the nine small shapes with tables of their own, told apart by a
-    // kind field: x = 58..60 the (1,2) (2,1) (2,2) loops (kinds 5..7: energy staged per cell), y = 54..59 stack (1),
-    // the two 1-bulges (2), 1x1 (3), (2,3) and (3,2) (4); what is left is padding with an unreachable size term
-    int s_, u1_, L_, kind_ = 0;
-    if (x < 64) {
-      const bool on = x < 58;
-      u1_ = (x < 29 || !on) ? 0 : x - 27;
-      s_ = !on ? 2 : x < 29 ? x + 2 : x - 27;
-      L_ = on ? T.bulge[s_] : 0x3fff;
-      if (x >= 58 && x <= 60) { kind_ = x - 53; s_ = x == 60 ? 4 : 3; u1_ = x == 58 ? 1 : 2; L_ = 0; }
-    } else {
-      const int y = x - 64;
-      const bool on = y < 54;
-      u1_ = (y < 27 || !on) ? 1 : y - 24;
-      s_ = !on ? 4 : y < 27 ? y + 4 : y - 23;
-      const int nl = s_ - 1;
-      L_ = on ? T.interior[nl + 1] + min(max_ninio, (nl - 1) * ninio) : 0x3fff;
-      if (y >= 54 && y <= 59) {
-        const int z = y - 54;                 // (0,0) (0,1) (1,0) (1,1) (2,3) (3,2)
-        kind_ = z == 0 ? 1 : z <= 2 ? 2 : z == 3 ? 3 : 4;
-        s_ = z == 0 ? 0 : z <= 2 ? 1 : z == 3 ? 2 : 5;
-        u1_ = z <= 1 ? 0 : z <= 3 ? 1 : z - 2;
-        L_ = 0;
-      }
-    }
-    sm.eshape_rows[x] = s_ | (kind_ << 5) | (u1_ << 8) | (L_ << 16);
-  }
+  mfe_init_eshape_rows<NT>(sm, T, tid);
   for (int k = tid; k < 32; k += NT) {
     sm.twc[k][0] = k >= 4 && k <= 30 ? min(max_ninio, (k - 4) * ninio) : INF;
     sm.twc[k][1] = k >= 6 && k <= 30 ? T.interior[k] : INF;
@@ -1054,8 +1059,8 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
 // it to its helper); every exit publishes DONE so that the helper leaves too
 template <int NT, bool DUAL>
 __device__ __forceinline__ void mfe_lds_body(MfeFastSmem<NT>& sm, MfeArgs A, int r, DualLink lk) {
-  if (A.rg.len) A.L = A.rg.len[r];
-  const long long so = A.rg.off ? (long long)A.rg.off[r] : (long long)r * A.L;      // offset in seqs / ss
+  A.L = A.rg.len_of(r, A.L);
+  const long long so = A.rg.off_of(r, A.L);      // offset in seqs / ss
   const int n = A.L, ld = A.ld, tid = threadIdx.x;
   const MfeTables& T = *A.T;
   int32_t* base = A.ws + (long long)r * A.ws_stride;
@@ -1072,6 +1077,8 @@ __device__ __forceinline__ void mfe_lds_body(MfeFastSmem<NT>& sm, MfeArgs A, int
   const bool ptl_on = Wc == A.ws && tid == 0;
   if (ptl_on) { ptl[0] = (long long)wall_clock64(); ptl[12287] = 0; }
 #endif
+  // (stage_energy_tables, written out: through the helper the three kernels with this body spill differently, scratch 336 -> 348
+  // bytes per lane in mfe_lds_kernel)
   for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
   for (int k = tid; k < 128; k += NT) {
     sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
@@ -1079,27 +1086,14 @@ __device__ __forceinline__ void mfe_lds_body(MfeFastSmem<NT>& sm, MfeArgs A, int
   }
   for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
   for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
-  if (tid == 0) { sm.flag = 0; sm.sync_fail = 0; }
-  __syncthreads();
-  const char* seq = A.seqs + so;
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-    sm.Sp[k + 1] = (unsigned char)(c < 0 ? 4 : c);
-    sm.sspk[k] = '.';
-  }
-  __syncthreads();
-  if (tid == 0) {
-    sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1];
-    sm.Sp[0] = 4; sm.Sp[n + 1] = 4;
-  }
-  __syncthreads();
+  if (tid == 0) sm.sync_fail = 0;
+  load_sequence<NT>(sm, A.seqs + so, n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.Emfe[r] = 0; if (DUAL) st_agent(lk.flagA, dual_done(lk.epoch)); }
     for (int k = tid; k < n; k += NT) A.ss[so + k] = '.';
     return;
   }
+  pk_start<NT>(sm, n, tid);
 
   int status = ST_OK;
   for (int round = 0; round <= A.pk_rounds; round++) {
@@ -1134,23 +1128,7 @@ __device__ __forceinline__ void mfe_lds_body(MfeFastSmem<NT>& sm, MfeArgs A, int
     }
     __syncthreads();
     if (sm.flag) { status = ST_TRACEBACK; break; }
-    const char op = round == 0 ? '(' : round == 1 ? '[' : round == 2 ? '<' : '{';
-    const char cl = round == 0 ? ')' : round == 1 ? ']' : round == 2 ? '>' : '}';
-    __syncthreads();
-    int any = 0;
-    for (int k = tid; k < n; k += NT) {
-      const char ch = sm.ssw[k];
-      if (ch == '(') { sm.sspk[k] = op; any = 1; }
-      else if (ch == ')') sm.sspk[k] = cl;
-      if (sm.sspk[k] != '.') sm.Sp[k + 1] = 4;
-    }
-    if (any) sm.flag = 2;
-    __syncthreads();
-    const bool more = (round == 0) || (sm.flag == 2);
-    __syncthreads();
-    if (tid == 0) sm.flag = 0;
-    __syncthreads();
-    if (!more) break;
+    if (!pk_merge_round<NT>(sm, n, round)) break;
   }
   if (DUAL && tid == 0) st_agent(lk.flagA, dual_done(lk.epoch));
   for (int k = tid; k < n; k += NT) A.ss[so + k] = sm.sspk[k];
@@ -1160,7 +1138,7 @@ __device__ __forceinline__ void mfe_lds_body(MfeFastSmem<NT>& sm, MfeArgs A, int
 template <int NT>
 __global__ __launch_bounds__(NT) void mfe_lds_kernel(MfeArgs A) {
   __shared__ MfeFastSmem<NT> sm;
-  const int r = A.rg.idx ? A.rg.idx[blockIdx.x] : blockIdx.x;
+  const int r = A.rg.seq_of(blockIdx.x);
   mfe_lds_body<NT, false>(sm, A, r, DualLink{});
 }
 

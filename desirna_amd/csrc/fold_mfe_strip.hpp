@@ -170,8 +170,8 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
   constexpr int NW = SM::NW, RS = SM::RS, P = SM::P, NFIN = SM::NFIN, NSVC = SM::NSVC, NG = SM::NG;
   const MfeTables& T = *A.T;
   const int r = lk.idx ? lk.idx[q] : q + lk.r0;
-  if (A.rg.len) A.L = A.rg.len[r];
-  const long long so = A.rg.off ? (long long)A.rg.off[r] : (long long)r * A.L;
+  A.L = A.rg.len_of(r, A.L);
+  const long long so = A.rg.off_of(r, A.L);
   const int n = A.L, ld = A.ld;
   const int tid = threadIdx.x, lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
@@ -209,13 +209,7 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
   if (lk.clk && tid == 0) lk.clk[((long long)q * STRIP_MAXS + s) * 2] = wall_clock_100mhz();
 
   // ---- prologue: tables
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
-  for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
-  }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
+  stage_energy_tables<NT>(sm, T, tid);
   if (tid == 0) { sm.flag = 0; sm.sync_fail[0] = 0; sm.sync_fail[1] = 0; }
   __syncthreads();
   // local sequence and pairing codes (4 = may not pair: positions paired in an earlier round, and both ends)
@@ -239,32 +233,7 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
   for (int k = tid; k < P; k += NT)
     for (int p = 0; p < 2; p++) { sm.accG[p][k] = INF; sm.accI[p][k] = INF; sm.accK[p][k] = INF; }
   for (int k = tid; k < 2 * NG * (GSLOTS + 2); k += NT) (&sm.gimp[0][0][0])[k] = INF;
-  for (int x = tid; x < 128; x += NT) {
-    // shape slots of the 16-lane-row E items (see mfe_fill_lds)
-    int s_, u1_, L_, kind_ = 0;
-    if (x < 64) {
-      const bool on = x < 58;
-      u1_ = (x < 29 || !on) ? 0 : x - 27;
-      s_ = !on ? 2 : x < 29 ? x + 2 : x - 27;
-      L_ = on ? T.bulge[s_] : 0x3fff;
-      if (x >= 58 && x <= 60) { kind_ = x - 53; s_ = x == 60 ? 4 : 3; u1_ = x == 58 ? 1 : 2; L_ = 0; }
-    } else {
-      const int y = x - 64;
-      const bool on = y < 54;
-      u1_ = (y < 27 || !on) ? 1 : y - 24;
-      s_ = !on ? 4 : y < 27 ? y + 4 : y - 23;
-      const int nl = s_ - 1;
-      L_ = on ? T.interior[nl + 1] + min(max_ninio, (nl - 1) * ninio) : 0x3fff;
-      if (y >= 54 && y <= 59) {
-        const int z = y - 54;
-        kind_ = z == 0 ? 1 : z <= 2 ? 2 : z == 3 ? 3 : 4;
-        s_ = z == 0 ? 0 : z <= 2 ? 1 : z == 3 ? 2 : 5;
-        u1_ = z <= 1 ? 0 : z <= 3 ? 1 : z - 2;
-        L_ = 0;
-      }
-    }
-    sm.eshape_rows[x] = s_ | (kind_ << 5) | (u1_ << 8) | (L_ << 16);
-  }
+  mfe_init_eshape_rows<NT>(sm, T, tid);
   for (int k = tid; k < 32; k += NT) sm.tw_L[k] = k >= 6 && k <= 30 ? T.interior[k] : INF;
   __syncthreads();
   for (int k = tid; k < 64; k += NT) sm.xtab[SM::XT_STACK + k] = sm.stack[k] - ((k & 7) > 2 ? TermAU : 0);
@@ -815,8 +784,8 @@ struct MfeTraceSmem : MfeSmemCore<STRIP_NMAX> {
 __device__ inline void mfe_strip_trace_body(MfeTraceSmem& sm, MfeArgs A, const int* idx, int q, int round, int r0 = 0) {
   constexpr int NT = TRACE_WAVES * WAVE;
   const int r = idx ? idx[q] : q + r0;
-  if (A.rg.len) A.L = A.rg.len[r];
-  const long long so = A.rg.off ? (long long)A.rg.off[r] : (long long)r * A.L;
+  A.L = A.rg.len_of(r, A.L);
+  const long long so = A.rg.off_of(r, A.L);
   const int n = A.L, ld = A.ld, tid = threadIdx.x;
   const MfeTables& T = *A.T;
   int32_t* base = A.ws + (long long)r * A.ws_stride;
@@ -826,6 +795,7 @@ __device__ inline void mfe_strip_trace_body(MfeTraceSmem& sm, MfeArgs A, const i
   const int32_t* EXT = base + 4 * tab;
   const int state = Wc[0];
   if (round > 0 && state != 2) return;                 // no fill this round: the sequence was finished earlier (workgroup-uniform)
+  // (stage_energy_tables, written out: through the helper this kernel takes one VGPR more)
   for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
   for (int k = tid; k < 128; k += NT) {
     sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
@@ -833,27 +803,10 @@ __device__ inline void mfe_strip_trace_body(MfeTraceSmem& sm, MfeArgs A, const i
   }
   for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
   for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
-  if (tid == 0) sm.flag = 0;
-  __syncthreads();
-  const char* seq = A.seqs + so;
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-    const char prev = round > 0 ? A.ss[so + k] : '.';
-    sm.sspk[k] = prev;
-    sm.Sp[k + 1] = (unsigned char)(c < 0 || prev != '.' ? 4 : c);
-    sm.ssw[k] = '.';
-  }
+  for (int k = tid; k < n; k += NT) sm.ssw[k] = '.';
   for (int k = tid; k <= n; k += NT) sm.f5[k] = Wc[ld + k];
   for (int k = tid; k < (int)(sizeof(sm.sec_ml) / sizeof(sm.sec_ml[0])); k += NT) sm.sec_ml[k] = 0;
-  __syncthreads();
-  if (tid == 0) {
-    sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; sm.Sp[0] = 4; sm.Sp[n + 1] = 4;
-    sm.sec_i[0] = 1; sm.sec_j[0] = (short)n; sm.sec_ml[0] = 1;          // entry 0 = the whole exterior interval (ml 0), published
-    sm.tbq[0] = 0; sm.tbq[1] = 1; sm.tbq[2] = 1; sm.tbq[3] = 0;
-  }
-  __syncthreads();
+  load_sequence<NT>(sm, A.seqs + so, n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.Emfe[r] = 0; Wc[0] = 0; }
     for (int k = tid; k < n; k += NT) A.ss[so + k] = '.';
@@ -864,6 +817,18 @@ __device__ inline void mfe_strip_trace_body(MfeTraceSmem& sm, MfeArgs A, const i
     for (int k = tid; k < n; k += NT) A.ss[so + k] = '.';
     return;
   }
+  // pairing codes of this round: 4 where an earlier round paired, and at both ends
+  for (int k = tid; k < n; k += NT) {
+    const char prev = round > 0 ? A.ss[so + k] : '.';
+    sm.sspk[k] = prev;
+    sm.Sp[k + 1] = prev != '.' ? 4 : sm.S[k + 1];
+  }
+  if (tid == 0) {
+    sm.Sp[0] = 4; sm.Sp[n + 1] = 4;
+    sm.sec_i[0] = 1; sm.sec_j[0] = (short)n; sm.sec_ml[0] = 1;          // entry 0 = the whole exterior interval (ml 0), published
+    sm.tbq[0] = 0; sm.tbq[1] = 1; sm.tbq[2] = 1; sm.tbq[3] = 0;
+  }
+  __syncthreads();
   (void)mfe_traceback_q(sm, A, Wc, FmlGlobal{FML, ld}, EXT, TbShared<MfeTraceSmem>{sm});
   __syncthreads();
   if (sm.tbq[3] == 2) {                                // a wave could not reproduce a table value
@@ -871,8 +836,8 @@ __device__ inline void mfe_strip_trace_body(MfeTraceSmem& sm, MfeArgs A, const i
     for (int k = tid; k < n; k += NT) A.ss[so + k] = sm.sspk[k];
     return;
   }
-  const char op = round == 0 ? '(' : round == 1 ? '[' : round == 2 ? '<' : '{';
-  const char cl = round == 0 ? ')' : round == 1 ? ']' : round == 2 ? '>' : '}';
+  char op, cl;
+  pk_brackets(round, op, cl);
   int any = 0;
   for (int k = tid; k < n; k += NT) {
     const char ch = sm.ssw[k];

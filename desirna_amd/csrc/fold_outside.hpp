@@ -79,23 +79,10 @@ __global__ __launch_bounds__(NT) void outside_kernel(OutArgs A) {
   double* CL = ob + 3 * tab;
   const double* q5g = ob + 4 * tab;
 
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
-  for (int k = tid; k < 128; k += NT) {
-    sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k]; sm.mm23[k] = T.mm23[k];
-    sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
-  }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
-  const char* seq = A.seqs + (long long)r * n;
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-  }
+  stage_energy_tables<NT>(sm, T, tid);
   for (int k = tid; k <= n; k += NT) sm.q5[k] = q5g[k];
   for (int e = tid; e < NPLAN; e += NT) { sm.plan_u[e] = P.u1[e] | (P.u2[e] << 8) | (P.kind[e] << 16); sm.plan_W[e] = P.W[e]; }
-  __syncthreads();
-  if (tid == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
-  __syncthreads();
+  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
   if (A.pf_status[r] != ST_OK) {          // bad character / PF out of range: the host reports it
     if (tid == 0) A.edef[r] = 0.0;
     return;
@@ -115,7 +102,7 @@ __global__ __launch_bounds__(NT) void outside_kernel(OutArgs A) {
   }
   __syncthreads();
 
-  if (wave == 0 && n - 1 >= TURN + 1) pf_build_plist(sm, n - 1, n, lane);
+  if (wave == 0 && n - 1 >= TURN + 1) build_plist(sm, sm.S, n - 1, n, lane);
   __syncthreads();
 
   for (int d = n - 1; d >= TURN + 1; d--) {
@@ -273,7 +260,7 @@ __global__ __launch_bounds__(NT) void outside_kernel(OutArgs A) {
       OMV[at] = om + V;
       OM1[at] = om1;
     }
-    if (wave == NW - 1 && d - 1 >= TURN + 1) pf_build_plist(sm, d - 1, n, lane);     // list of the next diagonal
+    if (wave == NW - 1 && d - 1 >= TURN + 1) build_plist(sm, sm.S, d - 1, n, lane);     // list of the next diagonal
     __syncthreads();
   }
 

@@ -59,24 +59,6 @@ struct PfSmem {
   f64x2 plan_pW[NPAIR_MAX];
 };
 
-// one wave: list of the cells (i, i+d) that can pair
-__device__ __forceinline__ void pf_build_plist(PfSmem& sm, int d, int n, int lane) {
-  const int par = d & 1;
-  int cnt = 0;
-  for (int i0 = 1; i0 <= n - d; i0 += WAVE) {
-    const int i = i0 + lane;
-    const bool on = i <= n - d && pair_type(sm.S[i], sm.S[i + d]) != 0;
-    const unsigned long long m = __ballot(on);
-    if (on) {
-      const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
-      sm.plist[par][pos] = (unsigned short)i;
-      sm.cpos[par][i] = (unsigned short)pos;
-    }
-    cnt += __popcll(m);
-  }
-  if (lane == 0) sm.pcnt[par] = cnt;
-}
-
 __device__ __forceinline__ double pf_hairpin(const PfSmem& sm, const PfArgs& A, int i, int j, int t) {
   const PfTables& T = *A.T;
   const int u = j - i - 1;
@@ -118,8 +100,8 @@ __global__ __launch_bounds__(NT) void pf_kernel(PfArgs A) {
   constexpr int NW = NT / WAVE;
   const PfTables& T = *A.T;
   const Plan& P = *A.plan;
-  const int r = A.rg.idx ? A.rg.idx[blockIdx.x] : blockIdx.x;
-  if (A.rg.len) A.L = A.rg.len[r];
+  const int r = A.rg.seq_of(blockIdx.x);
+  A.L = A.rg.len_of(r, A.L);
   const int n = A.L, ld = A.ld;
   const int tid = threadIdx.x, lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
@@ -138,13 +120,7 @@ __global__ __launch_bounds__(NT) void pf_kernel(PfArgs A) {
   double* QEXT = base + 6 * tab;
   unsigned char* INFO = reinterpret_cast<unsigned char*>(base + 7 * tab);
 
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
-  for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
-  }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
+  stage_energy_tables<NT>(sm, T, tid);
   for (int e = tid; e < NPLAN; e += NT) { sm.plan_u[e] = P.u1[e] | (P.u2[e] << 8) | (P.kind[e] << 16); sm.plan_W[e] = P.W[e]; }
   const int npair = P.n_pair;
   for (int p = tid; p < npair; p += NT) {
@@ -152,29 +128,19 @@ __global__ __launch_bounds__(NT) void pf_kernel(PfArgs A) {
     sm.plan_p[p] = P.u1[e] | (P.u2[e] << 8) | (c << 16);
     sm.plan_pW[p] = f64x2{P.W[e], c > 1 ? P.W[e + 1] : 0.0};
   }
-  if (tid == 0) sm.flag = 0;
-  __syncthreads();
-  const char* seq = A.seqs + (A.rg.off ? (long long)A.rg.off[r] : (long long)r * n);
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-  }
   // rows read before they are written (all zero): qm1 / U diag 3, D diags 2 and 3
   for (int k = tid; k < ld; k += NT) {
     QM1[3 * ld + k] = 0.0; UQ[3 * ld + k] = 0.0;
     DQ[2 * ld + k] = 0.0; DQ[3 * ld + k] = 0.0;
   }
-  __syncthreads();
-  if (tid == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
-  __syncthreads();
+  load_sequence<NT>(sm, A.seqs + A.rg.off_of(r, n), n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.Epf[r] = 0.0; }
     return;
   }
   const double b1 = A.eMLb[1];
   const double sc2 = A.scale[2];
-  if (wave == 0 && TURN + 1 < n) pf_build_plist(sm, TURN + 1, n, lane);
+  if (wave == 0 && TURN + 1 < n) build_plist(sm, sm.S, TURN + 1, n, lane);
   __syncthreads();
   // QM and QM1 (adjacent tables) through one buffer descriptor
   const auto rsQ = __builtin_amdgcn_make_buffer_rsrc((void*)QM, (short)0, (int)(2 * tab * 8), 0x00020000);
@@ -341,7 +307,7 @@ __global__ __launch_bounds__(NT) void pf_kernel(PfArgs A) {
       DQ[at] = aK;
       QM[at] = m1 + aK + U;
     }
-    if (wave == NW - 1 && d + 1 < n) pf_build_plist(sm, d + 1, n, lane);     // list of the next diagonal
+    if (wave == NW - 1 && d + 1 < n) build_plist(sm, sm.S, d + 1, n, lane);     // list of the next diagonal
     __syncthreads();
   }
 

@@ -415,7 +415,7 @@ __device__ __forceinline__ void pf_kfar_helper(const PfArgs& A, const EvalArgs& 
   // the main workgroup's pairable lists from diagonal PFL_D1 on (pf_pl_row), announced by the first flag: far sums complete below
   // the first diagonal that has any
   {
-    const char* seq = A.seqs + (A.rg.off ? (long long)A.rg.off[r] : (long long)r * n);
+    const char* seq = A.seqs + A.rg.off_of(r, n);
     for (int k = tid; k < n; k += NT) { const int c = enc_nt(seq[k]); sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c); }
     if (tid == 0) { sm.S[0] = 0; sm.S[n + 1] = 0; }
     __syncthreads();
@@ -458,8 +458,8 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
   const bool hm = A.helper != 0;                     // a helper workgroup per sequence computes the far multiloop split points (emulator: odd blocks; kernel: pair_block)
   const int bx = bx_in >= 0 ? bx_in : hm ? blockIdx.x >> 1 : blockIdx.x;
   const bool is_helper = hm && (helper_in >= 0 ? helper_in != 0 : (blockIdx.x & 1) != 0);
-  const int r = A.rg.idx ? A.rg.idx[bx] : bx;
-  if (A.rg.len) A.L = A.rg.len[r];
+  const int r = A.rg.seq_of(bx);
+  A.L = A.rg.len_of(r, A.L);
   const int n = A.L, ld = A.ld;
   if (is_helper) {
     if (A.helper == 2) return;                        // fault injection (tests): the helper never shows up, the main workgroup's wait expires
@@ -485,18 +485,14 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
   const double b1 = A.eMLb[1], sc1 = A.scale[1], sc2 = A.scale[2];
 
   // ---- prologue
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
+  stage_energy_tables<NT>(sm, T, tid);
   for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
     const double inv = 1.0 / T.mmI[k];
     sm.rinv[k] = inv;
     sm.rbul[k] = ((k >> 4) > 2 ? eTau : 1.0) * inv;
     sm.r1n[k] = T.mm1n[k] * inv;
     sm.r23[k] = T.mm23[k] * inv;
   }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
   for (int k = tid; k <= n; k += NT) sm.hpw[k] = A.hp_w[k];
   for (int t = tid; t < 36; t += NT) {
     sm.eWt[t][0] = t >= 2 && t <= 30 ? T.bulge[t] * A.scale[t + 2] : 0.0;
@@ -518,17 +514,8 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
   for (int k = tid; k < 2 * 4 * PfFastSmem<NT>::NSLOT; k += NT) (&sm.partK[0][0][0])[k] = 0.0;
   for (int k = tid; k < 2 * PfFastSmem<NT>::NSLOT; k += NT) (&sm.accE[0][0])[k] = 0.0;
   for (int k = tid; k < 6 * PfFastSmem<NT>::NSLOT; k += NT) (&sm.accX[0][0][0])[k] = 0.0;
-  if (tid == 0) { sm.flag = 0; sm.q5[0] = 1.0; }
-  __syncthreads();
-  const char* seq = A.seqs + (A.rg.off ? (long long)A.rg.off[r] : (long long)r * n);
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-  }
-  __syncthreads();
-  if (tid == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
-  __syncthreads();
+  if (tid == 0) sm.q5[0] = 1.0;
+  load_sequence<NT>(sm, A.seqs + A.rg.off_of(r, n), n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.Epf[r] = 0.0; if (hm) st_agent(A.hflags + (long long)r * 64, A.hbase + STRIP_DONE); }
     return;

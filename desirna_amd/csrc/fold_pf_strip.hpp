@@ -140,7 +140,7 @@ __device__ void pf_strip_body(PfStripSmem<NT>& sm, PfArgs A, StripLink lk, int q
   constexpr int NW = SM::NW, RS = SM::RS, P = SM::P, NFIN = SM::NFIN, NSVC = SM::NSVC;
   const PfTables& T = *A.T;
   const int r = lk.idx ? lk.idx[q] : q + lk.r0;
-  if (A.rg.len) A.L = A.rg.len[r];
+  A.L = A.rg.len_of(r, A.L);
   const int n = A.L, ld = A.ld;
   const int tid = threadIdx.x, lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
@@ -174,18 +174,14 @@ __device__ void pf_strip_body(PfStripSmem<NT>& sm, PfArgs A, StripLink lk, int q
   const double b1 = A.eMLb[1], sc1 = A.scale[1], sc2 = A.scale[2];
 
   // ---- prologue (as in pf_lds_kernel)
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
+  stage_energy_tables<NT>(sm, T, tid);
   for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
     const double inv = 1.0 / T.mmI[k];
     sm.rinv[k] = inv;
     sm.rbul[k] = ((k >> 4) > 2 ? eTau : 1.0) * inv;
     sm.r1n[k] = T.mm1n[k] * inv;
     sm.r23[k] = T.mm23[k] * inv;
   }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
   for (int k = tid; k <= n; k += NT) sm.hpw[k] = A.hp_w[k];
   for (int x = tid; x < 128; x += NT) {
     int s_, u1_;
@@ -224,7 +220,7 @@ __device__ void pf_strip_body(PfStripSmem<NT>& sm, PfArgs A, StripLink lk, int q
   if (tid == 0) { sm.flag = 0; sm.sync_fail[0] = 0; sm.sync_fail[1] = 0; sm.q5[0] = 1.0; }
   __syncthreads();
   // local sequence: S[k] = residue c0 - 1 + k, k = 0 .. n_loc + 1 (the ends wrap as in the one-workgroup kernels)
-  const char* seq = A.seqs + (A.rg.off ? (long long)A.rg.off[r] : (long long)r * n);
+  const char* seq = A.seqs + A.rg.off_of(r, n);
   for (int k = tid; k <= n_loc + 1; k += NT) {
     int g = c0 - 1 + k;                     // 1-based global position
     g = g < 1 ? n : (g > n ? 1 : g);

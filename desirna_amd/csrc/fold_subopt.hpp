@@ -79,27 +79,11 @@ __global__ __launch_bounds__(NT) void subopt_kernel(SubArgs A) {
   Top2* M = reinterpret_cast<Top2*>(base + 2 * tab);
   Top2* M2 = reinterpret_cast<Top2*>(base + 4 * tab);
 
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
-  for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
-  }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
-  if (tid == 0) sm.flag = 0;
-  __syncthreads();
-  const char* seq = A.seqs + (long long)r * n;
-  for (int k = tid; k < n; k += NT) {
-    const int c = enc_nt(seq[k]);
-    if (c < 0) sm.flag = 1;
-    sm.S[k + 1] = (unsigned char)(c < 0 ? 0 : c);
-  }
+  stage_energy_tables<NT>(sm, T, tid);
   // diagonals 0 .. TURN: no pair, no multiloop content
   for (int d = 0; d <= TURN && d < n; d++)
     for (int k = tid; k < ld; k += NT) { C[d * ld + k] = Top2{INF, INF}; M[d * ld + k] = Top2{INF, INF}; M2[d * ld + k] = Top2{INF, INF}; }
-  __syncthreads();
-  if (tid == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
-  __syncthreads();
+  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.E2[r] = 0; if (A.E12) { A.E12[2 * r] = 0; A.E12[2 * r + 1] = INF_REF; } }
     return;
@@ -355,13 +339,9 @@ __global__ __launch_bounds__(NT) void kbest_kernel(KbArgs A) {
   TopK<K>* F = C;                                       // rows 0 .. TURN of C are never read: row 0 holds F[0 .. n]
   int32_t* stacks = reinterpret_cast<int32_t*>(M2);     // rows 0, 1 of M2 are never read: one traceback stack of ld ints per rank
 
-  for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
-  for (int k = tid; k < 128; k += NT) {
-    sm.mmH[k] = T.mmH[k]; sm.mmI[k] = T.mmI[k]; sm.mm1n[k] = T.mm1n[k];
-    sm.mm23[k] = T.mm23[k]; sm.mmM[k] = T.mmM[k]; sm.mmExt[k] = T.mmExt[k];
-  }
-  for (int k = tid; k < 1024; k += NT) sm.int11[k] = T.int11[k];
-  for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
+  stage_energy_tables<NT>(sm, T, tid);
+  // (the sequence load of load_sequence, written out: with the initial stores below moved ahead of it the K = 8 instance takes
+  // 84 VGPRs instead of 76, one wave less per SIMD)
   if (tid == 0) sm.flag = 0;
   __syncthreads();
   const char* seq = A.seqs + (long long)r * n;
