@@ -39,7 +39,7 @@ static std::string g_create_error;
 #ifndef DRNA_MFE_FARK_MIN_STRIPS
 #define DRNA_MFE_FARK_MIN_STRIPS 4
 #endif
-constexpr int MFE_FARK_MIN_STRIPS = DRNA_MFE_FARK_MIN_STRIPS;   // (measured: tools/time_strip_variants.py)
+constexpr int MFE_FARK_MIN_STRIPS = DRNA_MFE_FARK_MIN_STRIPS;   // (measured against prebuilt variants)
 struct drna_engine {
   int device = 0, max_R = 0, max_L = 0, cus = 0;
   HostTables H;
@@ -1678,17 +1678,3 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
             prof[0] / n_iter, prof[1] / n_iter, prof[2] / n_iter);
   return DRNA_OK;
 }
-
-#if defined(DRNA_STAMPS) || defined(MSTRIP_STAMPS) || defined(DRNA_TL)
-// diagnostic build only: copy `count` int32 of the MFE workspace starting at int32 offset `off`
-extern "C" int drna_debug_read_mfe_ws(drna_engine* e, long long off, int count, int32_t* out) {
-  if (!e || !out) return DRNA_ERR_ARG;
-  HIP_TRY(hipMemcpy(out, e->d_ws_mfe + off, (size_t)count * 4, hipMemcpyDeviceToHost));
-  return DRNA_OK;
-}
-extern "C" int drna_debug_read_pf_ws(drna_engine* e, long long off, int count, double* out) {
-  if (!e || !out) return DRNA_ERR_ARG;
-  HIP_TRY(hipMemcpy(out, e->d_ws_pf + off, (size_t)count * 8, hipMemcpyDeviceToHost));
-  return DRNA_OK;
-}
-#endif

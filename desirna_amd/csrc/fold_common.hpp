@@ -21,6 +21,13 @@ constexpr int PART_ITEMS = 32;    // (cell-block, chunk) work items per diagonal
 constexpr int GRES = 28;          // 27 live entries + 1 spare
 enum : int { TW_LIVE = 0, TW_BIRTH = 1, TW_KILL = 2, TW_DEAD = 3 };   // flag in the low bits of a tower-table word
 
+// Floor builds only (-DDRNA_SKIP=15, tools/phase_cost.py: the finalize-only floor of the LDS-resident folds): a set bit leaves a
+// sweep phase out -- 1 the tower step, 2 the bulge / 1xn shape items, 4 the small fixed shapes (PF), 8 the multiloop split
+// items, tiles and helper sweeps.  The results of such a build are wrong by construction; it is timed, never checked.
+#ifndef DRNA_SKIP
+#define DRNA_SKIP 0
+#endif
+
 // kernel status codes (per sequence)
 enum : int { ST_OK = 0, ST_BAD_CHAR = 1, ST_TRACEBACK = 2, ST_PF_RANGE = 3, ST_SYNC = 4 };
 

@@ -73,24 +73,6 @@ struct FmlLds {
   }
 };
 
-// Diagnostic build only (-DDRNA_STAMPS): per-wave cycle totals of each phase of block 0, written to
-// an unused part of its workspace (never read by the kernel).
-#ifndef DRNA_SKIP
-#define DRNA_SKIP 0          // diagnostic builds only: see fold_pf_lds.hpp
-#endif
-#ifdef DRNA_STAMPS
-#define STAMP(k) do { long long _n = clock64(); st_acc[k] += _n - st_last; st_last = _n; } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
-// -DDRNA_TL (tools/timeline.py mfe): raw 100 MHz clocks per wave and step of sequence 0's main workgroup, into
-// the unused table 2 of its workspace: 0 after the barrier, 1 after the finalize / tower step, 2 after the last item
-#ifdef DRNA_TL
-#define MTLMARK(ev, k) do { if (mtl_on && lane == 0) mtl[((wave * 3 + (ev)) << 8) + (k)] = (long long)wall_clock64(); } while (0)
-#else
-#define MTLMARK(ev, k) do { } while (0)
-#endif
-
 // exterior column j: f5[j] = min(f5[j-1], min_i f5[i-1] + c[i,j] + E_ExtLoop); one wave, every lane stores the same value
 template <int NT>
 __device__ __forceinline__ void mfe_f5_column(MfeFastSmem<NT>& sm, const int32_t* __restrict__ EXT, int ld, int j, int lane) {
@@ -379,7 +361,7 @@ __device__ __forceinline__ void mfe_e_item(SM& sm, int e, int d, int par, int pc
   } else if (MODE == E_FAR) {
     // the 23 far shapes of a class (bulges u = DLAG-2 .. 30, 1xn loops u = DLAG-3 .. 29) in EFAR_PARTS items: as one item per class
     // (29 table entries, the near ones reading the INF row) an item was a 1.3 - 1.8 us chain, and at late diagonals, where a step has
-    // a dozen items for thirteen worker waves, the helper's step was its longest item (tools/timeline.py mfe)
+    // a dozen items for thirteen worker waves, the helper's step was its longest item (measured with a per-wave timeline build)
     const int cls = EFAR_PARTS == 1 ? x : x / EFAR_PARTS, part = EFAR_PARTS == 1 ? 0 : x - EFAR_PARTS * cls;
     const int first = cls * 32 + (EFAR_PARTS == 1 ? 0 : (cls < 2 ? NEAR_B : NEAR_I) + part * EFAR_NSH);
     if (cls < 2) v = mfe_e_class<EFAR_NSH, false>(sm, ring, par, first, lane) + outer_b;
@@ -625,7 +607,7 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
   // The pairable-list row of the next diagonal is staged into LDS by two SWEEP waves taking turns (block 0's even-size waves: the
   // one whose towers rest in a step requests the row after next, and writes it first thing in the following step, in which it is
   // active).  On a finalize wave the staging was +0.5 us on the cell finalize -- the pole of every step in which the outermost
-  // block still holds cells (tools/timeline.py mfe: +2.04 us against +1.27).  Small workgroups (emulation) keep it on a finalize wave.
+  // block still holds cells (measured with a per-wave timeline build: +2.04 us against +1.27).  Small workgroups (emulation) keep it on a finalize wave.
   const bool sweep_stage = !TWO_PAR && NBT >= 1;
   const bool stager = sweep_stage && my_tb == 0 && my_sig == 0;
   // ... and the exterior column j = k - 3 by block 0's two odd-size waves, the one that rests in the step (its cells, diagonals
@@ -635,18 +617,10 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
   // finalize waves that take the side jobs; wave 0 owns the outermost tower block, which has the fewest live cells
   const int w_tab = NB > 1 ? 1 : 0, w_pl = 0, w_q5 = NB - 1;
   // the shape table of the next diagonal goes to a wave of its own when there is one without a side job (n > 128: wave 2): with
-  // both tables on wave 1 that wave was the last to reach the barrier in two steps of three (tools/timeline.py: +1.84 us against
+  // both tables on wave 1 that wave was the last to reach the barrier in two steps of three (measured with a per-wave timeline build: +1.84 us against
   // +1.33 for the cell finalize alone)
   const int w_et = NB > 3 ? 2 : w_tab;
 
-#ifdef DRNA_TL
-  long long* ptl2 = reinterpret_cast<long long*>(Wc + 2ll * ld * ld);
-  const bool ptl2_on = Wc == A.ws && tid == 0;            // (sequence 0's main workgroup, whatever the block mapping)
-#define PTL2(x) do { if (ptl2_on) ptl2[256 + (x)] = (long long)wall_clock64(); } while (0)
-#else
-#define PTL2(x) do { } while (0)
-#endif
-  PTL2(0);
   if (DUAL) {
     // round prologue for the helper workgroup, first thing: the pairing codes of this round (masked positions = 4), then the
     // flag -- the helper builds the pairable lists of the diagonals from PL_D1 on while this workgroup fills its tables
@@ -655,7 +629,6 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
     for (int k = tid; k <= n + 1; k += NT) st_agent(xs + k, (int32_t)sm.Sp[k]);
     if (tid == 0) sm.sync_fail = 0;
   }
-  PTL2(1);
   // ---- prologue: constant tables, and the compacted list of pairable cells of every diagonal (HBM/L2)
   for (int k = tid; k < 4 * RS; k += NT) sm.dml[k] = INF;
   for (int k = tid; k < 32 * RS; k += NT) { sm.wring[k] = INF * 256; sm.ciring[k] = INF; }   // idle tower entries read row 0
@@ -682,11 +655,9 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
     __syncthreads();
     if (tid == 0) st_agent(lk.flagA, lk.base + TURN);
   }
-  PTL2(2);
   // (two-workgroup kernel: the rows from PL_D1 on are the helper's, see mfe_pl_row; this workgroup's own rows stay in its L2)
   for (int d = TURN + 1 + wave; d < (DUAL ? min(n, PL_D1) : n); d += NW) mfe_pl_row<false>(sm, T, PL, PLX, ld, n, d, lane, TermAU);
   __syncthreads();
-  PTL2(3);
   // tables and pairable list of the first diagonal
   if (aw < 0) {
     const int d = TURN + 1;
@@ -699,14 +670,6 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
   }
   __syncthreads();
 
-#ifdef DRNA_STAMPS
-  long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long st_last = clock64();
-#endif
-#ifdef DRNA_TL
-  long long* mtl = reinterpret_cast<long long*>(Wc + 2ll * ld * ld);
-  const bool mtl_on = Wc == A.ws;
-#endif
   if (aw < 0) {
     // ================= finalize waves
     // two-workgroup kernel: the helper's results for diagonal d (split minima, far-shape minima) are fetched one step AHEAD
@@ -738,7 +701,6 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
     if (!sweep_stage && wave == w_pl && TURN + 2 < n) pl_request(TURN + 2);
     for (int k = TURN + 1; k <= n; k++) {
       const int d = k - 1;
-      MTLMARK(0, k);
       // rows of diagonal d-2: stored in step k-2, and a step's stores have landed by the NEXT step's barrier (the counted wait
       // at the end of a step leaves that step's own stores in flight: no store latency inside a step)
       if (DUAL && tid == 0 && d - 2 > TURN) st_agent(lk.flagA, lk.base + d - 2);
@@ -756,7 +718,7 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
       }
       // ---- top of the step: the pipelined side jobs.  The list row of diagonal k+1 was requested a whole step ago (the rows were
       // written by the prologue and have left the L2 by now: they come from HBM, and with the request at the top of the SAME step
-      // the wave that stages them reached the barrier last in every early step -- tools/timeline.py: +2.46 us against +1.66 for
+      // the wave that stages them reached the barrier last in every early step -- measured with a per-wave timeline build: +2.46 us against +1.66 for
       // the cell finalize); it goes into LDS here -- the sweep waves read the other parity's buffer -- and the row of diagonal
       // k+2 is requested into the same registers.  The exterior column's cells are requested here and consumed after the cell
       // finalize.
@@ -790,9 +752,6 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
         int bK = pfK, bI = pfI;
         if (DUAL && d >= DUAL_D0) {                              // (before that diagonal the helper has nothing to add)
           if (!have) {                                           // not fetched ahead: wait for the helper here
-#ifdef DRNA_TL
-            if (mtl_on && tid == 0) { long long* cnt = mtl + 12287; cnt[0] += 1ll << (8 * (k / 25)); }      // (timeline builds: steps that met the helper late)
-#endif
             if (!sm.sync_fail && !wait_flag_wave(lk.flagB, lk.base + d)) sm.sync_fail = 1;
             const bool on = i >= 1 && i <= ncell;
             bK = on ? ld_agent(xk + d * XP + i) : INF;
@@ -844,7 +803,6 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
           }
         }
       }
-      MTLMARK(1, k);
       // side jobs of the step, one finalize wave each (when there are that many): tower table and pairable list of
       // diagonal k+1 (the sweep waves are reading those of diagonal k), exterior column j = k-3 (its cells, diagonals
       // <= k-4, were stored in step <= k-3 and had landed by the end of step k-2)
@@ -867,8 +825,6 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
         const int prev = sm.f5[j - 1];
         if (lane == WAVE - 1) sm.f5[j] = prev < m ? prev : m;
       }
-      STAMP(4);
-      MTLMARK(2, k);
       // every global load of the step has been consumed; what is still in flight are this step's stores (c, exterior term,
       // and the two published words of the two-workgroup kernel): the wait lets exactly those stay in flight across the
       // barrier, so the stores of the PREVIOUS step have landed -- which is what their readers rely on (exterior column
@@ -884,7 +840,6 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
       // step's own stores (2, or 4 in the two-workgroup kernel) stay in flight across the barrier
       if (stored) stores_in_flight<DUAL ? 4 : 2>(); else stores_in_flight<0>();
       lds_barrier();                       // one barrier per diagonal
-      STAMP(3);
     }
   } else {
     // ================= sweep waves
@@ -921,7 +876,6 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
     // (the wave that is active in the first step writes the second diagonal's row at its top: requested here)
     if (stager && ((my_pm >> ((TURN + 1) & 1)) & 1) && TURN + 2 < n) st_request(TURN + 2);
     for (int k = TURN + 1; k <= n; k++) {
-      MTLMARK(0, k);
       if (q5er && !((my_pm >> (k & 1)) & 1) && k - 3 >= TURN + 2) {
         const int j = k - 3;
         const int nch = (j - TURN - 1 + WAVE - 1) >> 6;
@@ -974,8 +928,6 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
             atomicMin(&sm.accG[par][blo + lane], accG);
           }
         }
-        STAMP(0);
-        MTLMARK(1, k);
         const int pcnt = __builtin_amdgcn_readfirstlane(sm.pcnt[par]);
         const int slot0 = sh + off0 - 1;          // tower slot of column i is i + slot0
         // ---- floating items of the diagonal, taken from a work queue (LDS counter) so the sweep waves stay
@@ -997,39 +949,21 @@ __device__ __forceinline__ void mfe_fill_lds(MfeFastSmem<NT>& sm, const MfeArgs&
         // die first -- before those of the centre blocks: no queue pops (a pop is an LDS atomic round trip of ~400 cycles)
         int it = DUAL ? item_rank_of(par) : queue_pop(&sm.qhead[par], lane);
         for (; it < nItems; it = DUAL ? it + NA : queue_pop(&sm.qhead[par], lane)) {
-          STAMP(6);
           if (it < nK) {
             if (DUAL) mfe_k_edge_item(sm, it, d, n, ncell, par, slot0, lane);
             else {
               const int lo = TURN + 1 + (it & ((1 << kssh) - 1)) * k_per;
               mfe_k_item(sm, it >> kssh, d, n, ncell, par, slot0, lane, lo, min(d - TURN - 2, lo + k_per - 1));
             }
-            STAMP(5);
-#ifdef DRNA_STAMPS
-            st_acc[7]++;
-#endif
           } else {
             if (DUAL) mfe_e_item<E_NEAR>(sm, it - nK, d, par, pcnt, slot0, lane, TermAU, e_bulge1, e_int23);
             else mfe_e_item_rows(sm, it - nK, d, par, pcnt, slot0, lane, TermAU, e_bulge1, e_int23);
-            STAMP(1);
-#ifdef DRNA_STAMPS
-            st_acc[2]++;
-#endif
           }
         }
-        STAMP(6);
-        MTLMARK(2, k);
       }
       __syncthreads();
-      STAMP(3);
     }
   }
-#ifdef DRNA_STAMPS
-  if (blockIdx.x == 0 && lane == 0) {
-    long long* dbg = reinterpret_cast<long long*>(Wc + 2ll * ld * ld);
-    for (int k = 0; k < 8; k++) dbg[wave * 8 + k] = st_acc[k];
-  }
-#endif
   // the remaining exterior columns (every store has landed: the loop ended with a draining barrier): their minima by one wave
   // each, side by side (column j reads f5 up to j - 5, which the loop has left final), then the three-step recurrence by one lane
   {
@@ -1070,13 +1004,6 @@ __device__ __forceinline__ void mfe_lds_body(MfeFastSmem<NT>& sm, MfeArgs A, int
   int32_t* PL = base + 3 * tab;      // compacted pairable-cell lists, one row per diagonal
   int32_t* PLX = base + 1 * tab;     // their staged (1,2) / (2,1) loop energies
 
-#ifdef DRNA_TL
-  // phase marks of sequence 0's (main) workgroup (tools/timeline.py mfe): kernel entry, fill done, traceback done (steps start at
-  // TURN + 1: slots 0 .. 3 of every event row are free); PTL2 in mfe_fill_lds: the parts of the first round's prologue
-  long long* ptl = reinterpret_cast<long long*>(Wc + 2ll * ld * ld);
-  const bool ptl_on = Wc == A.ws && tid == 0;
-  if (ptl_on) { ptl[0] = (long long)wall_clock64(); ptl[12287] = 0; }
-#endif
   // (stage_energy_tables, written out: through the helper the three kernels with this body spill differently, scratch 336 -> 348
   // bytes per lane in mfe_lds_kernel)
   for (int k = tid; k < 64; k += NT) sm.stack[k] = T.stack[k];
@@ -1100,9 +1027,6 @@ __device__ __forceinline__ void mfe_lds_body(MfeFastSmem<NT>& sm, MfeArgs A, int
     for (int k = tid; k < n; k += NT) sm.ssw[k] = '.';
     lk.base = dual_base(lk.epoch, round);
     mfe_fill_lds<NT, DUAL>(sm, A, Wc, EXT, PL, PLX, lk);           // ends with a barrier
-#ifdef DRNA_TL
-    if (ptl_on && round == 0) ptl[1] = (long long)wall_clock64();
-#endif
     if (DUAL && sm.sync_fail) { status = ST_SYNC; break; }
     // traceback by TB_WAVES waves working from one queue of sectors in LDS (TbShared): entry 0 = the whole exterior interval
     constexpr int TB_WAVES = NT / WAVE < 8 ? NT / WAVE : 8;
@@ -1113,18 +1037,11 @@ __device__ __forceinline__ void mfe_lds_body(MfeFastSmem<NT>& sm, MfeArgs A, int
       sm.tbq[0] = 0; sm.tbq[1] = 1; sm.tbq[2] = 1; sm.tbq[3] = 0;
     }
     __syncthreads();
-#ifdef DRNA_TL_TB
-    if (blockIdx.x == 0 && tid == 0) drna_tl_tb_ptr = round == 0 ? ptl : nullptr;
+    if (wave_id() < TB_WAVES) (void)mfe_traceback_q(sm, A, Wc, FmlLds<NT>{&sm, n}, EXT, TbShared<MfeFastSmem<NT>>{sm});
     __syncthreads();
-#endif
-    if (!(DRNA_SKIP & 256) && wave_id() < TB_WAVES) (void)mfe_traceback_q(sm, A, Wc, FmlLds<NT>{&sm, n}, EXT, TbShared<MfeFastSmem<NT>>{sm});
-    __syncthreads();
-#ifdef DRNA_TL
-    if (ptl_on && round == 0) ptl[2] = (long long)wall_clock64();
-#endif
     if (tid == 0) {
       if (round == 0) A.Emfe[r] = sm.f5[n];
-      sm.flag = (!(DRNA_SKIP & 256) && sm.tbq[3] == 2) ? 1 : 0;
+      sm.flag = sm.tbq[3] == 2 ? 1 : 0;
     }
     __syncthreads();
     if (sm.flag) { status = ST_TRACEBACK; break; }

@@ -18,14 +18,6 @@
 namespace drna {
 
 constexpr int MSTRIP_REC = 96;        // int32 per exchange record
-#ifdef MSTRIP_STAMPS
-#define MST(k) do { const long long _n = clock64(); st_acc[k] += _n - st_last; st_last = _n; } while (0)
-#else
-#define MST(k) do { } while (0)
-#endif
-#ifndef MSTRIP_SKIP
-#define MSTRIP_SKIP 0     // diagnostic builds only (results wrong): 1 no multiloop items, 2 no shape items, 4 no tower step, 8 no cell finalize, 128 split items without their second operand's loads, 256 those loads plain
-#endif
 
 constexpr int MSTRIP_KU = 8;       // split points per lane and round trip in the big batches (2 x 16-byte loads each)
 // ---- blocked multiloop splits (StripLink::fark, chosen per launch by the engine: long folds).  With m = i + tt + 2 the split
@@ -154,7 +146,7 @@ __device__ __forceinline__ void mstrip_tower(SM& sm, int (&G)[GSLOTS], int d, in
       G[qx] = mine ? v : G[qx];
     }
   }
-  const int accG = (MSTRIP_SKIP & 4) ? INF_DEV : mfe_tower_step(sm, G, par, i * 4, my_g, SM::NG, lane);
+  const int accG = mfe_tower_step(sm, G, par, i * 4, my_g, SM::NG, lane);
   if (live) atomicMin(&sm.accG[par][phys], accG);
   if (has_down && live && iraw == 1) {
     int32_t* rec = rec_out + (long long)d * MSTRIP_REC + 64 + my_g * GSLOTS;
@@ -315,7 +307,7 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
     const int kssh = fark ? (nterm > 96 ? 3 : nterm > 48 ? 2 : nterm > 24 ? 1 : 0) : (d > 96 ? 3 : d > 48 ? 2 : d > 24 ? 1 : 0);
     const int KS = 1 << kssh, KG = 4 << kssh;
     const int astep = 4 * KG * ld, cstep = 4 * KG * (ld - 1);
-    const int nK = (MSTRIP_SKIP & 1) ? 0 : ((ncell + 63) >> 6) << kssh, nE = (MSTRIP_SKIP & 2) ? 0 : (pcnt + 3) >> 2;
+    const int nK = ((ncell + 63) >> 6) << kssh, nE = (pcnt + 3) >> 2;
     const int nKF = nK;
     const int nItems = __builtin_amdgcn_readfirstlane(nKF + nE);
     auto pop = [&]() -> int {
@@ -385,7 +377,7 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
           for (int u = 0; u < U; u++) {
             const bool on = u < nvalid;
             a[u] = buf_load_i32x4(rsF, on ? vA + u * astep : vA, 0);
-            c[u] = (MSTRIP_SKIP & 128) ? a[u] : (MSTRIP_SKIP & 256) ? buf_load_i32x4(rsF, on ? vC - u * cstep : vC, 0) : buf_load_i32x4_sc1(rsF, on ? vC - u * cstep : vC, 0);
+            c[u] = buf_load_i32x4_sc1(rsF, on ? vC - u * cstep : vC, 0);
           }
 #pragma unroll
           for (int u = 0; u < U; u++) {
@@ -417,7 +409,7 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
 
   // ---- service jobs of step k.  What they read was stored write-through by other workgroups (or long ago by the prologue):
   // it comes from beyond the L2, ~1.5 us a trip -- with the loads inside the step the service waves WERE the floor of a step
-  // (3.4 k of its 4.2 k cycles, tools/strip_stamps.py).  So every load is requested one step AHEAD and consumed from registers
+  // (3.4 k of its 4.2 k cycles, measured with a per-wave cycle-stamp build).  So every load is requested one step AHEAD and consumed from registers
   // at the top of the next step; the registers ride across the items and the barrier.
   // A: the record of diagonal k-1 of the strip above (ring halo, fML / decomposition minimum of its first column, the minima of
   //    the tower that enters at diagonal k+1).  It is requested as soon as a flag value READ EARLIER covers it (the flag itself
@@ -465,7 +457,7 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
   constexpr int NFX = 15;       // chunks of the exterior column requested ahead (960 cells); longer columns continue inside the step
   int lp_cnt = 0, lp_p0 = 0, lp_p1 = 0, lp_x0 = 0, lp_x1 = 0, fx[NFX];
   auto sb_request = [&](const int k) {                                // for step k: list of diagonal k+1, column k-3
-    if (!(MSTRIP_SKIP & 64) && k + 1 < n_loc) {
+    if (k + 1 < n_loc) {
       const int32_t* row = PL + (k + 1) * ld + c0 - 1;
       const int32_t* rowx = PLX + (k + 1) * ld + c0 - 1;
       lp_cnt = PLC[(k + 1) * STRIP_MAXS + s];
@@ -473,7 +465,7 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
       lp_x0 = rowx[lane]; lp_x1 = rowx[min(lane + WAVE, wid)];
     }
     const int j = k - 3, fcnt = j - TURN - 1;
-    const int nch = (!(MSTRIP_SKIP & 32) && last && j >= TURN + 2) ? (fcnt + WAVE - 1) >> 6 : 0;
+    const int nch = (last && j >= TURN + 2) ? (fcnt + WAVE - 1) >> 6 : 0;
 #pragma unroll
     for (int c = 0; c < NFX; c++) {
       fx[c] = INF;
@@ -483,12 +475,12 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
   if (wave == w_svcB) sb_request(TURN + 1);
   auto service_b = [&](const int k) {
     const int dn = k + 1, j = k - 3, fcnt = j - TURN - 1;
-    if (!(MSTRIP_SKIP & 64) && k + 1 < n_loc) {
+    if (k + 1 < n_loc) {
       sm.plist[dn & 1][lane] = lp_p0; sm.xe[dn & 1][lane] = lp_x0;
       if (lane + WAVE < SM::NL) { sm.plist[dn & 1][lane + WAVE] = lp_p1; sm.xe[dn & 1][lane + WAVE] = lp_x1; }
       if (lane == 0) { sm.pcnt[dn & 1] = lp_cnt; sm.qk[dn & 1] = 0; sm.qe[dn & 1] = 0; }
     }
-    if (!(MSTRIP_SKIP & 32) && last && j >= TURN + 2) {
+    if (last && j >= TURN + 2) {
       int m = INF;
 #pragma unroll
       for (int c = 0; c < NFX; c++) {
@@ -533,7 +525,7 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
     const int xk = k + 15 + MKT_W, B = xk >> 4;
     g = xk & 15;
     q.t = tf + NTW * o; q.bj = q.t + B;
-    q.on = fark && !(MSTRIP_SKIP & 16) && g < MKT_W && B >= MKT_BMIN && 16 * q.t < wid && 16 * q.bj + 1 <= n_loc;   // (wave-uniform)
+    q.on = fark && g < MKT_W && B >= MKT_BMIN && 16 * q.t < wid && 16 * q.bj + 1 <= n_loc;   // (wave-uniform)
     q.m_lo = 16 * q.t + 31 + MKT_L; q.m_hi = 16 * q.bj - 13 - MKT_L;
     q.nch = (q.m_hi - q.m_lo + 4) >> 2;
     const int nl = (q.nch + 1) >> 1, nh = q.nch >> 1;
@@ -609,9 +601,6 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
   auto tile_job = [&](const int k) { tile_issue(k); tile_finish(k); };
 
   bool failed = false;
-#ifdef MSTRIP_STAMPS
-  long long st_acc[4] = {0, 0, 0, 0}, st_last = clock64();
-#endif
   if (fin) {
     // ================= finalize waves: diagonal d = k-1 at step k
     for (int k = TURN + 1; k <= n_loc; k++) {
@@ -621,7 +610,7 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
         const int ncell = min(wid, n_loc - d), sh = d >> 1, par = d & 1;
         const int i = ((tid - sh - 1) & (P - 1)) + 1;
         const int dm1v = as_vector(d - 1);
-        if (!(MSTRIP_SKIP & 8) && i <= ncell) {
+        if (i <= ncell) {
           const int aG = sm.accG[par][tid], aI = sm.accI[par][tid], aK = sm.accK[par][tid];
           sm.accG[par][tid] = INF; sm.accI[par][tid] = INF; sm.accK[par][tid] = INF;
           const int j = i + d;
@@ -674,31 +663,23 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
         }
       }
       if (!NSVC && wave == 0) { service_a(k); service_b(k); }
-      MST(0);
       if (k < n_loc) run_items(k, std::true_type{});
-      MST(1);
       STRIP_BARRIER();
-      MST(2);
       if (sm.sync_fail[k & 1]) { failed = true; break; }
     }
   } else if (NSVC && wave < NFIN + NSVC) {
     // ================= service waves
     for (int k = TURN + 1; k <= n_loc; k++) {
       if (wave == w_svcA) service_a(k); else service_b(k);
-      MST(0);
       if (k < n_loc) { tile_job(k); run_items(k, std::true_type{}); }
-      MST(1);
       STRIP_BARRIER();
-      MST(2);
       if (sm.sync_fail[k & 1]) { failed = true; break; }
     }
   } else if (!pinned) {
     // ================= floating waves: tile products and items
     for (int k = TURN + 1; k <= n_loc; k++) {
       if (k < n_loc) run_items(k, std::true_type{});
-      MST(1);
       STRIP_BARRIER();
-      MST(2);
       if (sm.sync_fail[k & 1]) { failed = true; break; }
     }
   } else {
@@ -713,32 +694,22 @@ __device__ void mfe_strip_body(MfeStripSmem<NT>& sm, MfeArgs A, StripLink lk, St
         tile_issue(k);
         mstrip_tower(sm, GE, k, wid, n_loc, phys, my_tb, my_g, lane, has_up, has_down, rec_out);
         tile_finish(k);
-        MST(0);
         run_items(k, std::false_type{});
-        MST(1);
       }
       STRIP_BARRIER();
-      MST(2);
       if (sm.sync_fail[k & 1]) { failed = true; break; }
       if (k + 1 > n_loc) break;
       if (k + 1 < n_loc) {
         tile_issue(k + 1);
         mstrip_tower(sm, GO, k + 1, wid, n_loc, phys, my_tb, my_g, lane, has_up, has_down, rec_out);
         tile_finish(k + 1);
-        MST(0);
         run_items(k + 1, std::false_type{});
-        MST(1);
       }
       STRIP_BARRIER();
-      MST(2);
       if (sm.sync_fail[(k + 1) & 1]) { failed = true; break; }
     }
   }
 
-#ifdef MSTRIP_STAMPS
-  if (lk.clk && q == 0 && last && lane == 0)
-    for (int k = 0; k < 4; k++) lk.clk[16 + wave * 4 + k] = st_acc[k];
-#endif
   if (failed) {
     if (tid == 0) {
       if (has_down) st_agent(my_flag, lk.base + STRIP_FAIL);

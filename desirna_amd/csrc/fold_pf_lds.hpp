@@ -331,30 +331,6 @@ __device__ __forceinline__ void k_tile_finish(RS rs, int ld, const KTile& t, int
   const int ii = 4 * t.a + 1 + (lane >> 4), jj = 4 * t.c + 1 + (lane & 3);
   if ((lane & 12) == 12 && jj <= n) store(jj - ii, ii, v);
 }
-// Diagnostic builds only (-DDRNA_SKIP=mask, tools/phase_cost.py): leave out a sweep phase to read its marginal cost
-// from the kernel time (results are wrong by construction).  1 = T, 2 = E, 4 = X, 8 = K, 16 = cell finalize, 32 = table / pairable-list
-// preparation, 64 = exterior column.
-#ifndef DRNA_SKIP
-#define DRNA_SKIP 0
-#endif
-// -DDRNA_TL (tools/timeline.py): every wave of sequence 0's main workgroup stores a raw clock at three points of every step
-// (0 after the barrier, 1 after the finalize / tower step, 2 after its last item) into the unused upper half of table 4
-#ifdef DRNA_TL
-#define TLMARK(ev, k) do { if (tl_on && lane == 0) tl[((wave * 3 + (ev)) << 8) + (k)] = (long long)wall_clock64(); } while (0)
-#define TLMARK2(ev, k) do { if (tl_on && lane == 0) tl[((48 + wave * 3 + (ev)) << 8) + (k)] = (long long)wall_clock64(); } while (0)
-#define TLMARK3(k) do { if (tl_on && lane == 0) tl[((60 + wave) << 8) + (k)] = (long long)wall_clock64(); } while (0)     // sweep waves: tile products done
-#else
-#define TLMARK(ev, k) do { } while (0)
-#define TLMARK2(ev, k) do { } while (0)
-#define TLMARK3(k) do { } while (0)
-#endif
-#ifndef STAMP
-#ifdef DRNA_STAMPS
-#define STAMP(k) do { long long _n = clock64(); st_acc[k] += _n - st_last; st_last = _n; } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
-#endif
 
 // ---- compacted list of the pairable cells of diagonal d (one wave): i | (pair type, inner neighbours) << 8, the count in the
 // row's last word.  With a helper workgroup the main workgroup builds the rows below PFL_D1 only; the helper, idle until the first
@@ -434,7 +410,7 @@ __device__ __forceinline__ void pf_kfar_helper(const PfArgs& A, const EvalArgs& 
     }
     __syncthreads();
     if (ctl[0]) break;
-    if (!(DRNA_SKIP & 8))                                                         // (DRNA_SKIP: timing builds)
+    if (!(DRNA_SKIP & 8))                                                         // (DRNA_SKIP: floor builds, fold_common.hpp)
       for (int a = wave; a <= Bmax - B; a += NW) {
         KTile t;
         k_tile_issue<true>(rsX, (int)tab * 8, ld, n, a, B, lane, t);
@@ -476,11 +452,6 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
   int32_t* PL = reinterpret_cast<int32_t*>(base + 4 * tab);   // compacted pairable-cell lists, one row per diagonal
   double* QEXT = base + 6 * tab;
 
-#ifdef DRNA_TL
-  long long* tl = reinterpret_cast<long long*>(base + 4 * tab + tab / 2);
-  const bool tl_on = r == 0;
-  TLMARK(0, 0);                       // kernel entry (steps start at TURN + 1: slots 0 .. 3 are free); 1: prologue done; 2, 3: epilogue
-#endif
   const double eTau = T.TermAU, eMLc = T.MLclosing, eMLi = T.MLintern;
   const double b1 = A.eMLb[1], sc1 = A.scale[1], sc2 = A.scale[2];
 
@@ -558,11 +529,6 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
   }
   __syncthreads();
 
-#ifdef DRNA_STAMPS
-  long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long st_last = clock64();
-  long long* dbg = reinterpret_cast<long long*>(base + 5 * tab);     // the U table is unused by this kernel
-#endif
   // X: weights of the nine fixed shapes (0,0) (0,1) (1,0) (1,1) (1,2) (2,1) (2,2) (2,3) (3,2)
 
   // QM and QM1 (adjacent tables) through one buffer descriptor
@@ -675,9 +641,6 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
         }
         if (q < pcnt) sm.accX[par][grp][i + slot0] = sum;
       }
-#ifdef DRNA_STAMPS
-      STAMP(it < nK ? 5 : it < nK + nE ? 1 : 2);
-#endif
     }
   };
 
@@ -691,7 +654,7 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
   // 0.56 / 0.61 / 0.63 / 0.65 ms for 0 / 1 / 2 / 4 products carried, against 0.54.)
   auto run_tiles = [&](const int d) {
     const int Bmax = (n - 1) >> 2, Bt = ((d + 3) >> 2) + 1, ph = (d + 3) & 3;
-    if (!TILES || (DRNA_SKIP & (8 | 512)) || hm || Bt < KT_BMIN || Bt > Bmax) return;         // (512: timing build without the far split points)
+    if (!TILES || (DRNA_SKIP & 8) || hm || Bt < KT_BMIN || Bt > Bmax) return;
     const int cnt = Bmax - Bt + 1, per = (cnt + 3) >> 2, a0 = ph * per;
     const int nT = __builtin_amdgcn_readfirstlane(max(0, min(cnt, a0 + per) - a0));
     for (int it = queue_pop(&sm.qtile[d & 1], lane); it < nT; it = queue_pop(&sm.qtile[d & 1], lane)) {
@@ -724,10 +687,9 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
         pl0 = row[lane]; pl1 = row[lane + WAVE]; pl2 = row[lane + 2 * WAVE]; pl3 = row[min(lane + 3 * WAVE, ld - 1)];
       }
     };
-    if (!(DRNA_SKIP & 32) && wave == w_pl && TURN + 2 < n) pl_request(TURN + 2);
+    if (wave == w_pl && TURN + 2 < n) pl_request(TURN + 2);
     for (int k = TURN + 1; k <= n; k++) {
       const int d = k - 1;
-      TLMARK(0, k);
       // side jobs of the step, one finalize wave each (when there are that many): pairable list of diagonal k+1, exterior
       // column j = k-3 (its cells were stored in step <= k-3 and drained by that step's barrier).  Their global loads are
       // REQUESTED here, before this step's stores, and consumed after the cell finalize: vector-memory operations retire in
@@ -736,7 +698,7 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
       // come from beyond this XCD's L2, ~2 us, and with the request at the top of the SAME step the staging wave reached the
       // barrier last once the steps were down to the finalize chain): it goes into LDS here -- the items of this step read the
       // other parity's buffer -- and the row of diagonal k+2 is requested into the same registers.
-      if (!(DRNA_SKIP & 32) && wave == w_pl) {
+      if (wave == w_pl) {
         if (k + 1 < n) {
           int* dst = sm.plist[(k + 1) & 1];
           dst[lane] = pl0; dst[lane + WAVE] = pl1; dst[lane + 2 * WAVE] = pl2;
@@ -745,7 +707,7 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
         }
         if (k + 2 < n) pl_request(k + 2);
       }
-      const bool job_q5 = !(DRNA_SKIP & 64) && wave == w_q5 && k - 3 >= TURN + 2;
+      const bool job_q5 = wave == w_q5 && k - 3 >= TURN + 2;
       double qx0 = 0.0, qx1 = 0.0, qx2 = 0.0, qx3 = 0.0;
       if (job_q5) {
         const int j = k - 3, top = j - TURN - 1;                   // i = 1 .. top
@@ -775,11 +737,10 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
         const int ic = tid + 1 - (k >> 1) - off0;
         if (ic >= 1 && ic <= n - k && kt_has_far(ic, k)) d_req = hm ? ld_agent(&DFAR[k * ld + ic]) : DFAR[k * ld + ic];
       }
-      TLMARK2(0, k);
       if (d > TURN) {
         const int ncell = n - d, sh = d >> 1, par = d & 1;
         const int i = tid + 1 - sh - off0;
-        if (!(DRNA_SKIP & 16) && i >= 1 && i <= ncell) {
+        if (i >= 1 && i <= ncell) {
           // every producer writes its slot of every live cell on every diagonal it exists for, so nothing is zeroed here:
           // a family that does not exist yet (or a cell that cannot pair) is simply not read
           const int j = i + d;
@@ -838,7 +799,6 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
           }
         }
       }
-      TLMARK2(1, k);
       if (job_q5) {
         // q5[j] = q5[j-1] scale[1] + sum_i q5[i-1] qb[i,j] expExt(i,j): four strided terms per lane, fixed-order wave sum
         const int j = k - 3, top = j - TURN - 1;
@@ -850,17 +810,10 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
         sq = wave_total_f64_lane63(sq);          // DPP scan (no LDS traffic); lane 63 holds the total
         if (lane == WAVE - 1) sm.q5[j] = sm.q5[j - 1] * sc1 + sq;
       }
-      STAMP(4);
-      TLMARK(1, k);
-      if (!(DRNA_SKIP & 128) && k < n) run_items(k);          // help the sweep of diagonal k
-      TLMARK(2, k);
+      if (k < n) run_items(k);          // help the sweep of diagonal k
       dfar_next = d_req;
       if (hm) fb_last = __builtin_amdgcn_readfirstlane(f_req);
       __syncthreads();
-      STAMP(3);
-#ifdef DRNA_STAMPS
-      if (blockIdx.x == 0 && tid == 0) dbg[256 + k] = st_acc[4];
-#endif
     }
   } else {
     // ================= sweep waves: diagonal d = k at step k
@@ -868,7 +821,6 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
 #pragma unroll
     for (int q = 0; q < TSL; q++) { GE[q] = 0.0; if (TWO_PAR) GO[q] = 0.0; }
     for (int k = TURN + 1; k <= n; k++) {
-      TLMARK(0, k);
       if (k < n) {
         const int d = k;
         const int ncell = n - d, sh = d >> 1, par = d & 1;
@@ -889,28 +841,13 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
             sm.partG[par][my_sig][T0 + my_tb * WAVE + lane] = accG;
           }
         }
-        STAMP(0);
-        TLMARK(1, k);
         run_tiles(d);
-        TLMARK3(k);
         run_items(d);
-        STAMP(6);
-        TLMARK(2, k);
       }
       __syncthreads();
-      STAMP(3);
-#ifdef DRNA_STAMPS
-      if (blockIdx.x == 0 && aw == 0 && lane == 0) dbg[512 + k] = st_last;
-      if (blockIdx.x == 0 && lane == 0) dbg[1024 + (wave - NB) * 256 + k] = st_acc[3];
-#endif
     }
   }
 
-#ifdef DRNA_STAMPS
-  if (blockIdx.x == 0 && lane == 0)
-    for (int k = 0; k < 8; k++) dbg[wave * 8 + k] = st_acc[k];
-#endif
-  TLMARK(0, 2);
   // the remaining exterior columns -- their sums by one wave each, side by side (column j reads q5 up to j - 5, which the loop has
   // left final; the same lanes add the same terms in the same order as pf_q5_column), the three-step recurrence by one lane -- then Z
   const int jq0 = max(TURN + 2, n - 2);
@@ -941,7 +878,6 @@ __device__ __forceinline__ void pf_lds_body(PfFastSmem<NT>& sm, PfArgs A, const 
       }
       if (hm) st_agent(flagA, A.hbase + STRIP_DONE);
     }
-    TLMARK(0, 3);
   }
 }
 

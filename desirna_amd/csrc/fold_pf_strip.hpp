@@ -46,12 +46,6 @@ namespace drna {
 // registers across the steps, the 256 sums stored to the table DFAR at the end of the window.  The per-diagonal multiloop items
 // keep only the NEAR split points of their cells (m < m_lo or m > m_hi: at most 24 + PKT_L on either side, from rows written or
 // read a few steps ago) and start from the DFAR entry.  Every sum has one fixed order of additions: Epf is reproducible.
-#ifndef PSTRIP_FARK
-#define PSTRIP_FARK 1
-#endif
-#ifndef PSTRIP_SKIP
-#define PSTRIP_SKIP 0        // diagnostic builds only (timing; results wrong): 1 no multiloop items, 2 no bulge / 1xn items, 4 no small shapes, 8 no towers, 16 no tile products
-#endif
 // (measured and dropped, DESIGN 3.8: tile rows on the tower waves with the tower step under the operands' round trip -- 100
 // spilled VGPRs, 2.5 vs 1.57 ms at 400 nt; the step's first item between a floating wave's tile loads and its products -- 36
 // spills, 1.72 vs 1.59 ms; tile rows on the floating waves only -- 1.61 vs 1.58 ms)
@@ -65,7 +59,7 @@ constexpr int PKT_NB = 4;                               // near split points per
 #endif
 constexpr int PKT_W = DRNA_PKT_W;                       // steps a tile product is spread over (<= 16: the windows of consecutive block distances do not overlap)
 constexpr int PKT_L = DRNA_PKT_L;                       // the far range's operands are final this many diagonals before d_min
-constexpr int PKT_BMIN = PSTRIP_FARK ? (44 + 2 * PKT_L + 15) / 16 : (1 << 20);   // smallest block distance with a far range
+constexpr int PKT_BMIN = (44 + 2 * PKT_L + 15) / 16;   // smallest block distance with a far range
 static_assert(PKT_W >= 1 && PKT_W <= 16, "tile windows must not overlap");
 static_assert(PKT_L >= 3, "a chunk must be final and visible when its step comes");
 
@@ -124,7 +118,7 @@ __device__ __forceinline__ void strip_tower(SM& sm, double (&G)[PGSLOTS], int d,
       G[qx] = mine ? v : G[qx];
     }
   }
-  const double accG = (PSTRIP_SKIP & 8) ? 0.0 : pf_tower_step(sm, G, par, i * 8, my_g, lane);
+  const double accG = pf_tower_step(sm, G, par, i * 8, my_g, lane);
   if (live) sm.partG[par][my_g][phys] = accG;
   if (has_down && live && iraw == 1) {               // the tower leaves the strip: its sums go into the record
     double* rec = rec_out + (long long)d * STRIP_REC + 48 + my_g * PGSLOTS;
@@ -300,8 +294,7 @@ __device__ void pf_strip_body(PfStripSmem<NT>& sm, PfArgs A, StripLink lk, int q
     int kssh = nterm > 192 ? 3 : nterm > 96 ? 2 : nterm > 48 ? 1 : 0;
     if (ncell <= 32 && kssh < 2) kssh = 2;
     const int KS = 1 << kssh, KG = 4 << kssh;
-    const int nK = (PSTRIP_SKIP & 1) ? 0 : ((ncell + 31) >> 5) << kssh, nE = (PSTRIP_SKIP & 2) ? 0 : (pcnt + 3) >> 2,
-              nX = (PSTRIP_SKIP & 4) ? 0 : 3 * ((pcnt + WAVE - 1) / WAVE);
+    const int nK = ((ncell + 31) >> 5) << kssh, nE = (pcnt + 3) >> 2, nX = 3 * ((pcnt + WAVE - 1) / WAVE);
     const int nItems = __builtin_amdgcn_readfirstlane(nK + nE + nX);
     // two queues: the multiloop items (16 loads in flight per lane: only waves that hold no tower sums take them), then the shape items
     auto pop = [&]() -> int {
@@ -538,7 +531,7 @@ __device__ void pf_strip_body(PfStripSmem<NT>& sm, PfArgs A, StripLink lk, int q
     const int x = k + 15 + PKT_W, B = x >> 4;
     g = x & 15;
     q.t = tf + NTW * o; q.bj = q.t + B;
-    q.on = PSTRIP_FARK && !(PSTRIP_SKIP & 16) && g < PKT_W && B >= PKT_BMIN && 16 * q.t < wid && 16 * q.bj + 1 <= n_loc;   // (wave-uniform)
+    q.on = g < PKT_W && B >= PKT_BMIN && 16 * q.t < wid && 16 * q.bj + 1 <= n_loc;   // (wave-uniform)
     q.m_lo = 16 * q.t + 31 + PKT_L; q.m_hi = 16 * q.bj - 13 - PKT_L;
     q.nch = (q.m_hi - q.m_lo + 4) >> 2;
     const int nl = (q.nch + 1) >> 1, nh = q.nch >> 1;
