@@ -29,6 +29,7 @@
 #include "fold_pf_strip.hpp"
 #include "fold_subopt.hpp"
 #include "fold_cofold_subopt.hpp"
+#include "fold_cofold_outside.hpp"
 #include "host_driver.hpp"
 #include "tables.hpp"
 
@@ -852,14 +853,22 @@ extern "C" int drna_info(const drna_engine* e, int64_t out[6]) {
 
 // ---------------------------------------------------------------- ensemble defect (inside + outside recursion)
 
+// workspace of the outside recursions (one strand: OB, OBI, A, CL and q5; two strands: the four tables without joining pairs),
+// ws_slots sequences of max_L, allocated on first use
+static int outside_workspace(drna_engine* e) {
+  if (!e->d_ws_out) {
+    const size_t b = (size_t)outside_ws_stride(e->max_L + 2) * sizeof(double) * e->ws_slots;
+    HIP_TRY(hipMalloc((void**)&e->d_ws_out, b));
+    e->ws_bytes += b;
+  }
+  return DRNA_OK;
+}
+
 // one batch that fits the workspaces; its sequences are the caller's r_base, r_base + 1, ...
 static int ensemble_defect_impl(drna_engine* e, int R, int L, const char* d_seqs, double* d_edef, double* d_bpp, int r_base) {
   HIP_TRY(hipSetDevice(e->device));
-  const int ldmax = e->max_L + 2, ld = L + 2;
-  if (!e->d_ws_out) {
-    HIP_TRY(hipMalloc((void**)&e->d_ws_out, (size_t)outside_ws_stride(ldmax) * sizeof(double) * e->ws_slots));
-    e->ws_bytes += (size_t)outside_ws_stride(ldmax) * sizeof(double) * e->ws_slots;
-  }
+  const int ld = L + 2;
+  { const int rc = outside_workspace(e); if (rc != DRNA_OK) return rc; }
   for (int k = 0; k < R; k++) e->h_status[e->max_R + k] = ST_OK;
   // the general inside kernel: it leaves qb / qm / qm1 in the workspace (the LDS kernel keeps only rings)
   PfArgs a = pf_args(e, d_seqs, L, ld, e->d_Epf);
@@ -1327,6 +1336,84 @@ extern "C" int drna_cofold_subopt_energy_batch(drna_engine* e, int R, int L, int
   HIP_TRY(hipMemcpy(E2, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (E12) HIP_TRY(hipMemcpy(E12, e->d_Epf, (size_t)2 * R * sizeof(int32_t), hipMemcpyDeviceToHost));
   return DRNA_OK;
+}
+
+// ---------------------------------------------------------------- two strands: pair probabilities and ensemble defect (-sf Edef)
+
+// one batch that fits the workspaces (cofold_pf_kernel, then the outside recursion on its tables); pairs r_base, r_base + 1, ...
+static int cofold_edef_impl(drna_engine* e, int R, int L, int cut, const char* d_seqs, double* d_edef, double* d_bpp, int r_base) {
+  const int ld = L + 2;
+  for (int k = 0; k < R; k++) e->h_status[e->max_R + k] = ST_OK;
+  CoArgs a;
+  a.F = e->d_pfT; a.plan = e->d_plan; a.hp_w = e->d_hp_w; a.scale = e->d_scale; a.eMLb = e->d_eMLb;
+  a.seqs = d_seqs; a.L = L; a.cut = cut; a.ld = ld;
+  a.eDuplexInit = std::exp(-(double)e->H.DuplexInit * 10.0 / e->H.pf.kT);
+  a.wsp = e->d_ws_pf; a.wsp_stride = (long long)pf_ws_stride(ld);
+  a.F4 = e->d_F4; a.status_pf = e->d_status + e->max_R;
+  CoOutArgs o;
+  o.F = e->d_pfT; o.plan = e->d_plan; o.scale = e->d_scale; o.eMLb = e->d_eMLb;
+  o.seqs = d_seqs; o.L = L; o.cut = cut; o.ld = ld; o.eDuplexInit = a.eDuplexInit;
+  o.wsp = e->d_ws_pf; o.wsp_stride = a.wsp_stride;         // the four outside tables fill the slot behind QB, QM, QM1, INFO
+  o.wu = e->d_ws_out; o.wu_stride = outside_ws_stride(ld);
+  o.pt = e->d_pt; o.edef = d_edef; o.bpp = d_bpp; o.status_pf = a.status_pf;
+  HIP_TRY(hipEventRecord(e->ev_o0, e->s_pf));
+  hipLaunchKernelGGL(cofold_pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_o1, e->s_pf));
+  hipLaunchKernelGGL(cofold_outside_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, o);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_o2, e->s_pf));
+  HIP_TRY(hipStreamSynchronize(e->s_pf));
+  HIP_TRY(hipEventElapsedTime(&e->timing_edef[0], e->ev_o0, e->ev_o1));
+  HIP_TRY(hipEventElapsedTime(&e->timing_edef[1], e->ev_o1, e->ev_o2));
+  return fold_status(e, R, false, true, nullptr, r_base, "unexpected status of the co-fold partition function");
+}
+
+extern "C" int drna_cofold_ensemble_defect_batch(drna_engine* e, int R, int L, int cut, const char* seqs, double* edef, double* bpp) {
+  if (!e) return DRNA_ERR_ARG;
+  if (R < 1 || R > e->max_R || L < 2 || L > e->max_L || cut < 1 || cut >= L || !seqs || !edef) {
+    e->err = "drna_cofold_ensemble_defect_batch: bad argument (R, L within the engine's limits, 1 <= cut < L; seqs and edef required)";
+    return DRNA_ERR_ARG;
+  }
+  if (e->n_targets < 1 || e->L_targets != L) {
+    e->err = "drna_cofold_ensemble_defect_batch: needs drna_set_targets() with the same L ('&' removed; targets[0] is the reference structure)";
+    return DRNA_ERR_ARG;
+  }
+  static_assert(sizeof(double) == 8, "workspace strides are counted in doubles");
+  if (cofold_outside_ws_stride(L + 2) > (long long)pf_ws_stride(L + 2) || 4ll * (L + 2) * (L + 2) > outside_ws_stride(L + 2)) {
+    e->err = "drna_cofold_ensemble_defect_batch: workspace slot too small for the outside tables";
+    return DRNA_ERR_INTERNAL;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  { const int rc = outside_workspace(e); if (rc != DRNA_OK) return rc; }
+  if (!e->d_edef) HIP_TRY(hipMalloc((void**)&e->d_edef, (size_t)e->max_R * sizeof(double)));
+  if (!e->d_F4) HIP_TRY(hipMalloc((void**)&e->d_F4, (size_t)4 * e->max_R * sizeof(double)));
+  HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
+  double* d_bpp = nullptr;
+  const size_t nb = (size_t)R * (L + 1) * (L + 1) * sizeof(double);
+  if (bpp) {
+    HIP_TRY(hipMalloc((void**)&d_bpp, nb));
+    hipError_t z = hipMemset(d_bpp, 0, nb);
+    if (z == hipSuccess) z = hipDeviceSynchronize();     // the memset runs on the null stream, the kernels on a non-blocking stream
+    if (z != hipSuccess) { (void)hipFree(d_bpp); e->err = "hipMemset(bpp)"; return DRNA_ERR_DEVICE; }
+  }
+  // more pairs than the workspaces hold (DRNA_WS_GB): one sub-batch of ws_slots after the other; last_edef_timing = their sums
+  int rc = DRNA_OK;
+  float sum[2] = {0, 0};
+  for (int r0 = 0; r0 < R && rc == DRNA_OK; r0 += e->ws_slots) {
+    const int m = std::min(e->ws_slots, R - r0);
+    rc = cofold_edef_impl(e, m, L, cut, e->d_seqs + (size_t)r0 * L, e->d_edef + r0,
+                          d_bpp ? d_bpp + (size_t)r0 * (L + 1) * (L + 1) : nullptr, r0);
+    sum[0] += e->timing_edef[0]; sum[1] += e->timing_edef[1];
+  }
+  e->timing_edef[0] = sum[0]; e->timing_edef[1] = sum[1];
+  if (rc == DRNA_OK) {
+    hipError_t c1 = hipMemcpy(edef, e->d_edef, (size_t)R * sizeof(double), hipMemcpyDeviceToHost);
+    hipError_t c2 = bpp ? hipMemcpy(bpp, d_bpp, nb, hipMemcpyDeviceToHost) : hipSuccess;
+    if (c1 != hipSuccess || c2 != hipSuccess) { e->err = "hipMemcpy(edef/bpp)"; rc = DRNA_ERR_DEVICE; }
+  }
+  if (d_bpp) (void)hipFree(d_bpp);
+  return rc;
 }
 
 // ---------------------------------------------------------------- host-side batched MC helpers (no device work)

@@ -9,7 +9,9 @@ motif bonus (:121-123, :443-450).  What changes is where the numbers come from: 
 E(target), E(alt targets) for every replica of the batch, instead of 3-8 ViennaRNA calls per
 sequence inside a forked worker.
 
-``Edef`` is served by ``Engine.ensemble_defect`` (inside + outside recursion on the GPU).
+``Edef`` is served by ``Engine.ensemble_defect`` (inside + outside recursion on the GPU), for two strands by
+``Engine.cofold_ensemble_defect`` (the outside recursion under the co-fold rules; no golden in the reference: checked against
+exhaustive enumeration); two-strand ``Ed-MFE`` takes the co-fold MFE energy.
 
 Two strands (``oligo_state`` heterodimer / homodimer, and ``avoid`` = ``-o on``) go through ``Engine.cofold_batch``
 (co-fold MFE + partition function + two-strand evaluation on the GPU); the oligomer / monomer bonus terms of
@@ -242,13 +244,15 @@ class ReplicaScorer:
 
     def _score_two_strands(self, seqs):
         """reference score_sequence() for oligo_state heterodimer / homodimer (:70-118): Epf = pf_dimer()[-1] (FAB), MFE
-        structure of mfe_dimer() with the '&' re-inserted, E(target) of the two-strand evaluation, with -nd on the second-best
+        structure of mfe_dimer() with the '&' re-inserted, E(target) of the two-strand evaluation, Ed-MFE against the co-fold MFE energy and
+        Edef in the co-fold ensemble (the reference calls get_MFE / get_ensemble_defect whatever the oligo_state), with -nd on the second-best
         co-fold energy of the solved candidates, then the oligomer bonus (hetero-dimer, or homodimer with two different
         structures) or the monomer-fraction term (two equal structures), then the motifs -- the reference's order of additions."""
         out = self.engine.cofold_batch(seqs, _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL)
         metrics = batch_metrics(self.input_file.sec_struct.replace("&", "Ee"),
                                 [s.replace("&", "Ee") for s in out["mfe_ss"]])
         ss1, ss2 = self.input_file.sec_struct.split("&")
+        edef = self.engine.cofold_ensemble_defect(seqs) if self.want_edef else None
         res = []
         for k, seq in enumerate(seqs):
             sc = ScoreSeq(sequence=seq)
@@ -263,8 +267,11 @@ class ReplicaScorer:
             for function, _ in self.sim_options.scoring_f:
                 if function == 'sln_Epf':
                     sc.get_sln_Epf()
-                if function in ('Ed-MFE', 'Edef'):
-                    raise NotImplementedError("-sf %s is a one-strand quantity in the reference (RNA.fold / md defaults)" % function)
+                if function == 'Ed-MFE':
+                    sc.get_MFE(int(out["Emfe"][k]) / 100.0)
+                    sc.get_edesired_minus_MFE()
+                if function == 'Edef':
+                    sc.get_ensemble_defect(float(edef[k]))
             sc.get_scoring_function(self.sim_options.scoring_f)
             sc.oligo_fraction = float(oligo_fraction(out["FA"][k], out["FB"][k], out["FcAB"][k]))
             if self.oligo_state == "heterodimer" or ss1 != ss2:

@@ -25,7 +25,7 @@ EXPORTS = ("drna_create", "drna_destroy", "drna_last_error", "drna_set_targets",
            "drna_score_batch_device", "drna_last_timing", "drna_info", "drna_simscore_batch", "drna_propose_batch",
            "drna_metropolis_batch", "drna_ensemble_defect_batch", "drna_ensemble_defect_batch_device",
            "drna_last_edef_timing", "drna_propose_batch_alt", "drna_set_targets_ragged", "drna_score_ragged", "drna_cofold_batch", "drna_mc_run", "drna_subopt_energy_batch",
-           "drna_cofold_subopt_energy_batch",
+           "drna_cofold_subopt_energy_batch", "drna_cofold_ensemble_defect_batch",
            "drna_subopt_structs_batch", "drna_rng_seed", "drna_rng_random", "drna_set_option", "drna_timing_sums", "drna_debug_strip_clocks", "drna_get_option", "drna_abi_version")
 
 ABI_VERSION = 3        # DRNA_ABI_VERSION this binding was written against (include/desirna_amd.h)
@@ -93,6 +93,8 @@ def load_library(path=None):
     L.drna_subopt_energy_batch.argtypes = [vp, ci, ci, C.c_char_p, vp, vp]
     L.drna_cofold_subopt_energy_batch.restype = ci
     L.drna_cofold_subopt_energy_batch.argtypes = [vp, ci, ci, ci, C.c_char_p, vp, vp]
+    L.drna_cofold_ensemble_defect_batch.restype = ci
+    L.drna_cofold_ensemble_defect_batch.argtypes = [vp, ci, ci, ci, C.c_char_p, vp, vp]
     L.drna_subopt_structs_batch.restype = ci
     L.drna_subopt_structs_batch.argtypes = [vp, ci, ci, C.c_char_p, ci, vp, vp]
     L.drna_simscore_batch.restype = ci
@@ -356,6 +358,26 @@ class Engine:
         bpp = np.zeros((R, L + 1, L + 1), dtype=np.float64) if want_bpp else None
         self._check(self._L.drna_ensemble_defect_batch(self._h, R, L, "".join(seqs).encode("ascii"), ed.ctypes.data,
                                                        bpp.ctypes.data if want_bpp else None))
+        return (ed, bpp) if want_bpp else ed
+
+    def cofold_ensemble_defect(self, seqs, want_bpp=False):
+        """Two strands: ensemble defect of each 'AAAA&BBBB' pair against targets[0] ('&' removed) in the ensemble of
+        :meth:`cofold_batch`'s partition function (connected structures weighted by expDuplexInit, halved for two equal
+        strands).  Returns float64[R]; with want_bpp also the (R, L+1, L+1) pair probabilities over the concatenation
+        (1-based, upper triangle)."""
+        a0, b0 = seqs[0].split("&")
+        cut, L = len(a0), len(a0) + len(b0)
+        flat = []
+        for s in seqs:
+            a, b = s.split("&")
+            if len(a) != cut or len(a) + len(b) != L:
+                raise ValueError("all pairs of a batch must have the same strand lengths")
+            flat.append(a + b)
+        R = len(flat)
+        ed = np.zeros(R, dtype=np.float64)
+        bpp = np.zeros((R, L + 1, L + 1), dtype=np.float64) if want_bpp else None
+        self._check(self._L.drna_cofold_ensemble_defect_batch(self._h, R, L, cut, "".join(flat).encode("ascii"), ed.ctypes.data,
+                                                              bpp.ctypes.data if want_bpp else None))
         return (ed, bpp) if want_bpp else ed
 
     def ensemble_defect_arrays(self, seqs_u8):

@@ -150,6 +150,21 @@ int drna_subopt_energy_batch(drna_engine *e, int R, int L, const char *seqs, int
 int drna_cofold_subopt_energy_batch(drna_engine *e, int R, int L, int cut, const char *seqs, int32_t *E2, int32_t *E12);
 
 /*
+ * Base-pair probabilities and ensemble defect of R sequence pairs (two-strand -sf Edef): the reference's
+ * ScoreSeq.get_ensemble_defect on a heterodimer / homodimer input (utils/energy_scores.py:93-94, :362-374; it pins no value
+ * there).  Pairs as for drna_cofold_batch: total length L, both strands concatenated WITHOUT the '&', the first strand `cut`
+ * nucleotides long (1 <= cut < L).  The ensemble is that of drna_cofold_batch's partition function: a structure weighs its
+ * Boltzmann factor, times expDuplexInit if a pair joins the strands (halved when the two strands are the same sequence), so
+ * the weights sum to exp(-FAB / kT).  P(i,j) = weight of the structures that hold the pair (i,j) / weight of all;
+ * edef = (1/L) [ sum_{i unpaired in target} sum_j P(i,j) + sum_{i paired with m} (1 - P(i,m)) ] against targets[0] of
+ * drna_set_targets (same L, '&' removed, '(' ')' pairs only).
+ *   edef  R doubles
+ *   bpp   R*(L+1)*(L+1) doubles, may be NULL: P(i,j) at [i*(L+1)+j], 1 <= i < j <= L, every other entry 0
+ * A new symbol: no existing buffer changes, DRNA_ABI_VERSION stays 3.
+ */
+int drna_cofold_ensemble_defect_batch(drna_engine *e, int R, int L, int cut, const char *seqs, double *edef, double *bpp);
+
+/*
  * The K lowest-energy structures of R sequences, energies and dot-bracket strings.  Replaces
  * get_first_suboptimal_structure_and_energy(seq, fc, k)[0] for k = 1 .. #alternative structures, the call behind
  * get_alt_mcc() (utils/sequence_utils.py:766-793, utils/energy_scores.py:453-488): entry k of ViennaRNA's energy-sorted
