@@ -184,6 +184,18 @@ static EvalArgs eval_args(const drna_engine* e, const char* seqs, int L, int32_t
   a.seqs = seqs; a.pt = e->d_pt; a.L = L; a.n_targets = e->n_targets; a.Ed = Ed;
   return a;
 }
+// two strands of L nucleotides in all, the first one cut long (F4 is allocated by the entry points that fold two strands)
+static CoArgs co_args(const drna_engine* e, const char* seqs, int L, int cut, int ld) {
+  CoArgs a;
+  a.T = e->d_mfeT; a.F = e->d_pfT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.hp_w = e->d_hp_w;
+  a.scale = e->d_scale; a.eMLb = e->d_eMLb; a.seqs = seqs; a.L = L; a.cut = cut; a.ld = ld;
+  a.DuplexInit = e->H.DuplexInit;
+  a.eDuplexInit = std::exp(-(double)e->H.DuplexInit * 10.0 / e->H.pf.kT);
+  a.wsm = e->d_ws_mfe; a.wsm_stride = (long long)mfe_ws_stride(ld);
+  a.wsp = e->d_ws_pf; a.wsp_stride = (long long)pf_ws_stride(ld);
+  a.Emfe = e->d_Emfe; a.ss = e->d_ss; a.F4 = e->d_F4; a.status = e->d_status; a.status_pf = e->d_status + e->max_R;
+  return a;
+}
 // hand-over flags hold (epoch << 12 | diagonal) for the strips and ((epoch * 8 + round) << 10 | diagonal) for the two-workgroup
 // kernel, compared wrap-safe: valid while live values are less than 2^31 apart, i.e. 2^19 (2^18) epochs.  Reset at a quarter of that.
 constexpr int STRIP_EPOCH_RESET = 1 << 17, DUAL_EPOCH_RESET = 1 << 16;
@@ -851,7 +863,30 @@ extern "C" int drna_info(const drna_engine* e, int64_t out[6]) {
   return DRNA_OK;
 }
 
-// ---------------------------------------------------------------- ensemble defect (inside + outside recursion)
+// ---------------------------------------------------------------- auxiliary entry points: shared checks
+
+// Argument check of the entry points beside the score_batch family; who names the entry point in the message.  R and L within the
+// engine's limits, two strands (cut given) split inside the sequence, and ok: the required pointers (need says which) are there
+static int aux_check(drna_engine* e, const char* who, int R, int L, const int* cut, bool ok, const char* need) {
+  if (R >= 1 && R <= e->max_R && L >= 1 && L <= e->max_L && (!cut || (*cut >= 1 && *cut < L)) && ok) return DRNA_OK;
+  e->err = std::string(who) + ": bad argument (R, L within the engine's limits" + (cut ? ", 1 <= cut < L; " : "; ") + need + ")";
+  return DRNA_ERR_ARG;
+}
+static int need_targets(drna_engine* e, const char* who, int L) {
+  if (e->n_targets >= 1 && e->L_targets == L) return DRNA_OK;
+  e->err = std::string(who) + ": needs drna_set_targets() with the same L ('&' removed; targets[0] is the reference structure)";
+  return DRNA_ERR_ARG;
+}
+static int fits_workspace(drna_engine* e, const char* who, int R) {
+  if (R <= e->ws_slots) return DRNA_OK;
+  e->err = std::string(who) + ": batch larger than the workspace (raise DRNA_WS_GB or split the batch)";
+  return DRNA_ERR_ARG;
+}
+static void reset_status(drna_engine* e) {
+  for (int k = 0; k < 2 * e->max_R; k++) e->h_status[k] = ST_OK;
+}
+
+// ---------------------------------------------------------------- ensemble defect (inside + outside recursion), one and two strands
 
 // workspace of the outside recursions (one strand: OB, OBI, A, CL and q5; two strands: the four tables without joining pairs),
 // ws_slots sequences of max_L, allocated on first use
@@ -864,12 +899,27 @@ static int outside_workspace(drna_engine* e) {
   return DRNA_OK;
 }
 
+// the inside kernel, then the outside kernel on its tables, both on the partition function's stream and timed (timing_edef);
+// the R sequences are the caller's r_base, r_base + 1, ...
+template <class Inside, class Outside>
+static int inside_outside(drna_engine* e, int R, int r_base, const char* internal_msg, Inside&& inside, Outside&& outside) {
+  reset_status(e);
+  HIP_TRY(hipEventRecord(e->ev_o0, e->s_pf));
+  inside();
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_o1, e->s_pf));
+  outside();
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_o2, e->s_pf));
+  HIP_TRY(hipStreamSynchronize(e->s_pf));
+  HIP_TRY(hipEventElapsedTime(&e->timing_edef[0], e->ev_o0, e->ev_o1));
+  HIP_TRY(hipEventElapsedTime(&e->timing_edef[1], e->ev_o1, e->ev_o2));
+  return fold_status(e, R, false, true, nullptr, r_base, internal_msg);
+}
+
 // one batch that fits the workspaces; its sequences are the caller's r_base, r_base + 1, ...
 static int ensemble_defect_impl(drna_engine* e, int R, int L, const char* d_seqs, double* d_edef, double* d_bpp, int r_base) {
-  HIP_TRY(hipSetDevice(e->device));
   const int ld = L + 2;
-  { const int rc = outside_workspace(e); if (rc != DRNA_OK) return rc; }
-  for (int k = 0; k < R; k++) e->h_status[e->max_R + k] = ST_OK;
   // the general inside kernel: it leaves qb / qm / qm1 in the workspace (the LDS kernel keeps only rings)
   PfArgs a = pf_args(e, d_seqs, L, ld, e->d_Epf);
   a.q5_stride = outside_ws_stride(ld);
@@ -880,36 +930,42 @@ static int ensemble_defect_impl(drna_engine* e, int R, int L, const char* d_seqs
   o.ws = e->d_ws_pf; o.ws_stride = a.ws_stride;
   o.wo = e->d_ws_out; o.wo_stride = outside_ws_stride(ld);
   o.pt = e->d_pt; o.edef = d_edef; o.bpp = d_bpp; o.pf_status = e->d_status + e->max_R;
-  HIP_TRY(hipEventRecord(e->ev_o0, e->s_pf));
-  hipLaunchKernelGGL(pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->ev_o1, e->s_pf));
-  hipLaunchKernelGGL(outside_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, o);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->ev_o2, e->s_pf));
-  HIP_TRY(hipStreamSynchronize(e->s_pf));
-  HIP_TRY(hipEventElapsedTime(&e->timing_edef[0], e->ev_o0, e->ev_o1));
-  HIP_TRY(hipEventElapsedTime(&e->timing_edef[1], e->ev_o1, e->ev_o2));
-  return fold_status(e, R, false, true, nullptr, r_base, "unexpected status of the partition function");
+  return inside_outside(e, R, r_base, "unexpected status of the partition function",
+                        [&] { hipLaunchKernelGGL(pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a); },
+                        [&] { hipLaunchKernelGGL(outside_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, o); });
+}
+// two strands (cofold_pf_kernel, then the outside recursion on its tables); pairs r_base, r_base + 1, ...
+static int cofold_edef_impl(drna_engine* e, int R, int L, int cut, const char* d_seqs, double* d_edef, double* d_bpp, int r_base) {
+  const int ld = L + 2;
+  const CoArgs a = co_args(e, d_seqs, L, cut, ld);
+  CoOutArgs o;
+  o.F = e->d_pfT; o.plan = e->d_plan; o.scale = e->d_scale; o.eMLb = e->d_eMLb;
+  o.seqs = d_seqs; o.L = L; o.cut = cut; o.ld = ld; o.eDuplexInit = a.eDuplexInit;
+  o.wsp = e->d_ws_pf; o.wsp_stride = a.wsp_stride;         // the four outside tables fill the slot behind QB, QM, QM1, INFO
+  o.wu = e->d_ws_out; o.wu_stride = outside_ws_stride(ld);
+  o.pt = e->d_pt; o.edef = d_edef; o.bpp = d_bpp; o.status_pf = a.status_pf;
+  return inside_outside(e, R, r_base, "unexpected status of the co-fold partition function",
+                        [&] { hipLaunchKernelGGL(cofold_pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a); },
+                        [&] { hipLaunchKernelGGL(cofold_outside_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, o); });
 }
 
-extern "C" int drna_ensemble_defect_batch_device(drna_engine* e, int R, int L, const char* d_seqs, double* d_edef,
-                                                 double* d_bpp) {
-  if (!e) return DRNA_ERR_ARG;
-  if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || !d_seqs || !d_edef) {
-    e->err = "drna_ensemble_defect_batch: bad argument (R, L within the engine's limits; seqs and edef required)";
-    return DRNA_ERR_ARG;
+// R sequences in device memory (cut = 0: one strand).  More of them than the workspaces hold (DRNA_WS_GB): one sub-batch of
+// ws_slots after the other; last_edef_timing = their sums
+static int edef_batch_device(drna_engine* e, int R, int L, int cut, const char* d_seqs, double* d_edef, double* d_bpp) {
+  static_assert(sizeof(double) == 8, "workspace strides are counted in doubles");
+  if (cut && (cofold_outside_ws_stride(L + 2) > (long long)pf_ws_stride(L + 2) || 4ll * (L + 2) * (L + 2) > outside_ws_stride(L + 2))) {
+    e->err = "drna_cofold_ensemble_defect_batch: workspace slot too small for the outside tables";
+    return DRNA_ERR_INTERNAL;
   }
-  if (e->n_targets < 1 || e->L_targets != L) {
-    e->err = "drna_ensemble_defect_batch: needs drna_set_targets() with the same L (targets[0] is the reference structure)";
-    return DRNA_ERR_ARG;
-  }
-  // more sequences than the workspaces hold (DRNA_WS_GB): one sub-batch of ws_slots after the other; last_edef_timing = their sums
+  HIP_TRY(hipSetDevice(e->device));
+  { const int rc = outside_workspace(e); if (rc != DRNA_OK) return rc; }
+  if (cut && !e->d_F4) HIP_TRY(hipMalloc((void**)&e->d_F4, (size_t)4 * e->max_R * sizeof(double)));
   float sum[2] = {0, 0};
   for (int r0 = 0; r0 < R; r0 += e->ws_slots) {
     const int m = std::min(e->ws_slots, R - r0);
-    const int rc = ensemble_defect_impl(e, m, L, d_seqs + (size_t)r0 * L, d_edef + r0,
-                                        d_bpp ? d_bpp + (size_t)r0 * (L + 1) * (L + 1) : nullptr, r0);
+    const char* s = d_seqs + (size_t)r0 * L;
+    double* b = d_bpp ? d_bpp + (size_t)r0 * (L + 1) * (L + 1) : nullptr;
+    const int rc = cut ? cofold_edef_impl(e, m, L, cut, s, d_edef + r0, b, r0) : ensemble_defect_impl(e, m, L, s, d_edef + r0, b, r0);
     if (rc != DRNA_OK) return rc;
     sum[0] += e->timing_edef[0]; sum[1] += e->timing_edef[1];
   }
@@ -917,12 +973,8 @@ extern "C" int drna_ensemble_defect_batch_device(drna_engine* e, int R, int L, c
   return DRNA_OK;
 }
 
-extern "C" int drna_ensemble_defect_batch(drna_engine* e, int R, int L, const char* seqs, double* edef, double* bpp) {
-  if (!e) return DRNA_ERR_ARG;
-  if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || !seqs || !edef) {
-    e->err = "drna_ensemble_defect_batch: bad argument (R, L within the engine's limits; seqs and edef required)";
-    return DRNA_ERR_ARG;
-  }
+// the same from and to host memory; bpp optional
+static int edef_batch_host(drna_engine* e, int R, int L, int cut, const char* seqs, double* edef, double* bpp) {
   HIP_TRY(hipSetDevice(e->device));
   if (!e->d_edef) HIP_TRY(hipMalloc((void**)&e->d_edef, (size_t)e->max_R * sizeof(double)));
   HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
@@ -931,9 +983,10 @@ extern "C" int drna_ensemble_defect_batch(drna_engine* e, int R, int L, const ch
   if (bpp) {
     HIP_TRY(hipMalloc((void**)&d_bpp, nb));
     hipError_t z = hipMemset(d_bpp, 0, nb);
+    if (z == hipSuccess) z = hipDeviceSynchronize();     // the memset runs on the null stream, the kernels on a non-blocking stream
     if (z != hipSuccess) { (void)hipFree(d_bpp); e->err = "hipMemset(bpp)"; return DRNA_ERR_DEVICE; }
   }
-  int rc = drna_ensemble_defect_batch_device(e, R, L, e->d_seqs, e->d_edef, d_bpp);
+  int rc = edef_batch_device(e, R, L, cut, e->d_seqs, e->d_edef, d_bpp);
   if (rc == DRNA_OK) {
     hipError_t c1 = hipMemcpy(edef, e->d_edef, (size_t)R * sizeof(double), hipMemcpyDeviceToHost);
     hipError_t c2 = bpp ? hipMemcpy(bpp, d_bpp, nb, hipMemcpyDeviceToHost) : hipSuccess;
@@ -941,6 +994,30 @@ extern "C" int drna_ensemble_defect_batch(drna_engine* e, int R, int L, const ch
   }
   if (d_bpp) (void)hipFree(d_bpp);
   return rc;
+}
+
+static int edef_check(drna_engine* e, const char* who, int R, int L, const int* cut, bool ok) {
+  const int rc = aux_check(e, who, R, L, cut, ok, "seqs and edef required");
+  return rc != DRNA_OK ? rc : need_targets(e, who, L);
+}
+
+extern "C" int drna_ensemble_defect_batch_device(drna_engine* e, int R, int L, const char* d_seqs, double* d_edef,
+                                                 double* d_bpp) {
+  if (!e) return DRNA_ERR_ARG;
+  const int rc = edef_check(e, "drna_ensemble_defect_batch", R, L, nullptr, d_seqs && d_edef);
+  return rc != DRNA_OK ? rc : edef_batch_device(e, R, L, 0, d_seqs, d_edef, d_bpp);
+}
+
+extern "C" int drna_ensemble_defect_batch(drna_engine* e, int R, int L, const char* seqs, double* edef, double* bpp) {
+  if (!e) return DRNA_ERR_ARG;
+  const int rc = edef_check(e, "drna_ensemble_defect_batch", R, L, nullptr, seqs && edef);
+  return rc != DRNA_OK ? rc : edef_batch_host(e, R, L, 0, seqs, edef, bpp);
+}
+
+extern "C" int drna_cofold_ensemble_defect_batch(drna_engine* e, int R, int L, int cut, const char* seqs, double* edef, double* bpp) {
+  if (!e) return DRNA_ERR_ARG;
+  const int rc = edef_check(e, "drna_cofold_ensemble_defect_batch", R, L, &cut, seqs && edef);
+  return rc != DRNA_OK ? rc : edef_batch_host(e, R, L, cut, seqs, edef, bpp);
 }
 
 extern "C" int drna_last_edef_timing(const drna_engine* e, float out[2]) {
@@ -1168,42 +1245,63 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
   return DRNA_OK;
 }
 
-// ---------------------------------------------------------------- second-best structure energy (-nd on)
+// ---------------------------------------------------------------- second-best structure energy (-nd on), one and two strands
 
-extern "C" int drna_subopt_energy_batch(drna_engine* e, int R, int L, const char* seqs, int32_t* E2, int32_t* E12) {
-  if (!e) return DRNA_ERR_ARG;
-  if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || !seqs || !E2) {
-    e->err = "drna_subopt_energy_batch: bad argument (R, L within the engine's limits; seqs and E2 required)";
-    return DRNA_ERR_ARG;
-  }
-  if (R > e->ws_slots) { e->err = "drna_subopt_energy_batch: batch larger than the workspace (raise DRNA_WS_GB or split the batch)"; return DRNA_ERR_ARG; }
+// what SubArgs and CoSubArgs share: the tables live in the partition function's workspace, E2 comes back in d_Emfe, E12 in d_Epf
+template <class A>
+static A sub_args(const drna_engine* e, int L) {
+  A a;
+  a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = e->d_seqs; a.L = L; a.ld = L + 2;
+  a.ws = reinterpret_cast<int32_t*>(e->d_ws_pf); a.ws_stride = 2 * (long long)pf_ws_stride(L + 2);   // int32 units of the PF workspace
+  a.E2 = e->d_Emfe; a.E12 = reinterpret_cast<int32_t*>(e->d_Epf); a.status = e->d_status;
+  return a;
+}
+// upload, launch() on the MFE stream (timed as "mfe"), status, E2 and (optional) E12 back
+template <class Launch>
+static int second_best_batch(drna_engine* e, int R, int L, const char* seqs, int32_t* E2, int32_t* E12, const char* internal_msg,
+                             Launch&& launch) {
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
-  const int ld = L + 2;
-  for (int k = 0; k < e->max_R; k++) e->h_status[k] = ST_OK;
-  SubArgs a;
-  a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = e->d_seqs; a.L = L; a.ld = ld;
-  a.ws = reinterpret_cast<int32_t*>(e->d_ws_pf); a.ws_stride = 2 * (long long)pf_ws_stride(ld);   // int32 units of the PF workspace
-  a.E2 = e->d_Emfe; a.E12 = reinterpret_cast<int32_t*>(e->d_Epf); a.status = e->d_status;
+  reset_status(e);
   HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-  hipLaunchKernelGGL(subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
+  launch();
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
   HIP_TRY(hipStreamSynchronize(e->s_mfe));
   HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
   e->timing[1] = e->timing[2] = 0.f; e->timing[3] = e->timing[0];
-  { const int rc = fold_status(e, R, true, false, nullptr, 0, "unexpected status of the second-best fold"); if (rc != DRNA_OK) return rc; }
+  { const int rc = fold_status(e, R, true, false, nullptr, 0, internal_msg); if (rc != DRNA_OK) return rc; }
   HIP_TRY(hipMemcpy(E2, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (E12) HIP_TRY(hipMemcpy(E12, e->d_Epf, (size_t)2 * R * sizeof(int32_t), hipMemcpyDeviceToHost));
   return DRNA_OK;
 }
+static int second_best_check(drna_engine* e, const char* who, int R, int L, const int* cut, bool ok) {
+  const int rc = aux_check(e, who, R, L, cut, ok, "seqs and E2 required");
+  return rc != DRNA_OK ? rc : fits_workspace(e, who, R);
+}
+
+extern "C" int drna_subopt_energy_batch(drna_engine* e, int R, int L, const char* seqs, int32_t* E2, int32_t* E12) {
+  if (!e) return DRNA_ERR_ARG;
+  { const int rc = second_best_check(e, "drna_subopt_energy_batch", R, L, nullptr, seqs && E2); if (rc != DRNA_OK) return rc; }
+  const SubArgs a = sub_args<SubArgs>(e, L);
+  return second_best_batch(e, R, L, seqs, E2, E12, "unexpected status of the second-best fold",
+                           [&] { hipLaunchKernelGGL(subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a); });
+}
+
+extern "C" int drna_cofold_subopt_energy_batch(drna_engine* e, int R, int L, int cut, const char* seqs, int32_t* E2, int32_t* E12) {
+  if (!e) return DRNA_ERR_ARG;
+  { const int rc = second_best_check(e, "drna_cofold_subopt_energy_batch", R, L, &cut, seqs && E2); if (rc != DRNA_OK) return rc; }
+  CoSubArgs a = sub_args<CoSubArgs>(e, L);
+  a.cut = cut; a.DuplexInit = e->H.DuplexInit;
+  return second_best_batch(e, R, L, seqs, E2, E12, "unexpected status of the second-best co-fold",
+                           [&] { hipLaunchKernelGGL(cofold_subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a); });
+}
 
 extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const char* seqs, int K, int32_t* E, char* ss) {
   if (!e) return DRNA_ERR_ARG;
-  if (R < 1 || L < 1 || L > e->max_L || K < 1 || K > 8 || !seqs || !E || !ss) {
-    e->err = "drna_subopt_structs_batch: bad argument (L within the engine's limit, 1 <= K <= 8; seqs, E and ss required)";
-    return DRNA_ERR_ARG;
-  }
+  // (no upper limit on R here: the batch goes through the K-best workspace in chunks of kb_chunk)
+  { const int rc = aux_check(e, "drna_subopt_structs_batch", std::min(R, e->max_R), L, nullptr, K >= 1 && K <= 8 && seqs && E && ss,
+                             "1 <= K <= 8; seqs, E and ss required"); if (rc != DRNA_OK) return rc; }
   HIP_TRY(hipSetDevice(e->device));
   const int KT = K <= 4 ? 4 : 8;                      // kernel instantiations
   const int ldmax = e->max_L + 2;
@@ -1255,29 +1353,17 @@ extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const ch
                                  int32_t* Emfe, char* mfe_ss, int32_t* Ed) {
   if (!e) return DRNA_ERR_ARG;
   const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & DRNA_NEED_MFE, want_ev = flags & DRNA_NEED_EVAL;
-  if (R < 1 || R > e->max_R || L < 2 || L > e->max_L || cut < 1 || cut >= L || !seqs || (want_pf && !F4) ||
-      (want_mfe && (!Emfe || !mfe_ss)) || (want_ev && !Ed) || (flags & DRNA_NEED_PK)) {
-    e->err = "drna_cofold_batch: bad argument (1 <= cut < L <= max_L, R <= max_R; output pointers for every requested flag; no NEED_PK)";
-    return DRNA_ERR_ARG;
-  }
-  if (want_ev && (e->n_targets < 1 || e->L_targets != L)) {
-    e->err = "drna_cofold_batch: DRNA_NEED_EVAL needs drna_set_targets() with the same L ('&' removed)";
-    return DRNA_ERR_ARG;
-  }
-  if (R > e->ws_slots) { e->err = "drna_cofold_batch: batch larger than the workspace (raise DRNA_WS_GB or split the batch)"; return DRNA_ERR_ARG; }
+  const char* who = "drna_cofold_batch";
+  int rc = aux_check(e, who, R, L, &cut, seqs && (!want_pf || F4) && (!want_mfe || (Emfe && mfe_ss)) && (!want_ev || Ed) && !(flags & DRNA_NEED_PK),
+                     "output pointers for every requested flag; no NEED_PK");
+  if (rc == DRNA_OK && want_ev) rc = need_targets(e, who, L);
+  if (rc == DRNA_OK) rc = fits_workspace(e, who, R);
+  if (rc != DRNA_OK) return rc;
   HIP_TRY(hipSetDevice(e->device));
   if (!e->d_F4) HIP_TRY(hipMalloc((void**)&e->d_F4, (size_t)4 * e->max_R * sizeof(double)));
   HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
-  const int ld = L + 2;
-  for (int k = 0; k < 2 * e->max_R; k++) e->h_status[k] = ST_OK;
-  CoArgs a;
-  a.T = e->d_mfeT; a.F = e->d_pfT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.hp_w = e->d_hp_w;
-  a.scale = e->d_scale; a.eMLb = e->d_eMLb; a.seqs = e->d_seqs; a.L = L; a.cut = cut; a.ld = ld;
-  a.DuplexInit = e->H.DuplexInit;
-  a.eDuplexInit = std::exp(-(double)e->H.DuplexInit * 10.0 / e->H.pf.kT);
-  a.wsm = e->d_ws_mfe; a.wsm_stride = (long long)mfe_ws_stride(ld);
-  a.wsp = e->d_ws_pf; a.wsp_stride = (long long)pf_ws_stride(ld);
-  a.Emfe = e->d_Emfe; a.ss = e->d_ss; a.F4 = e->d_F4; a.status = e->d_status; a.status_pf = e->d_status + e->max_R;
+  reset_status(e);
+  const CoArgs a = co_args(e, e->d_seqs, L, cut, L + 2);
   HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
   HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
   if (want_pf) hipLaunchKernelGGL(cofold_pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a);
@@ -1297,7 +1383,8 @@ extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const ch
   HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
   HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
   e->timing[2] = 0.f; e->timing[3] = e->timing[0] > e->timing[1] ? e->timing[0] : e->timing[1];
-  { const int rc = fold_status(e, R, want_mfe, want_pf, nullptr, 0, "traceback could not reproduce a table value"); if (rc != DRNA_OK) return rc; }
+  rc = fold_status(e, R, want_mfe, want_pf, nullptr, 0, "traceback could not reproduce a table value");
+  if (rc != DRNA_OK) return rc;
   if (want_pf) HIP_TRY(hipMemcpy(F4, e->d_F4, (size_t)4 * R * sizeof(double), hipMemcpyDeviceToHost));
   if (want_mfe) {
     HIP_TRY(hipMemcpy(Emfe, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1305,115 +1392,6 @@ extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const ch
   }
   if (want_ev) HIP_TRY(hipMemcpy(Ed, e->d_Ed, (size_t)R * e->n_targets * sizeof(int32_t), hipMemcpyDeviceToHost));
   return DRNA_OK;
-}
-
-// ---------------------------------------------------------------- second-best co-fold energy (two strands, -nd on)
-
-extern "C" int drna_cofold_subopt_energy_batch(drna_engine* e, int R, int L, int cut, const char* seqs, int32_t* E2, int32_t* E12) {
-  if (!e) return DRNA_ERR_ARG;
-  if (R < 1 || R > e->max_R || L < 2 || L > e->max_L || cut < 1 || cut >= L || !seqs || !E2) {
-    e->err = "drna_cofold_subopt_energy_batch: bad argument (R, L within the engine's limits, 1 <= cut < L; seqs and E2 required)";
-    return DRNA_ERR_ARG;
-  }
-  if (R > e->ws_slots) { e->err = "drna_cofold_subopt_energy_batch: batch larger than the workspace (raise DRNA_WS_GB or split the batch)"; return DRNA_ERR_ARG; }
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
-  const int ld = L + 2;
-  for (int k = 0; k < e->max_R; k++) e->h_status[k] = ST_OK;
-  CoSubArgs a;
-  a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = e->d_seqs; a.L = L; a.cut = cut; a.ld = ld;
-  a.DuplexInit = e->H.DuplexInit;
-  a.ws = reinterpret_cast<int32_t*>(e->d_ws_pf); a.ws_stride = 2 * (long long)pf_ws_stride(ld);   // int32 units of the PF workspace
-  a.E2 = e->d_Emfe; a.E12 = reinterpret_cast<int32_t*>(e->d_Epf); a.status = e->d_status;
-  HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-  hipLaunchKernelGGL(cofold_subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
-  HIP_TRY(hipStreamSynchronize(e->s_mfe));
-  HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
-  e->timing[1] = e->timing[2] = 0.f; e->timing[3] = e->timing[0];
-  { const int rc = fold_status(e, R, true, false, nullptr, 0, "unexpected status of the second-best co-fold"); if (rc != DRNA_OK) return rc; }
-  HIP_TRY(hipMemcpy(E2, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (E12) HIP_TRY(hipMemcpy(E12, e->d_Epf, (size_t)2 * R * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return DRNA_OK;
-}
-
-// ---------------------------------------------------------------- two strands: pair probabilities and ensemble defect (-sf Edef)
-
-// one batch that fits the workspaces (cofold_pf_kernel, then the outside recursion on its tables); pairs r_base, r_base + 1, ...
-static int cofold_edef_impl(drna_engine* e, int R, int L, int cut, const char* d_seqs, double* d_edef, double* d_bpp, int r_base) {
-  const int ld = L + 2;
-  for (int k = 0; k < R; k++) e->h_status[e->max_R + k] = ST_OK;
-  CoArgs a;
-  a.F = e->d_pfT; a.plan = e->d_plan; a.hp_w = e->d_hp_w; a.scale = e->d_scale; a.eMLb = e->d_eMLb;
-  a.seqs = d_seqs; a.L = L; a.cut = cut; a.ld = ld;
-  a.eDuplexInit = std::exp(-(double)e->H.DuplexInit * 10.0 / e->H.pf.kT);
-  a.wsp = e->d_ws_pf; a.wsp_stride = (long long)pf_ws_stride(ld);
-  a.F4 = e->d_F4; a.status_pf = e->d_status + e->max_R;
-  CoOutArgs o;
-  o.F = e->d_pfT; o.plan = e->d_plan; o.scale = e->d_scale; o.eMLb = e->d_eMLb;
-  o.seqs = d_seqs; o.L = L; o.cut = cut; o.ld = ld; o.eDuplexInit = a.eDuplexInit;
-  o.wsp = e->d_ws_pf; o.wsp_stride = a.wsp_stride;         // the four outside tables fill the slot behind QB, QM, QM1, INFO
-  o.wu = e->d_ws_out; o.wu_stride = outside_ws_stride(ld);
-  o.pt = e->d_pt; o.edef = d_edef; o.bpp = d_bpp; o.status_pf = a.status_pf;
-  HIP_TRY(hipEventRecord(e->ev_o0, e->s_pf));
-  hipLaunchKernelGGL(cofold_pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->ev_o1, e->s_pf));
-  hipLaunchKernelGGL(cofold_outside_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, o);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->ev_o2, e->s_pf));
-  HIP_TRY(hipStreamSynchronize(e->s_pf));
-  HIP_TRY(hipEventElapsedTime(&e->timing_edef[0], e->ev_o0, e->ev_o1));
-  HIP_TRY(hipEventElapsedTime(&e->timing_edef[1], e->ev_o1, e->ev_o2));
-  return fold_status(e, R, false, true, nullptr, r_base, "unexpected status of the co-fold partition function");
-}
-
-extern "C" int drna_cofold_ensemble_defect_batch(drna_engine* e, int R, int L, int cut, const char* seqs, double* edef, double* bpp) {
-  if (!e) return DRNA_ERR_ARG;
-  if (R < 1 || R > e->max_R || L < 2 || L > e->max_L || cut < 1 || cut >= L || !seqs || !edef) {
-    e->err = "drna_cofold_ensemble_defect_batch: bad argument (R, L within the engine's limits, 1 <= cut < L; seqs and edef required)";
-    return DRNA_ERR_ARG;
-  }
-  if (e->n_targets < 1 || e->L_targets != L) {
-    e->err = "drna_cofold_ensemble_defect_batch: needs drna_set_targets() with the same L ('&' removed; targets[0] is the reference structure)";
-    return DRNA_ERR_ARG;
-  }
-  static_assert(sizeof(double) == 8, "workspace strides are counted in doubles");
-  if (cofold_outside_ws_stride(L + 2) > (long long)pf_ws_stride(L + 2) || 4ll * (L + 2) * (L + 2) > outside_ws_stride(L + 2)) {
-    e->err = "drna_cofold_ensemble_defect_batch: workspace slot too small for the outside tables";
-    return DRNA_ERR_INTERNAL;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  { const int rc = outside_workspace(e); if (rc != DRNA_OK) return rc; }
-  if (!e->d_edef) HIP_TRY(hipMalloc((void**)&e->d_edef, (size_t)e->max_R * sizeof(double)));
-  if (!e->d_F4) HIP_TRY(hipMalloc((void**)&e->d_F4, (size_t)4 * e->max_R * sizeof(double)));
-  HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
-  double* d_bpp = nullptr;
-  const size_t nb = (size_t)R * (L + 1) * (L + 1) * sizeof(double);
-  if (bpp) {
-    HIP_TRY(hipMalloc((void**)&d_bpp, nb));
-    hipError_t z = hipMemset(d_bpp, 0, nb);
-    if (z == hipSuccess) z = hipDeviceSynchronize();     // the memset runs on the null stream, the kernels on a non-blocking stream
-    if (z != hipSuccess) { (void)hipFree(d_bpp); e->err = "hipMemset(bpp)"; return DRNA_ERR_DEVICE; }
-  }
-  // more pairs than the workspaces hold (DRNA_WS_GB): one sub-batch of ws_slots after the other; last_edef_timing = their sums
-  int rc = DRNA_OK;
-  float sum[2] = {0, 0};
-  for (int r0 = 0; r0 < R && rc == DRNA_OK; r0 += e->ws_slots) {
-    const int m = std::min(e->ws_slots, R - r0);
-    rc = cofold_edef_impl(e, m, L, cut, e->d_seqs + (size_t)r0 * L, e->d_edef + r0,
-                          d_bpp ? d_bpp + (size_t)r0 * (L + 1) * (L + 1) : nullptr, r0);
-    sum[0] += e->timing_edef[0]; sum[1] += e->timing_edef[1];
-  }
-  e->timing_edef[0] = sum[0]; e->timing_edef[1] = sum[1];
-  if (rc == DRNA_OK) {
-    hipError_t c1 = hipMemcpy(edef, e->d_edef, (size_t)R * sizeof(double), hipMemcpyDeviceToHost);
-    hipError_t c2 = bpp ? hipMemcpy(bpp, d_bpp, nb, hipMemcpyDeviceToHost) : hipSuccess;
-    if (c1 != hipSuccess || c2 != hipSuccess) { e->err = "hipMemcpy(edef/bpp)"; rc = DRNA_ERR_DEVICE; }
-  }
-  if (d_bpp) (void)hipFree(d_bpp);
-  return rc;
 }
 
 // ---------------------------------------------------------------- host-side batched MC helpers (no device work)

@@ -186,6 +186,40 @@ class ReplicaScorer:
         # reference :93-94: get_ensemble_defect(input_file.sec_struct) whenever 'Edef' is among the -sf terms
         self.want_edef = any(function == 'Edef' for function, _ in sim_options.scoring_f)
 
+    def _candidate(self, seq, k, out, Epf, metrics, edef):
+        """ScoreSeq of candidate k of a scored batch, up to the -sf terms (reference score_sequence(), :70-96); Epf is the
+        batch's column of ensemble free energies"""
+        sc = ScoreSeq(sequence=seq)
+        sc.get_Epf(float(Epf[k]))
+        sc.get_mfe_ss(out["mfe_ss"][k])
+        sc.get_edesired(int(out["Ed"][k, 0]) / 100.0)
+        sc.get_edesired_minus_Epf(sc.Epf, sc.edesired)
+        mcc, recall, precision = metrics[k]
+        sc.get_precision(precision)
+        sc.get_recall(recall)
+        sc.get_mcc(mcc)
+        for function, _ in self.sim_options.scoring_f:
+            if function == 'sln_Epf':
+                sc.get_sln_Epf()
+            if function == 'Ed-MFE':
+                sc.get_MFE(int(out["Emfe"][k]) / 100.0)
+                sc.get_edesired_minus_MFE()
+            if function == 'Edef':
+                sc.get_ensemble_defect(float(edef[k]))
+        sc.get_scoring_function(self.sim_options.scoring_f)
+        return sc
+
+    def _negative_design(self, seqs, res, second_best):
+        """reference :105-108 (-nd on): for solved candidates (1-MCC == 0) the energy of the first sub-optimal structure, which
+        second_best (Engine.subopt_energy, or Engine.cofold_subopt_energy for two strands) returns for a list of sequences"""
+        hit = [k for k, sc in enumerate(res) if sc.mcc == 0]
+        if hit:
+            e2 = second_best([seqs[k] for k in hit])
+            for k, v in zip(hit, e2):
+                res[k].get_subopt_e(int(v) / 100.0)
+                res[k].get_esubopt_minus_Epf(res[k].Epf, res[k].subopt_e)
+                res[k].get_scoring_function_w_subopt()
+
     def score(self, seqs):
         """list of sequences -> list of ScoreSeq (reference score_sequence(), once per replica)."""
         if self.oligo_state in ("heterodimer", "homodimer"):
@@ -196,24 +230,7 @@ class ReplicaScorer:
         edef = self.engine.ensemble_defect(list(seqs)) if self.want_edef else None
         res = []
         for k, seq in enumerate(seqs):
-            sc = ScoreSeq(sequence=seq)
-            sc.get_Epf(float(out["Epf"][k]))
-            sc.get_mfe_ss(out["mfe_ss"][k])
-            sc.get_edesired(int(out["Ed"][k, 0]) / 100.0)
-            sc.get_edesired_minus_Epf(sc.Epf, sc.edesired)
-            mcc, recall, precision = metrics[k]
-            sc.get_precision(precision)
-            sc.get_recall(recall)
-            sc.get_mcc(mcc)
-            for function, _ in self.sim_options.scoring_f:
-                if function == 'sln_Epf':
-                    sc.get_sln_Epf()
-                if function == 'Ed-MFE':
-                    sc.get_MFE(int(out["Emfe"][k]) / 100.0)
-                    sc.get_edesired_minus_MFE()
-                if function == 'Edef':
-                    sc.get_ensemble_defect(float(edef[k]))
-            sc.get_scoring_function(self.sim_options.scoring_f)
+            sc = self._candidate(seq, k, out, out["Epf"], metrics, edef)
             if getattr(self.input_file, "alt_sec_struct", None) is not None:
                 energies = [int(e) / 100.0 for e in out["Ed"][k, 1:]]
                 sc.get_edesired2(sum(energies) / len(energies))
@@ -221,14 +238,7 @@ class ReplicaScorer:
                 sc.get_scoring_function_w_alt_ss()
             res.append(sc)
         if self.subopt:
-            # reference :105-108 (-nd on): for solved candidates (1-MCC == 0) the energy of the first sub-optimal structure
-            hit = [k for k, sc in enumerate(res) if sc.mcc == 0]
-            if hit:
-                e2 = self.engine.subopt_energy([seqs[k] for k in hit])
-                for k, v in zip(hit, e2):
-                    res[k].get_subopt_e(int(v) / 100.0)
-                    res[k].get_esubopt_minus_Epf(res[k].Epf, res[k].subopt_e)
-                    res[k].get_scoring_function_w_subopt()
+            self._negative_design(seqs, res, self.engine.subopt_energy)
         if self.oligo_state == "avoid":
             # reference get_scoring_function_monomer (:411-418): homodimer of the sequence with itself, monomer fraction bonus
             # (applied before the motif bonus in the reference; both are additive)
@@ -255,40 +265,15 @@ class ReplicaScorer:
         edef = self.engine.cofold_ensemble_defect(seqs) if self.want_edef else None
         res = []
         for k, seq in enumerate(seqs):
-            sc = ScoreSeq(sequence=seq)
-            sc.get_Epf(float(out["FAB"][k]))
-            sc.get_mfe_ss(out["mfe_ss"][k])
-            sc.get_edesired(int(out["Ed"][k, 0]) / 100.0)
-            sc.get_edesired_minus_Epf(sc.Epf, sc.edesired)
-            mcc, recall, precision = metrics[k]
-            sc.get_precision(precision)
-            sc.get_recall(recall)
-            sc.get_mcc(mcc)
-            for function, _ in self.sim_options.scoring_f:
-                if function == 'sln_Epf':
-                    sc.get_sln_Epf()
-                if function == 'Ed-MFE':
-                    sc.get_MFE(int(out["Emfe"][k]) / 100.0)
-                    sc.get_edesired_minus_MFE()
-                if function == 'Edef':
-                    sc.get_ensemble_defect(float(edef[k]))
-            sc.get_scoring_function(self.sim_options.scoring_f)
+            sc = self._candidate(seq, k, out, out["FAB"], metrics, edef)
             sc.oligo_fraction = float(oligo_fraction(out["FA"][k], out["FB"][k], out["FcAB"][k]))
             if self.oligo_state == "heterodimer" or ss1 != ss2:
                 sc.oligomer_bonus = float(kTlog_oligo_fraction(sc.oligo_fraction))
             else:
                 sc.oligomer_bonus = float(kTlog_monomer_fraction(sc.oligo_fraction))
             res.append(sc)
-        if self.subopt:
-            # reference :105-108 (-nd on) on the dimer fold compound: for solved candidates (1-MCC == 0) the energy of the
-            # first sub-optimal co-fold structure, before the oligomer / monomer bonus
-            hit = [k for k, sc in enumerate(res) if sc.mcc == 0]
-            if hit:
-                e2 = self.engine.cofold_subopt_energy([seqs[k] for k in hit])
-                for k, v in zip(hit, e2):
-                    res[k].get_subopt_e(int(v) / 100.0)
-                    res[k].get_esubopt_minus_Epf(res[k].Epf, res[k].subopt_e)
-                    res[k].get_scoring_function_w_subopt()
+        if self.subopt:                   # on the dimer fold compound, before the oligomer / monomer bonus
+            self._negative_design(seqs, res, self.engine.cofold_subopt_energy)
         for seq, sc in zip(seqs, res):
             sc.scoring_function = sc.scoring_function + sc.oligomer_bonus
             if getattr(self.sim_options, "motifs", None):

@@ -21,12 +21,43 @@ NEED_PF, NEED_MFE, NEED_PK, NEED_EVAL = 1, 2, 4, 8
 _ERRORS = {-1: "bad argument", -2: "bad parameter blob", -3: "HIP/device error", -4: "bad sequence character",
            -5: "unbalanced structure", -6: "partition function out of fp64 range", -7: "internal (traceback)"}
 
-EXPORTS = ("drna_create", "drna_destroy", "drna_last_error", "drna_set_targets", "drna_score_batch",
-           "drna_score_batch_device", "drna_last_timing", "drna_info", "drna_simscore_batch", "drna_propose_batch",
-           "drna_metropolis_batch", "drna_ensemble_defect_batch", "drna_ensemble_defect_batch_device",
-           "drna_last_edef_timing", "drna_propose_batch_alt", "drna_set_targets_ragged", "drna_score_ragged", "drna_cofold_batch", "drna_mc_run", "drna_subopt_energy_batch",
-           "drna_cofold_subopt_energy_batch", "drna_cofold_ensemble_defect_batch",
-           "drna_subopt_structs_batch", "drna_rng_seed", "drna_rng_random", "drna_set_option", "drna_timing_sums", "drna_debug_strip_clocks", "drna_get_option", "drna_abi_version")
+_vp, _ci, _u32, _dbl, _str = C.c_void_p, C.c_int, C.c_uint32, C.c_double, C.c_char_p
+# every export of include/desirna_amd.h: name -> (restype, argtypes)
+_SIGNATURES = {
+    "drna_abi_version": (_ci, []),
+    "drna_create": (_ci, [_vp, _ci, _ci, _ci, _ci, C.POINTER(_vp)]),
+    "drna_destroy": (None, [_vp]),
+    "drna_last_error": (_str, [_vp]),
+    "drna_set_targets": (_ci, [_vp, _ci, _ci, _str]),
+    "drna_score_batch": (_ci, [_vp, _ci, _ci, _str, _u32, _vp, _vp, _vp, _vp]),
+    "drna_score_batch_device": (_ci, [_vp, _ci, _ci, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "drna_last_timing": (_ci, [_vp, _vp]),
+    "drna_info": (_ci, [_vp, _vp]),
+    "drna_timing_sums": (_ci, [_vp, _vp, _ci]),
+    "drna_set_option": (_ci, [_vp, _str, _ci]),
+    "drna_get_option": (_ci, [_vp, _str, _vp]),
+    "drna_debug_strip_clocks": (_ci, [_vp, _vp, _ci]),
+    "drna_ensemble_defect_batch": (_ci, [_vp, _ci, _ci, _str, _vp, _vp]),
+    "drna_ensemble_defect_batch_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp]),
+    "drna_last_edef_timing": (_ci, [_vp, _vp]),
+    "drna_set_targets_ragged": (_ci, [_vp, _ci, _vp, _str]),
+    "drna_score_ragged": (_ci, [_vp, _ci, _vp, _str, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "drna_cofold_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _u32, _vp, _vp, _vp, _vp]),
+    "drna_mc_run": (_ci, [_vp, _ci, _ci, _ci, _str, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci, _vp,
+                          _dbl, _ci, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drna_subopt_energy_batch": (_ci, [_vp, _ci, _ci, _str, _vp, _vp]),
+    "drna_cofold_subopt_energy_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _vp, _vp]),
+    "drna_cofold_ensemble_defect_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _vp, _vp]),
+    "drna_subopt_structs_batch": (_ci, [_vp, _ci, _ci, _str, _ci, _vp, _vp]),
+    "drna_simscore_batch": (_ci, [_ci, _ci, _str, _vp, _vp, _vp, _vp]),
+    "drna_propose_batch": (_ci, [_ci, _ci, _str, _vp, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci, _vp, _vp]),
+    "drna_propose_batch_alt": (_ci, [_ci, _ci, _str, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci,
+                                     _vp, _vp]),
+    "drna_metropolis_batch": (_ci, [_ci, _vp, _vp, _vp, _dbl, _vp, _vp, _vp]),
+    "drna_rng_seed": (_ci, [_ci, _vp, _vp]),
+    "drna_rng_random": (_ci, [_ci, _vp, _vp]),
+}
+EXPORTS = tuple(_SIGNATURES)
 
 ABI_VERSION = 3        # DRNA_ABI_VERSION this binding was written against (include/desirna_amd.h)
 
@@ -47,70 +78,33 @@ def load_library(path=None):
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C desirna_amd/csrc`); there is no CPU fallback" % path)
     L = C.CDLL(path)
-    vp, ci, u32 = C.c_void_p, C.c_int, C.c_uint32
-    L.drna_create.restype = ci
-    L.drna_create.argtypes = [vp, ci, ci, ci, ci, C.POINTER(vp)]
-    L.drna_destroy.restype = None
-    L.drna_destroy.argtypes = [vp]
-    L.drna_last_error.restype = C.c_char_p
-    L.drna_last_error.argtypes = [vp]
-    L.drna_set_targets.restype = ci
-    L.drna_set_targets.argtypes = [vp, ci, ci, C.c_char_p]
-    L.drna_score_batch.restype = ci
-    L.drna_score_batch.argtypes = [vp, ci, ci, C.c_char_p, u32, vp, vp, vp, vp]
-    L.drna_score_batch_device.restype = ci
-    L.drna_score_batch_device.argtypes = [vp, ci, ci, vp, u32, vp, vp, vp, vp]
-    L.drna_abi_version.restype = ci
-    L.drna_abi_version.argtypes = []
-    if L.drna_abi_version() != ABI_VERSION:
-        raise EngineError(-1, "library ABI version %d, this binding expects %d: rebuild desirna_amd/csrc" % (L.drna_abi_version(), ABI_VERSION))
-    L.drna_last_timing.restype = ci
-    L.drna_last_timing.argtypes = [vp, vp]
-    L.drna_info.restype = ci
-    L.drna_info.argtypes = [vp, vp]
-    L.drna_timing_sums.restype = ci
-    L.drna_timing_sums.argtypes = [vp, vp, ci]
-    L.drna_set_option.restype = ci
-    L.drna_set_option.argtypes = [vp, C.c_char_p, ci]
-    L.drna_get_option.restype = ci
-    L.drna_get_option.argtypes = [vp, C.c_char_p, vp]
-    L.drna_ensemble_defect_batch.restype = ci
-    L.drna_ensemble_defect_batch.argtypes = [vp, ci, ci, C.c_char_p, vp, vp]
-    L.drna_ensemble_defect_batch_device.restype = ci
-    L.drna_ensemble_defect_batch_device.argtypes = [vp, ci, ci, vp, vp, vp]
-    L.drna_last_edef_timing.restype = ci
-    L.drna_last_edef_timing.argtypes = [vp, vp]
-    L.drna_set_targets_ragged.restype = ci
-    L.drna_set_targets_ragged.argtypes = [vp, ci, vp, C.c_char_p]
-    L.drna_score_ragged.restype = ci
-    L.drna_score_ragged.argtypes = [vp, ci, vp, C.c_char_p, vp, u32, vp, vp, vp, vp]
-    L.drna_cofold_batch.restype = ci
-    L.drna_cofold_batch.argtypes = [vp, ci, ci, ci, C.c_char_p, u32, vp, vp, vp, vp]
-    L.drna_mc_run.restype = ci
-    L.drna_mc_run.argtypes = [vp, ci, ci, ci, C.c_char_p, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, C.c_double, C.c_double, ci, vp,
-                              C.c_double, ci, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.drna_subopt_energy_batch.restype = ci
-    L.drna_subopt_energy_batch.argtypes = [vp, ci, ci, C.c_char_p, vp, vp]
-    L.drna_cofold_subopt_energy_batch.restype = ci
-    L.drna_cofold_subopt_energy_batch.argtypes = [vp, ci, ci, ci, C.c_char_p, vp, vp]
-    L.drna_cofold_ensemble_defect_batch.restype = ci
-    L.drna_cofold_ensemble_defect_batch.argtypes = [vp, ci, ci, ci, C.c_char_p, vp, vp]
-    L.drna_subopt_structs_batch.restype = ci
-    L.drna_subopt_structs_batch.argtypes = [vp, ci, ci, C.c_char_p, ci, vp, vp]
-    L.drna_simscore_batch.restype = ci
-    L.drna_simscore_batch.argtypes = [ci, ci, C.c_char_p, vp, vp, vp, vp]
-    L.drna_propose_batch.restype = ci
-    L.drna_propose_batch.argtypes = [ci, ci, C.c_char_p, vp, vp, vp, vp, ci, C.c_double, C.c_double, ci, vp, vp]
-    L.drna_propose_batch_alt.restype = ci
-    L.drna_propose_batch_alt.argtypes = [ci, ci, C.c_char_p, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, C.c_double,
-                                         C.c_double, ci, vp, vp]
-    L.drna_metropolis_batch.restype = ci
-    L.drna_metropolis_batch.argtypes = [ci, vp, vp, vp, C.c_double, vp, vp, vp]
-    L.drna_rng_seed.restype = ci
-    L.drna_rng_seed.argtypes = [ci, vp, vp]
-    L.drna_rng_random.restype = ci
-    L.drna_rng_random.argtypes = [ci, vp, vp]
+    for name, (restype, argtypes) in _SIGNATURES.items():         # drna_abi_version first: nothing else is called before the check
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+        if name == "drna_abi_version" and fn() != ABI_VERSION:
+            raise EngineError(-1, "library ABI version %d, this binding expects %d: rebuild desirna_amd/csrc" % (fn(), ABI_VERSION))
     return L
+
+
+def _equal_length(seqs):
+    """(R, L) of a batch of equal-length sequences"""
+    R, L = len(seqs), len(seqs[0])
+    if any(len(s) != L for s in seqs):
+        raise ValueError("all sequences of a batch must have the same length")
+    return R, L
+
+
+def _split_pairs(seqs):
+    """'AAAA&BBBB' strings of the same strand lengths -> (both strands of every pair in one bytes object, R, L, cut)"""
+    a0, b0 = seqs[0].split("&")
+    cut, L = len(a0), len(a0) + len(b0)
+    flat = []
+    for s in seqs:
+        a, b = s.split("&")
+        if len(a) != cut or len(a) + len(b) != L:
+            raise ValueError("all pairs of a batch must have the same strand lengths")
+        flat.append(a + b)
+    return "".join(flat).encode("ascii"), len(flat), L, cut
 
 
 _LIVE = None          # weak set of open engines, _CLOSED_FALLBACKS: the counters of the closed ones (sync_fallbacks_total)
@@ -185,10 +179,7 @@ class Engine:
     def score_batch(self, seqs, flags=NEED_PF | NEED_MFE | NEED_EVAL):
         """seqs: list of equal-length strings.  Returns dict(Epf, Emfe, mfe_ss, Ed) (None if not requested);
         energies in ViennaRNA's units: Epf kcal/mol (float), Emfe / Ed int dcal/mol."""
-        R = len(seqs)
-        L = len(seqs[0])
-        if any(len(s) != L for s in seqs):
-            raise ValueError("all sequences of a batch must have the same length")
+        R, L = _equal_length(seqs)
         sb = "".join(seqs).encode("ascii")
         Epf = np.zeros(R, dtype=np.float64) if flags & NEED_PF else None
         want_mfe = flags & (NEED_MFE | NEED_PK)
@@ -251,15 +242,7 @@ class Engine:
     def cofold_batch(self, seqs, flags=NEED_PF | NEED_MFE | NEED_EVAL):
         """Two-strand scoring: seqs are 'AAAA&BBBB' strings with the same strand lengths.  Returns dict(FA, FB, FcAB, FAB
         (kcal/mol; the reference's Epf is FAB), Emfe (dcal/mol), mfe_ss (with the '&' re-inserted), Ed (vs. set_targets))."""
-        a0, b0 = seqs[0].split("&")
-        cut, L = len(a0), len(a0) + len(b0)
-        flat = []
-        for s in seqs:
-            a, b = s.split("&")
-            if len(a) != cut or len(a) + len(b) != L:
-                raise ValueError("all pairs of a batch must have the same strand lengths")
-            flat.append(a + b)
-        R = len(flat)
+        flat, R, L, cut = _split_pairs(seqs)
         if not (flags & NEED_EVAL and self.n_targets):
             flags &= ~NEED_EVAL
         F4 = np.zeros((R, 4), dtype=np.float64) if flags & NEED_PF else None
@@ -267,7 +250,7 @@ class Engine:
         ss = np.zeros((R, L), dtype=np.uint8) if flags & NEED_MFE else None
         Ed = np.zeros((R, max(1, self.n_targets)), dtype=np.int32) if flags & NEED_EVAL else None
         ptr = lambda a: a.ctypes.data if a is not None else None
-        self._check(self._L.drna_cofold_batch(self._h, R, L, cut, "".join(flat).encode("ascii"), flags, ptr(F4), ptr(Emfe),
+        self._check(self._L.drna_cofold_batch(self._h, R, L, cut, flat, flags, ptr(F4), ptr(Emfe),
                                               ptr(ss), ptr(Ed)))
         out = {"Emfe": Emfe, "Ed": Ed, "mfe_ss": None, "FA": None, "FB": None, "FcAB": None, "FAB": None}
         if ss is not None:
@@ -303,9 +286,7 @@ class Engine:
     def subopt_energy(self, seqs, want_both=False):
         """Energy (dcal/mol) of the second-best structure of each sequence as the reference's -nd on path takes it from
         ViennaRNA's subopt (0 if none within 49 kcal/mol); with want_both also the (R, 2) array of the two lowest energies."""
-        R, L = len(seqs), len(seqs[0])
-        if any(len(s) != L for s in seqs):
-            raise ValueError("all sequences of a batch must have the same length")
+        R, L = _equal_length(seqs)
         E2 = np.zeros(R, dtype=np.int32)
         E12 = np.zeros((R, 2), dtype=np.int32) if want_both else None
         self._check(self._L.drna_subopt_energy_batch(self._h, R, L, "".join(seqs).encode("ascii"), E2.ctypes.data,
@@ -316,18 +297,10 @@ class Engine:
         """Two strands: energy (dcal/mol) of the second-best co-fold structure of each 'AAAA&BBBB' pair as the reference's -nd on
         path takes it from ViennaRNA's subopt on the dimer fold compound (0 if none within 49 kcal/mol); with want_both also
         the (R, 2) array of the two lowest energies (second = 10000000 if there is one structure only)."""
-        a0, b0 = seqs[0].split("&")
-        cut, L = len(a0), len(a0) + len(b0)
-        flat = []
-        for s in seqs:
-            a, b = s.split("&")
-            if len(a) != cut or len(a) + len(b) != L:
-                raise ValueError("all pairs of a batch must have the same strand lengths")
-            flat.append(a + b)
-        R = len(flat)
+        flat, R, L, cut = _split_pairs(seqs)
         E2 = np.zeros(R, dtype=np.int32)
         E12 = np.zeros((R, 2), dtype=np.int32) if want_both else None
-        self._check(self._L.drna_cofold_subopt_energy_batch(self._h, R, L, cut, "".join(flat).encode("ascii"), E2.ctypes.data,
+        self._check(self._L.drna_cofold_subopt_energy_batch(self._h, R, L, cut, flat, E2.ctypes.data,
                                                             E12.ctypes.data if want_both else None))
         return (E2, E12) if want_both else E2
 
@@ -336,9 +309,7 @@ class Engine:
         a sequence has fewer structures) and a list of R lists of K dot-bracket strings.  Rank k is entry k of ViennaRNA's
         energy-sorted subopt list as get_first_suboptimal_structure_and_energy(seq, fc, k) indexes it (reference
         utils/energy_scores.py:453-488); the order among structures of equal energy is the engine's own."""
-        R, L = len(seqs), len(seqs[0])
-        if any(len(s) != L for s in seqs):
-            raise ValueError("all sequences of a batch must have the same length")
+        R, L = _equal_length(seqs)
         E = np.zeros((R, K), dtype=np.int32)
         ss = np.zeros((R, K, L), dtype=np.uint8)
         self._check(self._L.drna_subopt_structs_batch(self._h, R, L, "".join(seqs).encode("ascii"), int(K), E.ctypes.data,
@@ -350,10 +321,7 @@ class Engine:
         """Ensemble defect of each sequence against targets[0] (reference ScoreSeq.get_ensemble_defect,
         utils/energy_scores.py:362-374).  Returns float64[R]; with want_bpp also the (R, L+1, L+1) base-pair
         probability matrices (1-based, upper triangle)."""
-        R = len(seqs)
-        L = len(seqs[0])
-        if any(len(s) != L for s in seqs):
-            raise ValueError("all sequences of a batch must have the same length")
+        R, L = _equal_length(seqs)
         ed = np.zeros(R, dtype=np.float64)
         bpp = np.zeros((R, L + 1, L + 1), dtype=np.float64) if want_bpp else None
         self._check(self._L.drna_ensemble_defect_batch(self._h, R, L, "".join(seqs).encode("ascii"), ed.ctypes.data,
@@ -365,18 +333,10 @@ class Engine:
         :meth:`cofold_batch`'s partition function (connected structures weighted by expDuplexInit, halved for two equal
         strands).  Returns float64[R]; with want_bpp also the (R, L+1, L+1) pair probabilities over the concatenation
         (1-based, upper triangle)."""
-        a0, b0 = seqs[0].split("&")
-        cut, L = len(a0), len(a0) + len(b0)
-        flat = []
-        for s in seqs:
-            a, b = s.split("&")
-            if len(a) != cut or len(a) + len(b) != L:
-                raise ValueError("all pairs of a batch must have the same strand lengths")
-            flat.append(a + b)
-        R = len(flat)
+        flat, R, L, cut = _split_pairs(seqs)
         ed = np.zeros(R, dtype=np.float64)
         bpp = np.zeros((R, L + 1, L + 1), dtype=np.float64) if want_bpp else None
-        self._check(self._L.drna_cofold_ensemble_defect_batch(self._h, R, L, cut, "".join(flat).encode("ascii"), ed.ctypes.data,
+        self._check(self._L.drna_cofold_ensemble_defect_batch(self._h, R, L, cut, flat, ed.ctypes.data,
                                                               bpp.ctypes.data if want_bpp else None))
         return (ed, bpp) if want_bpp else ed
 

@@ -1,5 +1,6 @@
 // emu_kernels.cpp -- TEST-ONLY: compiles the unmodified kernel headers against hip_emu.h and exposes
-// them through a tiny C interface for tests/test_kernels_emulated.py (CPU, no GPU needed).
+// them through a tiny C interface for tests/test_kernels_emulated.py and tests/test_cofold_{subopt,edef}_emulated.py (CPU, no
+// GPU needed).
 #include "hip_emu.h"
 
 thread_local emu_dim3 threadIdx;
@@ -17,6 +18,8 @@ thread_local emu_group* emu_g = nullptr;
 #include "../../desirna_amd/csrc/fold_outside.hpp"
 #include "../../desirna_amd/csrc/fold_cofold.hpp"
 #include "../../desirna_amd/csrc/fold_subopt.hpp"
+#include "../../desirna_amd/csrc/fold_cofold_subopt.hpp"
+#include "../../desirna_amd/csrc/fold_cofold_outside.hpp"
 
 using namespace drna;
 
@@ -379,5 +382,62 @@ int emu_kbest(const int32_t* blob, int n_int32, int R, int L, const char* seqs, 
   delete c;
   return 0;
 }
+
+// two-best co-fold energies (second-best structure) of R pairs of total length L, the first strand `cut` nucleotides long
+int emu_cofold_subopt(const int32_t* blob, int n_int32, int R, int L, int cut, const char* seqs, int nt, int32_t* E2, int32_t* E12,
+                      int32_t* status) {
+  if (nt != 64 && nt != 128) return -2;
+  Ctx* c = make_ctx(blob, n_int32, L);
+  if (!c->ok) { delete c; return -1; }
+  const int ld = L + 2;
+  std::vector<int32_t> ws((size_t)6 * ld * ld, 0);
+  for (int r = 0; r < R; r++) {
+    CoSubArgs a;
+    a.T = &c->H.mfe; a.plan = &c->H.plan; a.hp_len = c->H.hp_len.data(); a.seqs = seqs; a.L = L; a.cut = cut; a.ld = ld;
+    a.DuplexInit = c->H.DuplexInit;
+    a.ws = ws.data() - (size_t)r * 6 * ld * ld; a.ws_stride = (long long)6 * ld * ld;
+    a.E2 = E2; a.E12 = E12; a.status = status;
+    if (nt == 64) emu_launch(r, 64, [&]() { cofold_subopt_kernel<64>(a); });
+    else emu_launch(r, 128, [&]() { cofold_subopt_kernel<128>(a); });
+  }
+  delete c;
+  return 0;
 }
 
+// pair probabilities and ensemble defect of R pairs of total length L, the first strand `cut` nucleotides long, against the
+// pair table pt (L + 2 shorts); bpp (R x (L+1) x (L+1), zeroed by the caller) may be null; F4 = R x 4 free energies
+int emu_cofold_edef(const int32_t* blob, int n_int32, int R, int L, int cut, const char* seqs, const short* pt, int nt, double* edef,
+                    double* bpp, double* F4, int32_t* status) {
+  if (nt != 64 && nt != 128) return -2;
+  Ctx* c = make_ctx(blob, n_int32, L);
+  if (!c->ok) { delete c; return -1; }
+  const HostTables& H = c->H;
+  const int ld = L + 2;
+  const long long stride = cofold_outside_ws_stride(ld), ustride = (long long)4 * ld * ld;
+  std::vector<double> ws((size_t)stride, 0.0), wu((size_t)ustride, 0.0);
+  for (int r = 0; r < R; r++) {
+    CoArgs a;
+    a.F = &H.pf; a.plan = &H.plan; a.hp_w = H.hp_w.data(); a.scale = H.scale.data(); a.eMLb = H.eMLb.data();
+    a.seqs = seqs; a.L = L; a.cut = cut; a.ld = ld;
+    a.eDuplexInit = std::exp(-(double)H.DuplexInit * 10.0 / H.pf.kT);
+    a.wsp = ws.data() - (size_t)r * stride; a.wsp_stride = stride;
+    a.F4 = F4; a.status_pf = status;
+    CoOutArgs o;
+    o.F = &H.pf; o.plan = &H.plan; o.scale = H.scale.data(); o.eMLb = H.eMLb.data();
+    o.seqs = seqs; o.L = L; o.cut = cut; o.ld = ld; o.eDuplexInit = a.eDuplexInit;
+    o.wsp = a.wsp; o.wsp_stride = stride;
+    o.wu = wu.data() - (size_t)r * ustride; o.wu_stride = ustride;
+    o.pt = pt; o.edef = edef; o.bpp = bpp; o.status_pf = status;
+    status[r] = ST_OK;
+    if (nt == 64) {
+      emu_launch(r, 64, [&]() { cofold_pf_kernel<64>(a); });
+      emu_launch(r, 64, [&]() { cofold_outside_kernel<64>(o); });
+    } else {
+      emu_launch(r, 128, [&]() { cofold_pf_kernel<128>(a); });
+      emu_launch(r, 128, [&]() { cofold_outside_kernel<128>(o); });
+    }
+  }
+  delete c;
+  return 0;
+}
+}

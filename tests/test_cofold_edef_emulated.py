@@ -5,7 +5,7 @@ from the oracle's two-strand evaluation) and against identities that follow from
 import numpy as np
 import pytest
 
-from tests.emu.emu_cofold_outside import cofold_edef, cofold_edef_many
+from tests.emu.emu import cofold_edef, cofold_edef_many
 from tests.test_cofold_subopt_emulated import _enumeration_cases, _rand, cofold_structures
 
 KT = 1.98717e-3 * 310.15

@@ -12,7 +12,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from tests.emu.emu_cofold_outside import cofold_edef_many
+from tests.emu.emu import cofold_edef_many
 from tests.test_cofold_edef_emulated import EDEF_TOL, PAIRS, defect_from_matrix
 
 pytestmark = pytest.mark.gpu

@@ -5,7 +5,7 @@ against properties that follow from the structure set (unconnected-only pairs, h
 import numpy as np
 import pytest
 
-from tests.emu.emu_cofold_subopt import INF_REF, cofold_subopt, cofold_subopt_many
+from tests.emu.emu import INF_REF, cofold_subopt, cofold_subopt_many
 
 PAIRS = {("A", "U"), ("U", "A"), ("G", "C"), ("C", "G"), ("G", "U"), ("U", "G")}
 

@@ -11,7 +11,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from tests.emu.emu_cofold_subopt import INF_REF, cofold_subopt_many
+from tests.emu.emu import INF_REF, cofold_subopt_many
 
 pytestmark = pytest.mark.gpu
 
