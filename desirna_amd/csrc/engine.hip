@@ -1247,13 +1247,19 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
 
 // ---------------------------------------------------------------- second-best structure energy (-nd on), one and two strands
 
-// what SubArgs and CoSubArgs share: the tables live in the partition function's workspace, E2 comes back in d_Emfe, E12 in d_Epf
-template <class A>
-static A sub_args(const drna_engine* e, int L) {
-  A a;
-  a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = e->d_seqs; a.L = L; a.ld = L + 2;
-  a.ws = reinterpret_cast<int32_t*>(e->d_ws_pf); a.ws_stride = 2 * (long long)pf_ws_stride(L + 2);   // int32 units of the PF workspace
-  a.E2 = e->d_Emfe; a.E12 = reinterpret_cast<int32_t*>(e->d_Epf); a.status = e->d_status;
+// arguments of the three kernels of fold_subopt.hpp.  K = 2, the second-best folds: the tables live in the partition function's
+// workspace, E2 comes back in d_Emfe, E12 in d_Epf.  K = 4 / 8, the ranked structures: everything in the K-best buffers.
+static SuboptArgs subopt_args(const drna_engine* e, int L, int cut, int K) {
+  SuboptArgs a;
+  a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = e->d_seqs; a.L = L; a.cut = cut; a.ld = L + 2;
+  a.DuplexInit = e->H.DuplexInit; a.status = e->d_status;
+  if (K == 2) {
+    a.ws = reinterpret_cast<int32_t*>(e->d_ws_pf); a.ws_stride = 2 * (long long)pf_ws_stride(L + 2);   // int32 units of the PF workspace
+    a.E2 = e->d_Emfe; a.E12 = reinterpret_cast<int32_t*>(e->d_Epf);
+  } else {
+    a.ws = e->d_ws_kb; a.ws_stride = (long long)3 * K * a.ld * a.ld;
+    a.E = e->d_kbE; a.ss = e->d_kbss;
+  }
   return a;
 }
 // upload, launch() on the MFE stream (timed as "mfe"), status, E2 and (optional) E12 back
@@ -1283,7 +1289,7 @@ static int second_best_check(drna_engine* e, const char* who, int R, int L, cons
 extern "C" int drna_subopt_energy_batch(drna_engine* e, int R, int L, const char* seqs, int32_t* E2, int32_t* E12) {
   if (!e) return DRNA_ERR_ARG;
   { const int rc = second_best_check(e, "drna_subopt_energy_batch", R, L, nullptr, seqs && E2); if (rc != DRNA_OK) return rc; }
-  const SubArgs a = sub_args<SubArgs>(e, L);
+  const SuboptArgs a = subopt_args(e, L, 0, 2);
   return second_best_batch(e, R, L, seqs, E2, E12, "unexpected status of the second-best fold",
                            [&] { hipLaunchKernelGGL(subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a); });
 }
@@ -1291,8 +1297,7 @@ extern "C" int drna_subopt_energy_batch(drna_engine* e, int R, int L, const char
 extern "C" int drna_cofold_subopt_energy_batch(drna_engine* e, int R, int L, int cut, const char* seqs, int32_t* E2, int32_t* E12) {
   if (!e) return DRNA_ERR_ARG;
   { const int rc = second_best_check(e, "drna_cofold_subopt_energy_batch", R, L, &cut, seqs && E2); if (rc != DRNA_OK) return rc; }
-  CoSubArgs a = sub_args<CoSubArgs>(e, L);
-  a.cut = cut; a.DuplexInit = e->H.DuplexInit;
+  const SuboptArgs a = subopt_args(e, L, cut, 2);
   return second_best_batch(e, R, L, seqs, E2, E12, "unexpected status of the second-best co-fold",
                            [&] { hipLaunchKernelGGL(cofold_subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a); });
 }
@@ -1313,7 +1318,6 @@ extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const cha
     HIP_TRY(hipMalloc((void**)&e->d_kbss, (size_t)8 * e->kb_chunk * e->max_L));
     e->ws_bytes += stride_max * sizeof(int32_t) * e->kb_chunk;
   }
-  const int ld = L + 2;
   std::vector<int32_t> hE((size_t)KT * e->kb_chunk);
   std::vector<char> hs((size_t)KT * e->kb_chunk * L);
   float ms_total = 0.f;
@@ -1321,10 +1325,7 @@ extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const cha
     const int rc = R - r0 < e->kb_chunk ? R - r0 : e->kb_chunk;
     HIP_TRY(hipMemcpy(e->d_seqs, seqs + (size_t)r0 * L, (size_t)rc * L, hipMemcpyHostToDevice));
     for (int k = 0; k < rc; k++) e->h_status[k] = ST_OK;
-    KbArgs a;
-    a.T = e->d_mfeT; a.plan = e->d_plan; a.hp_len = e->d_hp_len; a.seqs = e->d_seqs; a.L = L; a.ld = ld;
-    a.ws = e->d_ws_kb; a.ws_stride = (long long)3 * KT * ld * ld;
-    a.E = e->d_kbE; a.ss = e->d_kbss; a.status = e->d_status;
+    const SuboptArgs a = subopt_args(e, L, 0, KT);
     HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
     if (KT == 4) hipLaunchKernelGGL((kbest_kernel<1024, 4>), dim3(rc), dim3(1024), 0, e->s_mfe, a);
     else hipLaunchKernelGGL((kbest_kernel<1024, 8>), dim3(rc), dim3(1024), 0, e->s_mfe, a);

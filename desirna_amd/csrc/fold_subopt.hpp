@@ -1,181 +1,66 @@
-// fold_subopt.hpp -- energy of the second-best secondary structure for one sequence per workgroup on gfx950.
-// Replaces get_first_suboptimal_structure_and_energy(seq, fc, 1)[1] of the reference's negative-design option
-// (-nd on; utils/energy_scores.py:105-107, :453-488): ViennaRNA's subopt enumeration (uniq_ML = 1) with a growing energy
-// band until it holds two structures, sorted by energy, second entry taken -- SURVEY 8(f)-4.  Only that entry's ENERGY is
-// used by the caller: the lowest energy over all structures other than one ground-state structure (0 if none lies
-// within 49 kcal/mol of the MFE).
+// fold_subopt.hpp -- the lowest-energy structures next to the ground state, one sequence (or sequence pair) per workgroup on
+// gfx950.  Three kernels over one table fill (kbest_fill) and one exterior level (kbest_exterior):
 //
-// Two-best dynamic programme over an unambiguous decomposition (every structure has one derivation, so the two smallest
-// values of a table entry belong to two different structures):
+//   subopt_kernel         energy of the second-best structure of one strand.  Replaces
+//       get_first_suboptimal_structure_and_energy(seq, fc, 1)[1] of the reference's negative-design option (-nd on;
+//       utils/energy_scores.py:105-107, :453-488): ViennaRNA's subopt enumeration (uniq_ML = 1) with a growing energy band
+//       until it holds two structures, sorted by energy, second entry taken -- SURVEY 8(f)-4.  Only that entry's ENERGY is
+//       used by the caller: the lowest energy over all structures other than one ground-state structure (0 if none lies
+//       within 49 kcal/mol of the MFE).
+//   cofold_subopt_kernel  the same for two strands: fold_cofold_subopt.hpp, over the CO = true instance of the fill below.
+//   kbest_kernel          K lowest-energy structures (energies AND dot-bracket strings) of one strand.  Replaces
+//       get_first_suboptimal_structure_and_energy(seq, fc, k)[0] for k = 1 .. #alt structures, the call behind get_alt_mcc()
+//       in the reference's final ranking of alternative-structure designs (utils/sequence_utils.py:766-793,
+//       utils/energy_scores.py:453-488): entry k of ViennaRNA's energy-sorted subopt list (uniq_ML = 1).
+//
+// K-best dynamic programme over an unambiguous decomposition (every structure has one derivation, so the K smallest
+// values of a table entry belong to K different structures):
 //   F[j]    = { F[j-1] ; F[i-1] + C[i,j] + ext(i,j) }
 //   C[i,j]  = { hairpin ; C[p,q] + interior ; M2[i+1,j-1] + closing }
 //   M[i,j]  (>= 1 stem) = { M[i,j-1] + b ; (k-i) b + C[k,j] + stem ; M[i,k-1] + C[k,j] + stem }
 //   M2[i,j] (>= 2 stems) = { M2[i,j-1] + b ; M[i,k-1] + C[k,j] + stem }
-// One wave per cell: the lanes share the interior-loop shapes and the positions k, the (best, second) pairs are folded
-// with a butterfly over disjoint lane groups.  Tables (pairs of int32, diagonal-major) live in HBM/L2.
+// One wave per cell: the lanes share the interior-loop shapes and the positions k, the K-lists are folded with a butterfly
+// over disjoint lane groups.  Tables (K int32 per entry, diagonal-major) live in HBM/L2.
+//
+// Two strands (concatenated, cut = length of the first): the structures are those cofold_mfe_kernel minimises over
+// (fold_cofold.hpp: canonical non-crossing pairs; hairpins, interior-loop stretches and multiloop backbones inside a strand;
+// the loop whose backbone holds the nick is exterior-like; dangles only inside a strand; DuplexInit iff a pair joins the
+// strands).  The same decomposition with the nick rules of cofold_mfe_kernel, term for term:
+//   C[i,j]  = { hairpin (same strand) ; nick loop: E_ExtLoop + fcA[i+1] + fcB[j-1] (joining pair) ;
+//               C[p,q] + interior (stretches inside a strand) ; M2[i+1,j-1] + closing (i,i+1 and j-1,j neighbours) }
+//   M[i,j]  (>= 1 stem) = { M[i,j-1] + b (j-1,j neighbours) ; (k-i) b + C[k,j] + stem (i..k inside a strand) ;
+//                           M[i,k-1] + C[k,j] + stem (k-1,k neighbours) }
+//   M2[i,j] (>= 2 stems) = { M2[i,j-1] + b (j-1,j neighbours) ; M[i,k-1] + C[k,j] + stem (k-1,k neighbours) }
+//   fcA[x] of [x..cut], fcB[y] of [cut+1..y]: exterior decompositions next to the nick, advanced one entry per diagonal.
+// Pairs that join the strands exist at any distance, so the sweep starts at diagonal 1.  No symmetry reduction for two equal
+// strands: a structure and its rotation by `cut` are two structures.
 #pragma once
-#include "fold_mfe.hpp"
+#include "fold_cofold.hpp"
 
 namespace drna {
 
-struct SubArgs {
+struct SuboptArgs {
   const MfeTables* T = nullptr;
   const Plan* plan = nullptr;
   const int* hp_len = nullptr;
-  const char* seqs = nullptr;     // R x L ASCII
-  int L = 0, ld = 0;
-  int32_t* ws = nullptr;          // per sequence: C, M, M2 as (best, second) int32 pairs: 6 ld*ld int32
+  const char* seqs = nullptr;     // R x L ASCII (two strands: both, no '&')
+  int L = 0, cut = 0, ld = 0;     // cut = length of the first strand, 0 = one strand
+  int DuplexInit = 0;             // two strands only
+  int32_t* ws = nullptr;          // per sequence: C, M, M2 as K-lists: 3 K ld*ld int32 (K = 2 in the second-best kernels)
   long long ws_stride = 0;
+  // second-best kernels
   int32_t* E2 = nullptr;          // R: the reference's subopt energy (dcal/mol; 0 = none within 4900)
   int32_t* E12 = nullptr;         // optional R x 2: the two lowest energies (second = INF_REF if there is one structure only)
+  // kbest_kernel
+  int32_t* E = nullptr;           // R x K energies, ascending (INF_REF where the sequence has fewer structures)
+  char* ss = nullptr;             // R x K x L dot-bracket strings (all dots where E = INF_REF)
   int32_t* status = nullptr;      // R
 };
+// the three kernels had an argument struct each; launch code written against those names keeps compiling
+using SubArgs = SuboptArgs;
+using KbArgs = SuboptArgs;
 
-struct Top2 { int a, b; };
-__device__ __forceinline__ void t2_add(Top2& t, int v) {
-  if (v >= INF_DEV / 2) return;
-  if (v < t.a) { t.b = t.a; t.a = v; }
-  else if (v < t.b) t.b = v;
-}
-__device__ __forceinline__ void t2_add_sum(Top2& t, Top2 x, int e) {
-  if (x.a < INF_DEV / 2) t2_add(t, x.a + e);
-  if (x.b < INF_DEV / 2) t2_add(t, x.b + e);
-}
-__device__ __forceinline__ void t2_add_sum2(Top2& t, Top2 x, Top2 y, int e) {
-  if (x.a >= INF_DEV / 2 || y.a >= INF_DEV / 2) return;
-  t2_add(t, x.a + y.a + e);
-  if (y.b < INF_DEV / 2) t2_add(t, x.a + y.b + e);
-  if (x.b < INF_DEV / 2) t2_add(t, x.b + y.a + e);
-}
-// every lane ends with the two smallest values of the wave (the lane groups merged at each step are disjoint)
-__device__ __forceinline__ Top2 wave_top2(Top2 t) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int oa = __shfl_xor(t.a, o), ob = __shfl_xor(t.b, o);
-    const int lo = min(t.a, oa), hi = max(t.a, oa);
-    t.b = min(hi, min(t.b, ob));
-    t.a = lo;
-  }
-  return t;
-}
-
-struct SubSmem : MfeSmemCore<MAXN> {
-  Top2 F[MAXN + 2];
-};
-
-template <int NT>
-__global__ __launch_bounds__(NT) void subopt_kernel(SubArgs A) {
-  __shared__ SubSmem sm;
-  const MfeTables& T = *A.T;
-  const Plan& P = *A.plan;
-  const int r = blockIdx.x;
-  const int n = A.L, ld = A.ld;
-  const int tid = threadIdx.x, lane = lane_id();
-  const int wave = __builtin_amdgcn_readfirstlane(wave_id());
-  const int INF = INF_DEV, HALF = INF_DEV / 2;
-  int32_t* base = A.ws + (long long)r * A.ws_stride;
-  const long long tab = (long long)ld * ld;
-  Top2* C = reinterpret_cast<Top2*>(base);
-  Top2* M = reinterpret_cast<Top2*>(base + 2 * tab);
-  Top2* M2 = reinterpret_cast<Top2*>(base + 4 * tab);
-
-  stage_energy_tables<NT>(sm, T, tid);
-  // diagonals 0 .. TURN: no pair, no multiloop content
-  for (int d = 0; d <= TURN && d < n; d++)
-    for (int k = tid; k < ld; k += NT) { C[d * ld + k] = Top2{INF, INF}; M[d * ld + k] = Top2{INF, INF}; M2[d * ld + k] = Top2{INF, INF}; }
-  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
-  if (sm.flag) {
-    if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.E2[r] = 0; if (A.E12) { A.E12[2 * r] = 0; A.E12[2 * r + 1] = INF_REF; } }
-    return;
-  }
-
-  for (int d = TURN + 1; d < n; d++) {
-    const int ncell = n - d;
-    for (int i = wave + 1; i <= ncell; i += NT / WAVE) {
-      const int j = i + d;
-      const int t = pair_type(sm.S[i], sm.S[j]);
-      const int tau = t > 2 ? T.TermAU : 0;
-      Top2 c{INF, INF};
-      if (t) {
-        const int si1 = sm.S[i + 1], sj1 = sm.S[j - 1];
-        for (int e = lane; e < NPLAN; e += WAVE) {
-          const int u1 = P.u1[e], u2 = P.u2[e];
-          const int dp = d - 2 - u1 - u2;
-          if (dp <= TURN) continue;
-          const int p = i + 1 + u1, q = j - 1 - u2;
-          const int t2 = pair_type(sm.S[p], sm.S[q]);
-          if (!t2) continue;
-          const Top2 cp = C[dp * ld + p];
-          if (cp.a >= HALF) continue;
-          const int info = (rtype_of(t2) << 4) | (sm.S[q + 1] << 2) | sm.S[p - 1];
-          t2_add_sum(c, cp, mfe_intloop(sm, T, u1, u2, t, si1, sj1, info));
-        }
-        if (lane == 0) {
-          t2_add(c, mfe_hairpin_e(sm, T, A.hp_len[d - 1], i, j, t));
-          t2_add_sum(c, M2[(d - 2) * ld + i + 1], T.MLclosing + T.MLintern + tau + sm.mmM[rtype_of(t) * 16 + sj1 * 4 + si1]);
-        }
-        c = wave_top2(c);
-      }
-      Top2 m{INF, INF}, m2{INF, INF};
-      if (lane == 0) {
-        t2_add_sum(m, M[(d - 1) * ld + i], T.MLbase);
-        t2_add_sum(m2, M2[(d - 1) * ld + i], T.MLbase);
-      }
-      for (int k = i + lane; k <= j - TURN - 1; k += WAVE) {
-        const int tk = pair_type(sm.S[k], sm.S[j]);
-        if (!tk) continue;
-        const Top2 ck = k == i ? c : C[(j - k) * ld + k];
-        if (ck.a >= HALF) continue;
-        const int st = T.MLintern + (tk > 2 ? T.TermAU : 0) + sm.mmM[tk * 16 + sm.S[k - 1] * 4 + sm.S[j + 1]];
-        t2_add_sum(m, ck, (k - i) * T.MLbase + st);
-        if (k > i) {
-          const Top2 mk = M[(k - 1 - i) * ld + i];
-          t2_add_sum2(m, mk, ck, st);
-          t2_add_sum2(m2, mk, ck, st);
-        }
-      }
-      m = wave_top2(m);
-      m2 = wave_top2(m2);
-      if (lane == 0) { C[d * ld + i] = c; M[d * ld + i] = m; M2[d * ld + i] = m2; }
-    }
-    __syncthreads();
-  }
-
-  if (wave != 0) return;
-  sm.F[0] = Top2{0, INF};
-  for (int j = 1; j <= n; j++) {
-    Top2 f{INF, INF};
-    if (lane == 0) t2_add_sum(f, sm.F[j - 1], 0);
-    for (int i = lane + 1; i <= j - TURN - 1; i += WAVE) {
-      const int t = pair_type(sm.S[i], sm.S[j]);
-      if (!t) continue;
-      const Top2 cij = C[(j - i) * ld + i];
-      if (cij.a >= HALF) continue;
-      t2_add_sum2(f, sm.F[i - 1], cij, (t > 2 ? T.TermAU : 0) + mfe_extstem(sm, t, i, j, n));
-    }
-    f = wave_top2(f);
-    sm.F[j] = f;                                   // every lane stores the same value
-  }
-  if (lane == 0) {
-    const Top2 f = sm.F[n];
-    A.status[r] = ST_OK;
-    A.E2[r] = (f.b >= HALF || f.b - f.a > 4900) ? 0 : f.b;
-    if (A.E12) { A.E12[2 * r] = f.a; A.E12[2 * r + 1] = f.b >= HALF ? INF_REF : f.b; }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// K lowest-energy structures (energies AND dot-bracket strings) of one sequence per workgroup.
-// Replaces get_first_suboptimal_structure_and_energy(seq, fc, k)[0] for k = 1 .. #alt structures, the call behind
-// get_alt_mcc() in the reference's final ranking of alternative-structure designs (utils/sequence_utils.py:766-793,
-// utils/energy_scores.py:453-488): entry k of ViennaRNA's energy-sorted subopt list (uniq_ML = 1).  Same unambiguous
-// decomposition as above with K-best lists per table entry, then one traceback per rank: a table entry's r-th value is
-// expanded by re-enumerating the entry's candidates in a fixed order and taking, among those that reproduce the value,
-// the one whose index equals the number of equal values ranked before r.  Different ranks of one entry thus expand to
-// different derivations, i.e. different structures.  The order among structures of EQUAL energy is this enumeration
-// order, not ViennaRNA's (which the reference pins nowhere).
-
+// the K smallest values seen, ascending, duplicates included
 template <int K>
 struct TopK { int v[K]; };
 
@@ -203,6 +88,7 @@ __device__ __forceinline__ void tk_add_sum2(TopK<K>& t, const TopK<K>& x, const 
     for (int b = 0; a + b < K; b++)       // the r-th best sum never needs ranks with a + b > r
       if (x.v[a] < INF_DEV / 2 && y.v[b] < INF_DEV / 2) tk_add(t, x.v[a] + y.v[b] + e);
 }
+// every lane ends with the K smallest values of the wave (the lane groups merged at each step are disjoint)
 template <int K>
 __device__ __forceinline__ TopK<K> wave_topk(TopK<K> t) {
 #pragma unroll
@@ -216,18 +102,234 @@ __device__ __forceinline__ TopK<K> wave_topk(TopK<K> t) {
   return t;
 }
 
-struct KbArgs {
-  const MfeTables* T = nullptr;
-  const Plan* plan = nullptr;
-  const int* hp_len = nullptr;
-  const char* seqs = nullptr;     // R x L ASCII
-  int L = 0, ld = 0;
-  int32_t* ws = nullptr;          // per sequence: C, M, M2 as K-lists: 3 K ld*ld int32
-  long long ws_stride = 0;
-  int32_t* E = nullptr;           // R x K energies, ascending (INF_REF where the sequence has fewer structures)
-  char* ss = nullptr;             // R x K x L dot-bracket strings (all dots where E = INF_REF)
-  int32_t* status = nullptr;      // R
+// K = 2, the lists of the second-best kernels (every scoring step): the two-value form of the merge.  With the generic one
+// above those kernels measured 4 - 14 % slower on an MI355X (profiles/subopt_family.json, generic_k2_build)
+__device__ __forceinline__ TopK<2> wave_topk(TopK<2> t) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int oa = __shfl_xor(t.v[0], o), ob = __shfl_xor(t.v[1], o);
+    const int lo = min(t.v[0], oa), hi = max(t.v[0], oa);
+    t.v[1] = min(hi, min(t.v[1], ob));
+    t.v[0] = lo;
+  }
+  return t;
+}
+
+// C, M, M2 of workgroup r
+template <int K>
+__device__ __forceinline__ void kb_tables(const SuboptArgs& A, int r, TopK<K>*& C, TopK<K>*& M, TopK<K>*& M2) {
+  int32_t* base = A.ws + (long long)r * A.ws_stride;
+  const long long tab = (long long)A.ld * A.ld * K;
+  C = reinterpret_cast<TopK<K>*>(base);
+  M = reinterpret_cast<TopK<K>*>(base + tab);
+  M2 = reinterpret_cast<TopK<K>*>(base + 2 * tab);
+}
+
+// the diagonal sweep that writes C, M, M2 (all threads of the workgroup).  The caller has set the rows below the first
+// diagonal of the sweep (TURN + 1; two strands: 1) and, for two strands (CO), sm.fcA / sm.fcB to the empty decomposition.
+// With CO false every nick test below is a compile-time constant.  (The scalars come from A, lane and wave from the kernel:
+// with n, ld, hp_len ... passed one by one the K = 8 instance takes 80 VGPRs instead of 76.)
+template <int NT, int K, bool CO, class SM>
+__device__ __forceinline__ void kbest_fill(SM& sm, const SuboptArgs& A, TopK<K>* C, TopK<K>* M, TopK<K>* M2, int lane, int wave) {
+  const MfeTables& T = *A.T;
+  const Plan& P = *A.plan;
+  const int n = A.L, cut = A.cut, ld = A.ld;
+  const int* hp_len = A.hp_len;
+  const int HALF = INF_DEV / 2;
+  constexpr int D0 = CO ? 1 : TURN + 1;               // first diagonal that can hold a pair
+  TopK<K> none;
+  tk_init(none);
+  for (int d = D0; d < n; d++) {
+    const int ncell = n - d;
+    for (int i = wave + 1; i <= ncell; i += NT / WAVE) {
+      const int j = i + d;
+      const bool same = !CO || co_same(i, j, cut);
+      const int t = (!CO || d > TURN || !same) ? pair_type(sm.S[i], sm.S[j]) : 0;
+      const int tau = t > 2 ? T.TermAU : 0;
+      const bool adj_i = !CO || co_same(i, i + 1, cut), adj_j = !CO || co_same(j - 1, j, cut);
+      TopK<K> c = none;
+      if (t) {
+        const int si1 = sm.S[i + 1], sj1 = sm.S[j - 1];
+        for (int e = lane; e < NPLAN; e += WAVE) {
+          const int u1 = P.u1[e], u2 = P.u2[e];
+          const int dp = d - 2 - u1 - u2;
+          if (dp < D0) continue;
+          const int p = i + 1 + u1, q = j - 1 - u2;
+          if (CO && (!co_same(i, p, cut) || !co_same(q, j, cut))) continue;
+          const int t2 = pair_type(sm.S[p], sm.S[q]);
+          if (!t2) continue;
+          const TopK<K> cp = C[dp * ld + p];
+          if (cp.v[0] >= HALF) continue;
+          const int info = (rtype_of(t2) << 4) | (sm.S[q + 1] << 2) | sm.S[p - 1];
+          tk_add_sum(c, cp, mfe_intloop(sm, T, u1, u2, t, si1, sj1, info));
+        }
+        if (lane == 0) {
+          if (same) tk_add(c, mfe_hairpin_e(sm, T, hp_len[d - 1], i, j, t));
+          if constexpr (CO)
+            if (!same) tk_add_sum2(c, sm.fcA[i + 1], sm.fcB[j - 1], tau + co_endstem(sm.mmExt, sm, rtype_of(t), adj_j, sj1, adj_i, si1));
+          if (adj_i && adj_j && (!CO || d >= 2))
+            tk_add_sum(c, M2[(d - 2) * ld + i + 1], T.MLclosing + T.MLintern + tau + sm.mmM[rtype_of(t) * 16 + sj1 * 4 + si1]);
+        }
+        c = wave_topk(c);
+      }
+      TopK<K> m = none, m2 = none;
+      if (lane == 0 && adj_j) {
+        tk_add_sum(m, M[(d - 1) * ld + i], T.MLbase);
+        tk_add_sum(m2, M2[(d - 1) * ld + i], T.MLbase);
+      }
+      const bool h3 = j < n && co_same(j, j + 1, cut);  // (two strands)
+      for (int k = i + lane; k <= j - D0; k += WAVE) {
+        const int tk = (!CO || j - k > TURN || !co_same(k, j, cut)) ? pair_type(sm.S[k], sm.S[j]) : 0;
+        if (!tk) continue;
+        // the cell's own list at k = i.  K = 2 selects the values; the longer lists select the address (the chosen list then
+        // goes through scratch): by value the K = 8 instance takes 83 VGPRs instead of 76, one wave less per SIMD
+        TopK<K> ck = c;
+        if constexpr (K == 2) { if (k != i) ck = C[(j - k) * ld + k]; }
+        else ck = k == i ? c : C[(j - k) * ld + k];
+        if (ck.v[0] >= HALF) continue;
+        int st = T.MLintern + (tk > 2 ? T.TermAU : 0);
+        if constexpr (CO) st += co_endstem(sm.mmM, sm, tk, k > 1 && co_same(k - 1, k, cut), sm.S[k - 1], h3, sm.S[j + 1]);
+        else st += sm.mmM[tk * 16 + sm.S[k - 1] * 4 + sm.S[j + 1]];
+        if (!CO || co_same(i, k, cut)) tk_add_sum(m, ck, (k - i) * T.MLbase + st);
+        if (k > i && (!CO || k - 1 != cut)) {
+          const TopK<K> mk = M[(k - 1 - i) * ld + i];
+          tk_add_sum2(m, mk, ck, st);
+          tk_add_sum2(m2, mk, ck, st);
+        }
+      }
+      m = wave_topk(m);
+      m2 = wave_topk(m2);
+      if (lane == 0) { C[d * ld + i] = c; M[d * ld + i] = m; M2[d * ld + i] = m2; }
+    }
+    __syncthreads();
+    if constexpr (CO) {
+      // exterior decompositions next to the nick: fcA[cut - d] of [cut-d .. cut], fcB[cut + 1 + d] of [cut+1 .. cut+1+d]
+      if (wave == 0 && cut - d >= 1) {
+        const int x = cut - d;
+        TopK<K> f = none;
+        if (lane == 0) tk_add_sum(f, sm.fcA[x + 1], 0);
+        for (int k = x + 1 + lane; k <= cut; k += WAVE) {
+          const int t = pair_type(sm.S[x], sm.S[k]);
+          if (!t) continue;
+          const TopK<K> ck = C[(k - x) * ld + x];
+          if (ck.v[0] >= HALF) continue;
+          const int ext = (t > 2 ? T.TermAU : 0) + co_endstem(sm.mmExt, sm, t, x > 1, sm.S[x - 1], k < cut, sm.S[k + 1]);
+          tk_add_sum2(f, ck, sm.fcA[k + 1], ext);
+        }
+        f = wave_topk(f);
+        sm.fcA[x] = f;                               // every lane stores the same value (here and below)
+      }
+      if (wave == (NT > WAVE ? 1 : 0) && cut + 1 + d <= n) {
+        const int y = cut + 1 + d;
+        TopK<K> f = none;
+        if (lane == 0) tk_add_sum(f, sm.fcB[y - 1], 0);
+        for (int k = cut + 1 + lane; k < y; k += WAVE) {
+          const int t = pair_type(sm.S[k], sm.S[y]);
+          if (!t) continue;
+          const TopK<K> ck = C[(y - k) * ld + k];
+          if (ck.v[0] >= HALF) continue;
+          const int ext = (t > 2 ? T.TermAU : 0) + co_endstem(sm.mmExt, sm, t, k > cut + 1, sm.S[k - 1], y < n, sm.S[y + 1]);
+          tk_add_sum2(f, sm.fcB[k - 1], ck, ext);
+        }
+        f = wave_topk(f);
+        sm.fcB[y] = f;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// exterior level over [1..n] from the filled C, one wave (every lane stores the same lists).  One strand: Fu = F above, Fc is
+// not used.  Two strands: the level is split into UNCONNECTED structures (Fu: no pair joins the strands) and CONNECTED ones
+// (Fc: exactly one exterior-level pair joins them -- two could only cross), so every structure is counted once and DuplexInit
+// goes to the connected half only: E = topK(Fu[n] ; Fc[n] + DuplexInit).
+template <int K, bool CO, class SM>
+__device__ __forceinline__ void kbest_exterior(const SM& sm, const MfeTables& T, const TopK<K>* C, TopK<K>* Fu, TopK<K>* Fc, int n,
+                                               int cut, int ld) {
+  const int lane = lane_id(), HALF = INF_DEV / 2;
+  constexpr int D0 = CO ? 1 : TURN + 1;
+  TopK<K> none;
+  tk_init(none);
+  TopK<K> f0 = none;
+  f0.v[0] = 0;
+  Fu[0] = f0;
+  if constexpr (CO) Fc[0] = none;
+  for (int j = 1; j <= n; j++) {
+    TopK<K> fu = none, fc = none;
+    if (lane == 0) {
+      tk_add_sum(fu, Fu[j - 1], 0);
+      if constexpr (CO) tk_add_sum(fc, Fc[j - 1], 0);
+    }
+    const bool h3 = j < n && co_same(j, j + 1, cut);  // (two strands)
+    for (int i = lane + 1; i <= j - D0; i += WAVE) {
+      const bool same = !CO || co_same(i, j, cut);
+      const int t = (!CO || j - i > TURN || !same) ? pair_type(sm.S[i], sm.S[j]) : 0;
+      if (!t) continue;
+      const TopK<K> cij = C[(j - i) * ld + i];
+      if (cij.v[0] >= HALF) continue;
+      int ext = t > 2 ? T.TermAU : 0;
+      if constexpr (CO) ext += co_endstem(sm.mmExt, sm, t, i > 1 && co_same(i - 1, i, cut), sm.S[i - 1], h3, sm.S[j + 1]);
+      else ext += mfe_extstem(sm, t, i, j, n);
+      if (same) {
+        tk_add_sum2(fu, Fu[i - 1], cij, ext);
+        if constexpr (CO) tk_add_sum2(fc, Fc[i - 1], cij, ext);
+      } else {
+        tk_add_sum2(fc, Fu[i - 1], cij, ext);       // the one exterior-level pair that joins the strands
+      }
+    }
+    fu = wave_topk(fu);
+    Fu[j] = fu;
+    if constexpr (CO) { fc = wave_topk(fc); Fc[j] = fc; }
+  }
+}
+
+// status and the two energies of a second-best kernel (one lane)
+__device__ __forceinline__ void second_best_report(const SuboptArgs& A, int r, int status, int e1, int e2) {
+  const int HALF = INF_DEV / 2;
+  A.status[r] = status;
+  A.E2[r] = (e2 >= HALF || e2 - e1 > 4900) ? 0 : e2;
+  if (A.E12) { A.E12[2 * r] = e1; A.E12[2 * r + 1] = e2 >= HALF ? INF_REF : e2; }
+}
+
+struct SubSmem : MfeSmemCore<MAXN> {
+  TopK<2> F[MAXN + 2];
 };
+
+template <int NT>
+__global__ __launch_bounds__(NT) void subopt_kernel(SuboptArgs A) {
+  __shared__ SubSmem sm;
+  const MfeTables& T = *A.T;
+  const int r = blockIdx.x;
+  const int n = A.L, ld = A.ld;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(wave_id());
+  TopK<2>*C, *M, *M2;
+  kb_tables(A, r, C, M, M2);
+
+  stage_energy_tables<NT>(sm, T, tid);
+  // diagonals 0 .. TURN: no pair, no multiloop content
+  TopK<2> none;
+  tk_init(none);
+  for (int d = 0; d <= TURN && d < n; d++)
+    for (int k = tid; k < ld; k += NT) { C[d * ld + k] = none; M[d * ld + k] = none; M2[d * ld + k] = none; }
+  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
+  if (sm.flag) {
+    if (tid == 0) second_best_report(A, r, ST_BAD_CHAR, 0, INF_DEV);
+    return;
+  }
+  kbest_fill<NT, 2, false>(sm, A, C, M, M2, lane_id(), wave);
+  if (wave != 0) return;
+  kbest_exterior<2, false>(sm, T, C, sm.F, nullptr, n, 0, ld);
+  if (tid == 0) second_best_report(A, r, ST_OK, sm.F[n].v[0], sm.F[n].v[1]);
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// kbest_kernel: the fill above with K-lists, then one traceback per rank: a table entry's r-th value is expanded by
+// re-enumerating the entry's candidates in a fixed order and taking, among those that reproduce the value, the one whose
+// index equals the number of equal values ranked before r.  Different ranks of one entry thus expand to different
+// derivations, i.e. different structures.  The order among structures of EQUAL energy is this enumeration order, not
+// ViennaRNA's (which the reference pins nowhere).
 
 template <int K>
 struct KbSmem : MfeSmemCore<MAXN> {
@@ -322,7 +424,7 @@ __device__ int kb_enum(const KbCtx<K>& X, int kind, int i, int j, int v, int e, 
 }
 
 template <int NT, int K>
-__global__ __launch_bounds__(NT) void kbest_kernel(KbArgs A) {
+__global__ __launch_bounds__(NT) void kbest_kernel(SuboptArgs A) {
   __shared__ KbSmem<K> sm;
   const MfeTables& T = *A.T;
   const Plan& P = *A.plan;
@@ -330,12 +432,9 @@ __global__ __launch_bounds__(NT) void kbest_kernel(KbArgs A) {
   const int n = A.L, ld = A.ld;
   const int tid = threadIdx.x, lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
-  const int INF = INF_DEV, HALF = INF_DEV / 2;
-  int32_t* base = A.ws + (long long)r * A.ws_stride;
-  const long long tab = (long long)ld * ld * K;
-  TopK<K>* C = reinterpret_cast<TopK<K>*>(base);
-  TopK<K>* M = reinterpret_cast<TopK<K>*>(base + tab);
-  TopK<K>* M2 = reinterpret_cast<TopK<K>*>(base + 2 * tab);
+  const int HALF = INF_DEV / 2;
+  TopK<K>*C, *M, *M2;
+  kb_tables(A, r, C, M, M2);
   TopK<K>* F = C;                                       // rows 0 .. TURN of C are never read: row 0 holds F[0 .. n]
   int32_t* stacks = reinterpret_cast<int32_t*>(M2);     // rows 0, 1 of M2 are never read: one traceback stack of ld ints per rank
 
@@ -362,76 +461,9 @@ __global__ __launch_bounds__(NT) void kbest_kernel(KbArgs A) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; for (int k = 0; k < K; k++) A.E[r * K + k] = INF_REF; }
     return;
   }
-
-  for (int d = TURN + 1; d < n; d++) {
-    const int ncell = n - d;
-    for (int i = wave + 1; i <= ncell; i += NT / WAVE) {
-      const int j = i + d;
-      const int t = pair_type(sm.S[i], sm.S[j]);
-      const int tau = t > 2 ? T.TermAU : 0;
-      TopK<K> c = none;
-      if (t) {
-        const int si1 = sm.S[i + 1], sj1 = sm.S[j - 1];
-        for (int e = lane; e < NPLAN; e += WAVE) {
-          const int u1 = P.u1[e], u2 = P.u2[e];
-          const int dp = d - 2 - u1 - u2;
-          if (dp <= TURN) continue;
-          const int p = i + 1 + u1, q = j - 1 - u2;
-          const int t2 = pair_type(sm.S[p], sm.S[q]);
-          if (!t2) continue;
-          const TopK<K> cp = C[dp * ld + p];
-          if (cp.v[0] >= HALF) continue;
-          const int info = (rtype_of(t2) << 4) | (sm.S[q + 1] << 2) | sm.S[p - 1];
-          tk_add_sum(c, cp, mfe_intloop(sm, T, u1, u2, t, si1, sj1, info));
-        }
-        if (lane == 0) {
-          tk_add(c, mfe_hairpin_e(sm, T, A.hp_len[d - 1], i, j, t));
-          tk_add_sum(c, M2[(d - 2) * ld + i + 1], T.MLclosing + T.MLintern + tau + sm.mmM[rtype_of(t) * 16 + sj1 * 4 + si1]);
-        }
-        c = wave_topk(c);
-      }
-      TopK<K> m = none, m2 = none;
-      if (lane == 0) {
-        tk_add_sum(m, M[(d - 1) * ld + i], T.MLbase);
-        tk_add_sum(m2, M2[(d - 1) * ld + i], T.MLbase);
-      }
-      for (int k = i + lane; k <= j - TURN - 1; k += WAVE) {
-        const int tk = pair_type(sm.S[k], sm.S[j]);
-        if (!tk) continue;
-        const TopK<K> ck = k == i ? c : C[(j - k) * ld + k];
-        if (ck.v[0] >= HALF) continue;
-        const int st = T.MLintern + (tk > 2 ? T.TermAU : 0) + sm.mmM[tk * 16 + sm.S[k - 1] * 4 + sm.S[j + 1]];
-        tk_add_sum(m, ck, (k - i) * T.MLbase + st);
-        if (k > i) {
-          const TopK<K> mk = M[(k - 1 - i) * ld + i];
-          tk_add_sum2(m, mk, ck, st);
-          tk_add_sum2(m2, mk, ck, st);
-        }
-      }
-      m = wave_topk(m);
-      m2 = wave_topk(m2);
-      if (lane == 0) { C[d * ld + i] = c; M[d * ld + i] = m; M2[d * ld + i] = m2; }
-    }
-    __syncthreads();
-  }
-
+  kbest_fill<NT, K, false>(sm, A, C, M, M2, lane, wave);
   if (wave == 0) {
-    TopK<K> f0 = none;
-    f0.v[0] = 0;
-    F[0] = f0;                                       // every lane stores the same value (here and below)
-    for (int j = 1; j <= n; j++) {
-      TopK<K> f = none;
-      if (lane == 0) tk_add_sum(f, F[j - 1], 0);
-      for (int i = lane + 1; i <= j - TURN - 1; i += WAVE) {
-        const int t = pair_type(sm.S[i], sm.S[j]);
-        if (!t) continue;
-        const TopK<K> cij = C[(j - i) * ld + i];
-        if (cij.v[0] >= HALF) continue;
-        tk_add_sum2(f, F[i - 1], cij, (t > 2 ? T.TermAU : 0) + mfe_extstem(sm, t, i, j, n));
-      }
-      f = wave_topk(f);
-      F[j] = f;
-    }
+    kbest_exterior<K, false>(sm, T, C, F, nullptr, n, 0, ld);
     if (lane == 0) {
       A.status[r] = ST_OK;
       for (int k = 0; k < K; k++) A.E[r * K + k] = F[n].v[k] >= HALF ? INF_REF : F[n].v[k];

@@ -342,17 +342,25 @@ int emu_cofold(const int32_t* blob, int n_int32, int R, int L, int cut, const ch
   return 0;
 }
 
+// arguments of the fold_subopt.hpp kernels for sequence r of a batch that goes through the one workspace slot ws
+static SuboptArgs subopt_args(const Ctx* c, int L, int cut, const char* seqs, std::vector<int32_t>& ws, int r, int32_t* status) {
+  SuboptArgs a;
+  const int ld = L + 2;
+  a.T = &c->H.mfe; a.plan = &c->H.plan; a.hp_len = c->H.hp_len.data(); a.seqs = seqs; a.L = L; a.cut = cut; a.ld = ld;
+  a.DuplexInit = c->H.DuplexInit;
+  a.ws_stride = (long long)ws.size(); a.ws = ws.data() - (size_t)r * ws.size();
+  a.status = status;
+  return a;
+}
+
 // two-best energies (second-best structure) of R sequences
 int emu_subopt(const int32_t* blob, int n_int32, int R, int L, const char* seqs, int nt, int32_t* E2, int32_t* E12, int32_t* status) {
   Ctx* c = make_ctx(blob, n_int32, L);
   if (!c->ok) { delete c; return -1; }
-  const int ld = L + 2;
-  std::vector<int32_t> ws((size_t)6 * ld * ld, 0);
+  std::vector<int32_t> ws((size_t)3 * 2 * (L + 2) * (L + 2), 0);
   for (int r = 0; r < R; r++) {
-    SubArgs a;
-    a.T = &c->H.mfe; a.plan = &c->H.plan; a.hp_len = c->H.hp_len.data(); a.seqs = seqs; a.L = L; a.ld = ld;
-    a.ws = ws.data() - (size_t)r * 6 * ld * ld; a.ws_stride = (long long)6 * ld * ld;
-    a.E2 = E2; a.E12 = E12; a.status = status;
+    SuboptArgs a = subopt_args(c, L, 0, seqs, ws, r, status);
+    a.E2 = E2; a.E12 = E12;
     if (nt == 64) emu_launch(r, 64, [&]() { subopt_kernel<64>(a); });
     else emu_launch(r, 128, [&]() { subopt_kernel<128>(a); });
   }
@@ -361,23 +369,20 @@ int emu_subopt(const int32_t* blob, int n_int32, int R, int L, const char* seqs,
 }
 // K lowest-energy structures (energies + strings) of R sequences
 int emu_kbest(const int32_t* blob, int n_int32, int R, int L, const char* seqs, int nt, int K, int32_t* E, char* ss, int32_t* status) {
+  if (K != 4 && K != 8) return -2;
   Ctx* c = make_ctx(blob, n_int32, L);
   if (!c->ok) { delete c; return -1; }
-  const int ld = L + 2;
-  const size_t stride = (size_t)3 * K * ld * ld;
-  std::vector<int32_t> ws(stride, 0);
+  std::vector<int32_t> ws((size_t)3 * K * (L + 2) * (L + 2), 0);
   for (int r = 0; r < R; r++) {
-    KbArgs a;
-    a.T = &c->H.mfe; a.plan = &c->H.plan; a.hp_len = c->H.hp_len.data(); a.seqs = seqs; a.L = L; a.ld = ld;
-    a.ws = ws.data() - (size_t)r * stride; a.ws_stride = (long long)stride;
-    a.E = E; a.ss = ss; a.status = status;
+    SuboptArgs a = subopt_args(c, L, 0, seqs, ws, r, status);
+    a.E = E; a.ss = ss;
     if (K == 4) {
       if (nt == 64) emu_launch(r, 64, [&]() { kbest_kernel<64, 4>(a); });
       else emu_launch(r, 128, [&]() { kbest_kernel<128, 4>(a); });
-    } else if (K == 8) {
+    } else {
       if (nt == 64) emu_launch(r, 64, [&]() { kbest_kernel<64, 8>(a); });
       else emu_launch(r, 128, [&]() { kbest_kernel<128, 8>(a); });
-    } else { delete c; return -2; }
+    }
   }
   delete c;
   return 0;
@@ -389,14 +394,10 @@ int emu_cofold_subopt(const int32_t* blob, int n_int32, int R, int L, int cut, c
   if (nt != 64 && nt != 128) return -2;
   Ctx* c = make_ctx(blob, n_int32, L);
   if (!c->ok) { delete c; return -1; }
-  const int ld = L + 2;
-  std::vector<int32_t> ws((size_t)6 * ld * ld, 0);
+  std::vector<int32_t> ws((size_t)3 * 2 * (L + 2) * (L + 2), 0);
   for (int r = 0; r < R; r++) {
-    CoSubArgs a;
-    a.T = &c->H.mfe; a.plan = &c->H.plan; a.hp_len = c->H.hp_len.data(); a.seqs = seqs; a.L = L; a.cut = cut; a.ld = ld;
-    a.DuplexInit = c->H.DuplexInit;
-    a.ws = ws.data() - (size_t)r * 6 * ld * ld; a.ws_stride = (long long)6 * ld * ld;
-    a.E2 = E2; a.E12 = E12; a.status = status;
+    SuboptArgs a = subopt_args(c, L, cut, seqs, ws, r, status);
+    a.E2 = E2; a.E12 = E12;
     if (nt == 64) emu_launch(r, 64, [&]() { cofold_subopt_kernel<64>(a); });
     else emu_launch(r, 128, [&]() { cofold_subopt_kernel<128>(a); });
   }

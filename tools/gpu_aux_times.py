@@ -34,6 +34,21 @@ def cofold_edef(eng, seqs):
     return {"cofold_pf_ms": p, "inside_in_edef_call_ms": t["inside"], "cofold_outside_ms": t["outside"]}
 
 
+def subopt_energy(eng, seqs):
+    """second-best structure energy of one strand (-nd on, every scoring step)"""
+    eng.subopt_energy(seqs)
+    return {"subopt_ms": eng.last_timing()["mfe"]}
+
+
+def subopt_structs(eng, seqs):
+    """K lowest-energy structures with their strings (get_alt_mcc), both kernel instantiations"""
+    out = {}
+    for K in (4, 8):
+        eng.subopt_structs(seqs, K)
+        out["kbest%d_ms" % K] = eng.last_timing()["mfe"]
+    return out
+
+
 PAIRS = ((64, 18, 18), (64, 50, 50), (64, 100, 100))
 # one round of a section -> (shapes (R, strand lengths ...), seed, a fresh generator per shape, rounds, derived figure)
 SECTIONS = {
@@ -41,21 +56,38 @@ SECTIONS = {
            lambda R, v: ("defects_per_s", R / ((v["inside_ms"] + v["outside_ms"]) * 1e-3))),
     cofold_subopt: (PAIRS, 5, False, 5, lambda R, v: ("ratio", v["cofold_subopt_ms"] / v["cofold_mfe_ms"])),
     cofold_edef: (PAIRS, 5, False, 5, lambda R, v: ("ratio", v["cofold_outside_ms"] / v["cofold_pf_ms"])),
+    subopt_energy: (((64, 36), (64, 100), (64, 200)), 5, False, 5, lambda R, v: ("folds_per_s", R / (v["subopt_ms"] * 1e-3))),
+    subopt_structs: (((16, 100), (16, 200)), 5, False, 5, lambda R, v: ("ratio", v["kbest8_ms"] / v["kbest4_ms"])),
 }
-out = {}
-for one_round, (shapes, seed, reseed, rounds, derived) in SECTIONS.items():
-    if sys.argv[1:] and one_round.__name__ not in sys.argv[1:]:
-        continue
+
+
+def section_inputs(name):
+    """(key, R, total length, sequences) of every shape of a section, as the timing loop below draws them"""
+    one_round = next(f for f in SECTIONS if f.__name__ == name)
+    shapes, seed, reseed = SECTIONS[one_round][:3]
     rng = np.random.default_rng(seed)
-    sec = out[one_round.__name__] = {}
     for R, *lens in shapes:
         rng = np.random.default_rng(seed) if reseed else rng
         seqs = ["&".join("".join(rng.choice(list("ACGU"), n)) for n in lens) for _ in range(R)]
-        eng = E.Engine(max_R=R, max_L=sum(lens), device=0)
-        eng.set_targets(["." * sum(lens)])
-        runs = [one_round(eng, seqs) for _ in range(rounds)]
-        v = {k: float(np.median([r[k] for r in runs[1:]])) for k in runs[0]}
-        v.update([derived(R, v)])
-        sec["R%d_" % R + ("L%d" % lens[0] if len(lens) == 1 else "%d+%d" % tuple(lens))] = v
-        eng.close()
-print(json.dumps(out))
+        yield "R%d_" % R + ("L%d" % lens[0] if len(lens) == 1 else "%d+%d" % tuple(lens)), R, sum(lens), seqs
+
+
+def main(names):
+    out = {}
+    for one_round, (_, _, _, rounds, derived) in SECTIONS.items():
+        if names and one_round.__name__ not in names:
+            continue
+        sec = out[one_round.__name__] = {}
+        for key, R, L, seqs in section_inputs(one_round.__name__):
+            eng = E.Engine(max_R=R, max_L=L, device=0)
+            eng.set_targets(["." * L])
+            runs = [one_round(eng, seqs) for _ in range(rounds)]
+            v = {k: float(np.median([r[k] for r in runs[1:]])) for k in runs[0]}
+            v.update([derived(R, v)])
+            sec[key] = v
+            eng.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
