@@ -19,6 +19,7 @@
 #include "eval_structure.hpp"
 #include "fold_mfe.hpp"
 #include "fold_cofold.hpp"
+#include "fold_cofold_lds.hpp"
 #include "fold_mfe_lds.hpp"
 #include "fold_mfe_dual.hpp"
 #include "fold_fused.hpp"
@@ -84,6 +85,8 @@ struct drna_engine {
   int* d_rpt_off = nullptr;
   std::vector<int> rt_len;
   double* d_F4 = nullptr;   // co-fold free energies (FA, FB, FcAB, FAB per pair)
+  double *hm_F4 = nullptr, *dm_F4 = nullptr;   // ... of drna_cofold_batch and drna_mc_run_cofold: host-mapped like hm_Epf, allocated on first use
+  bool cofold_lds = true;   // option "cofold_lds": pairs of at most CO_LDS_MAX nt fold with their tables in LDS (fold_cofold_lds.hpp)
   // K-best structures: workspace for kb_chunk sequences, allocated on first use
   int32_t* d_ws_kb = nullptr;
   int32_t* d_kbE = nullptr;
@@ -384,7 +387,7 @@ extern "C" void drna_destroy(drna_engine* e) {
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_status) (void)hipHostFree(e->h_status);
-  void* hm[] = {e->hm_seqs, e->hm_ss, e->hm_Epf, e->hm_Emfe, e->hm_Ed, e->h_clk};
+  void* hm[] = {e->hm_seqs, e->hm_ss, e->hm_Epf, e->hm_Emfe, e->hm_Ed, e->hm_F4, e->h_clk};
   for (void* b : hm)
     if (b) (void)hipHostFree(b);
   hipStream_t ss[] = {e->s_mfe, e->s_pf, e->s_eval};
@@ -407,6 +410,7 @@ extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!strcmp(name, "dual")) { e->dual = value != 0; e->dual_force = value == 2; return DRNA_OK; }
   if (!strcmp(name, "strips")) { e->strips = value < 0 ? 0 : value > 2 ? 2 : value; return DRNA_OK; }
   if (!strcmp(name, "pf_helper")) { e->pf_helper = value != 0; return DRNA_OK; }
+  if (!strcmp(name, "cofold_lds")) { e->cofold_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "helper_fault")) { e->helper_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "strip_fault")) { e->strip_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "mfe_fark_min_strips")) { e->mfe_fark_min_strips = value < 1 ? 1 : value; return DRNA_OK; }
@@ -431,6 +435,8 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "strips")) { *value = e->strips; return DRNA_OK; }
   if (!strcmp(name, "pf_helper")) { *value = e->pf_helper ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "fused")) { *value = e->fused ? 1 : 0; return DRNA_OK; }
+  if (!strcmp(name, "cofold_lds")) { *value = e->cofold_lds ? 1 : 0; return DRNA_OK; }
+  if (!strcmp(name, "cofold_lds_max")) { *value = CO_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "last_fused")) { *value = e->last_fused ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "fused_blocks_per_cu")) { *value = e->fused_blocks_per_cu; return DRNA_OK; }
   if (!strcmp(name, "pair_blocks_per_cu")) { *value = e->pair_blocks_per_cu; return DRNA_OK; }
@@ -812,6 +818,18 @@ extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char*
   return sub_batches();
 }
 
+// host-mapped E(targets) of max_R sequences against the installed targets (allocated on first use, again after more targets)
+static int mapped_Ed(drna_engine* e) {
+  const size_t cap = (size_t)e->max_R * (e->n_targets > 0 ? e->n_targets : 1);
+  if (e->hm_Ed_cap >= cap) return DRNA_OK;
+  if (e->hm_Ed) (void)hipHostFree(e->hm_Ed);
+  e->hm_Ed = nullptr; e->hm_Ed_cap = 0;
+  HIP_TRY(hipHostMalloc((void**)&e->hm_Ed, cap * sizeof(int32_t), hipHostMallocMapped));
+  HIP_TRY(hipHostGetDevicePointer((void**)&e->dm_Ed, e->hm_Ed, 0));
+  e->hm_Ed_cap = cap;
+  return DRNA_OK;
+}
+
 extern "C" int drna_score_batch(drna_engine* e, int R, int L, const char* seqs, uint32_t flags, double* Epf,
                                 int32_t* Emfe, char* mfe_ss, int32_t* Ed) {
   if (!e) return DRNA_ERR_ARG;
@@ -824,14 +842,7 @@ extern "C" int drna_score_batch(drna_engine* e, int R, int L, const char* seqs, 
   }
   HIP_TRY(hipSetDevice(e->device));
   const size_t ned = (size_t)R * (e->n_targets > 0 ? e->n_targets : 1);
-  if (want_ev && e->hm_Ed_cap < ned) {
-    if (e->hm_Ed) (void)hipHostFree(e->hm_Ed);
-    e->hm_Ed = nullptr; e->hm_Ed_cap = 0;
-    const size_t cap = (size_t)e->max_R * (e->n_targets > 0 ? e->n_targets : 1);
-    HIP_TRY(hipHostMalloc((void**)&e->hm_Ed, cap * sizeof(int32_t), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&e->dm_Ed, e->hm_Ed, 0));
-    e->hm_Ed_cap = cap;
-  }
+  if (want_ev) { const int rc = mapped_Ed(e); if (rc != DRNA_OK) return rc; }
   std::memcpy(e->hm_seqs, seqs, (size_t)R * L);
   int rc = drna_score_batch_device(e, R, L, e->dm_seqs, flags, e->dm_Epf, e->dm_Emfe, e->dm_ss, e->dm_Ed);
   if (rc != DRNA_OK) return rc;
@@ -1350,30 +1361,35 @@ extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const cha
 
 // ---------------------------------------------------------------- two strands (co-fold)
 
-extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const char* seqs, uint32_t flags, double* F4,
-                                 int32_t* Emfe, char* mfe_ss, int32_t* Ed) {
-  if (!e) return DRNA_ERR_ARG;
-  const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & DRNA_NEED_MFE, want_ev = flags & DRNA_NEED_EVAL;
-  const char* who = "drna_cofold_batch";
-  int rc = aux_check(e, who, R, L, &cut, seqs && (!want_pf || F4) && (!want_mfe || (Emfe && mfe_ss)) && (!want_ev || Ed) && !(flags & DRNA_NEED_PK),
-                     "output pointers for every requested flag; no NEED_PK");
-  if (rc == DRNA_OK && want_ev) rc = need_targets(e, who, L);
-  if (rc == DRNA_OK) rc = fits_workspace(e, who, R);
-  if (rc != DRNA_OK) return rc;
+// R pairs whose letters the caller has put into hm_seqs (L each, no '&'): both folds side by side on their streams and the
+// two-strand evaluation, every result written by the kernels into the host-mapped buffers (hm_F4, hm_Emfe, hm_ss, hm_Ed), so a
+// batch costs no hipMemcpy.  Pairs of at most CO_LDS_MAX nucleotides take the LDS-resident kernels (option "cofold_lds")
+static int cofold_batch_mapped(drna_engine* e, int R, int L, int cut, bool want_pf, bool want_mfe, bool want_ev) {
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->d_F4) HIP_TRY(hipMalloc((void**)&e->d_F4, (size_t)4 * e->max_R * sizeof(double)));
-  HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
+  if (!e->hm_F4) {
+    HIP_TRY(hipHostMalloc((void**)&e->hm_F4, (size_t)4 * e->max_R * sizeof(double), hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer((void**)&e->dm_F4, e->hm_F4, 0));
+  }
+  if (want_ev) { const int rc = mapped_Ed(e); if (rc != DRNA_OK) return rc; }
   reset_status(e);
-  const CoArgs a = co_args(e, e->d_seqs, L, cut, L + 2);
+  CoArgs a = co_args(e, e->dm_seqs, L, cut, L + 2);
+  a.F4 = e->dm_F4; a.Emfe = e->dm_Emfe; a.ss = e->dm_ss;
+  const bool lds = e->cofold_lds && L <= CO_LDS_MAX;
   HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
   HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-  if (want_pf) hipLaunchKernelGGL(cofold_pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a);
-  if (want_mfe) hipLaunchKernelGGL(cofold_mfe_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
+  if (want_pf) {
+    if (lds) hipLaunchKernelGGL(cofold_pf_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a);
+    else hipLaunchKernelGGL(cofold_pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, a);
+  }
+  if (want_mfe) {
+    if (lds) hipLaunchKernelGGL(cofold_mfe_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
+    else hipLaunchKernelGGL(cofold_mfe_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(e->ev_p1, e->s_pf));
   HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
   if (want_ev) {
-    EvalArgs v = eval_args(e, e->d_seqs, L, e->d_Ed);
+    EvalArgs v = eval_args(e, e->dm_seqs, L, e->dm_Ed);
     v.cut = cut; v.DuplexInit = e->H.DuplexInit;
     hipLaunchKernelGGL(eval_kernel, dim3(R * e->n_targets), dim3(WAVE), 0, e->s_eval, v);
     HIP_TRY(hipGetLastError());
@@ -1384,14 +1400,28 @@ extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const ch
   HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
   HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
   e->timing[2] = 0.f; e->timing[3] = e->timing[0] > e->timing[1] ? e->timing[0] : e->timing[1];
-  rc = fold_status(e, R, want_mfe, want_pf, nullptr, 0, "traceback could not reproduce a table value");
+  return fold_status(e, R, want_mfe, want_pf, nullptr, 0, "traceback could not reproduce a table value");
+}
+
+extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const char* seqs, uint32_t flags, double* F4,
+                                 int32_t* Emfe, char* mfe_ss, int32_t* Ed) {
+  if (!e) return DRNA_ERR_ARG;
+  const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & DRNA_NEED_MFE, want_ev = flags & DRNA_NEED_EVAL;
+  const char* who = "drna_cofold_batch";
+  int rc = aux_check(e, who, R, L, &cut, seqs && (!want_pf || F4) && (!want_mfe || (Emfe && mfe_ss)) && (!want_ev || Ed) && !(flags & DRNA_NEED_PK),
+                     "output pointers for every requested flag; no NEED_PK");
+  if (rc == DRNA_OK && want_ev) rc = need_targets(e, who, L);
+  if (rc == DRNA_OK) rc = fits_workspace(e, who, R);
   if (rc != DRNA_OK) return rc;
-  if (want_pf) HIP_TRY(hipMemcpy(F4, e->d_F4, (size_t)4 * R * sizeof(double), hipMemcpyDeviceToHost));
+  std::memcpy(e->hm_seqs, seqs, (size_t)R * L);
+  rc = cofold_batch_mapped(e, R, L, cut, want_pf, want_mfe, want_ev);
+  if (rc != DRNA_OK) return rc;
+  if (want_pf) std::memcpy(F4, e->hm_F4, (size_t)4 * R * sizeof(double));
   if (want_mfe) {
-    HIP_TRY(hipMemcpy(Emfe, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(mfe_ss, e->d_ss, (size_t)R * L, hipMemcpyDeviceToHost));
+    std::memcpy(Emfe, e->hm_Emfe, (size_t)R * sizeof(int32_t));
+    std::memcpy(mfe_ss, e->hm_ss, (size_t)R * L);
   }
-  if (want_ev) HIP_TRY(hipMemcpy(Ed, e->d_Ed, (size_t)R * e->n_targets * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (want_ev) std::memcpy(Ed, e->hm_Ed, (size_t)R * e->n_targets * sizeof(int32_t));
   return DRNA_OK;
 }
 
@@ -1432,7 +1462,27 @@ struct ProposeCtx {
   const int32_t *snake_of = nullptr, *snake_off = nullptr, *snake_nodes = nullptr, *snake_nstates = nullptr;
   const char* snake_states = nullptr;
   std::vector<int> pt, pd, mutable_pos;
+  // two strands (drna_propose_batch_co, drna_mc_run_cofold): the strings keep the '&' at column amp (-1: one strand) as a fixed,
+  // unpaired letter; homodimer: the reference's strand-copy rules follow every move, ss_equal = both sub-structures are the same
+  int amp = -1;
+  bool homodimer = false, ss_equal = false;
+  bool fixed(int i) const { return i == amp || __builtin_popcount(allowed_mask[i] & 15u) == 1; }
 };
+// the two-strand part of a context built by propose_ctx_init: target and every string carry the '&' at the same column
+static int propose_ctx_two_strands(ProposeCtx& c, const char* target, int oligo_state) {
+  const int L = c.L;
+  int amp = -1;
+  for (int i = 0; i < L; i++)
+    if (target[i] == '&') { if (amp >= 0) return DRNA_ERR_ARG; amp = i; }
+  if (amp < 1 || amp > L - 2 || (oligo_state != 1 && oligo_state != 2)) return DRNA_ERR_ARG;
+  c.amp = amp;
+  c.homodimer = oligo_state == 2;
+  c.ss_equal = L - amp - 1 == amp && std::memcmp(target, target + amp + 1, (size_t)amp) == 0;
+  c.mutable_pos.clear();
+  for (int i = 0; i < L; i++)
+    if (!c.fixed(i)) c.mutable_pos.push_back(i);
+  return c.mutable_pos.empty() ? DRNA_ERR_ARG : DRNA_OK;
+}
 static int propose_ctx_init(ProposeCtx& c, int L, const char* target, const int32_t* partner, const unsigned char* allowed_mask,
                             const int32_t* snake_of, const int32_t* snake_off, const int32_t* snake_nodes,
                             const int32_t* snake_nstates, const char* snake_states, int n_shelves, double tm_max, double tm_min,
@@ -1471,7 +1521,7 @@ static int targeted_pool(const ProposeCtx& c, const int* pq, char* mark, int* po
   std::memset(mark, 0, (size_t)L);
   bool any = false;
   for (int i = 0; i < L; i++)
-    if (c.pt[i] != pq[i] && (c.pt[i] >= 0 || pq[i] >= 0) && __builtin_popcount(c.allowed_mask[i] & 15u) != 1) {
+    if (c.pt[i] != pq[i] && (c.pt[i] >= 0 || pq[i] >= 0) && !c.fixed(i)) {
       any = true;                                       // end of a false-negative or false-positive pair
       for (int k = -3; k <= 3; k++) { const int x = i + k; if (x > 0 && x <= L - 1) mark[x] = 1; }
     }
@@ -1480,6 +1530,30 @@ static int targeted_pool(const ProposeCtx& c, const int* pq, char* mark, int* po
     for (int i = 0; i < L; i++) if (mark[i]) pool[np++] = i;
   return any ? np : -1;                                  // -1: no mispaired position (no draw is made then)
 }
+// Homodimer designs: the reference's strand-copy rules after a move at pos (utils/sequence_utils.py:1104-1126), s = the sequence
+// before the move, o = after it.  Two different sub-structures: a pair move outside a snake is crossed over, strand 1 takes the
+// letter of strand 2 at the pair's second end (as an index into strand 2) and strand 2 that of strand 1 at the first end.  Two
+// equal sub-structures: the strand that changed is copied over the other.  The reference does the first with Python slices
+// (s1[:b] + s2[b] + s1[b+1:]); an index that would change a string's length there (b = -1, an index past the end) is an error here
+static int homodimer_copy(const ProposeCtx& c, const char* s, int pos, char* o) {
+  const int len1 = c.amp, len2 = c.L - c.amp - 1;
+  char *s1 = o, *s2 = o + len1 + 1;
+  const int j = c.pd[pos];
+  if (j >= 0 && !(c.snake_of && c.snake_of[pos] >= 0) && !c.ss_equal) {
+    const int a = pos < j ? pos : j, b = (pos < j ? j : pos) - len1 - 1;
+    // Python's index rules: a negative index counts from the end
+    if (a >= len1 || a >= len2 || b >= len1 || b >= len2 || b == -1 || b < -len1 || b < -len2) return DRNA_ERR_ARG;
+    const char from2 = s2[b >= 0 ? b : len2 + b], from1 = s1[a];
+    s1[b >= 0 ? b : len1 + b] = from2;
+    s2[a] = from1;
+  }
+  if (c.ss_equal) {
+    if (std::memcmp(s1, s, (size_t)len1) != 0) std::memcpy(s2, s1, (size_t)len1);
+    else if (std::memcmp(s2, s + len1 + 1, (size_t)len2) != 0) std::memcpy(s1, s2, (size_t)len1);
+  }
+  return DRNA_OK;
+}
+
 // one proposal of one replica: s = its sequence, pool / np = targeted_pool of its current MFE structure (np = -1 without targeted
 // moves), p_shelf = shelf_probability of its temperature shelf
 static int propose_one(const ProposeCtx& c, const char* s, const int* pool, int np, double p_shelf, drna_host::Mt st, char* o) {
@@ -1531,7 +1605,7 @@ static int propose_one(const ProposeCtx& c, const char* s, const int* pool, int 
       for (int b = 0; b < 4; b++) if (o2 & (1u << b)) { if (!k2--) { o[pos] = LET[n1]; o[j] = LET[b]; break; } }
     }
   }
-  return DRNA_OK;
+  return c.homodimer ? homodimer_copy(c, s, pos, o) : DRNA_OK;
 }
 
 // one proposal per replica; partner = partner of every design pair (target + ordinary alternative pairs), snakes optional
@@ -1539,11 +1613,12 @@ static int propose_impl(int R, int L, const char* target, const int32_t* partner
                         const int32_t* snake_of, const int32_t* snake_off, const int32_t* snake_nodes,
                         const int32_t* snake_nstates, const char* snake_states, const char* seqs, const char* mfe_ss,
                         const int32_t* shelf_index, int n_shelves, double tm_max, double tm_min, int targeted,
-                        uint32_t* rng_state, char* out_seqs) {
+                        uint32_t* rng_state, char* out_seqs, int oligo_state = 0) {
   using namespace drna_host;
   ProposeCtx c;
   int rc = propose_ctx_init(c, L, target, partner, allowed_mask, snake_of, snake_off, snake_nodes, snake_nstates, snake_states,
                             n_shelves, tm_max, tm_min, targeted);
+  if (rc == DRNA_OK && oligo_state) rc = propose_ctx_two_strands(c, target, oligo_state);
   if (rc != DRNA_OK) return rc;
   std::vector<int> pq(L), pool(L);
   std::vector<char> mark(L);
@@ -1592,6 +1667,16 @@ extern "C" int drna_propose_batch_alt(int R, int L, const char* target, const in
                       out_seqs);
 }
 
+extern "C" int drna_propose_batch_co(int R, int L, const char* target, const unsigned char* allowed_mask, int oligo_state,
+                                     const char* seqs, const char* mfe_ss, const int32_t* shelf_index, int n_shelves, double tm_max,
+                                     double tm_min, int targeted, uint32_t* rng_state, char* out_seqs) {
+  if (R < 0 || L < 3 || L > 2048 || !target || !allowed_mask || (oligo_state != 1 && oligo_state != 2) ||
+      (R > 0 && (!seqs || !mfe_ss || !shelf_index || !rng_state || !out_seqs)))
+    return DRNA_ERR_ARG;
+  return propose_impl(R, L, target, nullptr, allowed_mask, nullptr, nullptr, nullptr, nullptr, nullptr, seqs, mfe_ss,
+                      shelf_index, n_shelves, tm_max, tm_min, targeted, rng_state, out_seqs, oligo_state);
+}
+
 extern "C" int drna_metropolis_batch(int R, const double* score_o, const double* score_m, const double* temps, double Lconst,
                                      uint32_t* rng_state, unsigned char* accept, unsigned char* better) {
   if (R < 0 || (R > 0 && (!score_o || !score_m || !temps || !rng_state || !accept || !better))) return DRNA_ERR_ARG;
@@ -1606,39 +1691,29 @@ extern "C" int drna_metropolis_batch(int R, const double* score_o, const double*
 
 // ---------------------------------------------------------------- the whole Monte-Carlo inner loop of one exchange step
 
-extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char* target, const int32_t* partner,
-                           const unsigned char* allowed_mask, const int32_t* snake_of, int n_snakes, const int32_t* snake_off,
-                           const int32_t* snake_nodes, const int32_t* snake_nstates, const char* snake_states,
-                           const int32_t* shelf_index, int n_shelves, double tm_max, double tm_min, int targeted,
-                           const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w,
-                           uint32_t flags, uint32_t* rng_state, char* seqs, char* mfe_ss, double* score, double* mcc1,
-                           double* Epf, double* Ed, int64_t* counters, char* best_seq, char* best_ss, double* best) {
+// What one scoring pass over the R proposals of an iteration leaves per replica (filled by the entry point's score step)
+struct McScored {
+  std::vector<char> ss;                          // R x L MFE structures, in the layout of the state strings
+  std::vector<double> Epf, ed, Emfe, edef;       // kcal/mol: ensemble free energy, E(targets[0]), MFE energy; ensemble defect
+  std::vector<double> add;                       // added to the -sf sum (alternative structures; oligomer / monomer-fraction bonus)
+  std::vector<double> x0, x1;                    // two strands: oligo_fraction and the bonus, kept with an accepted state
+  bool has_add = false;
+};
+
+// The loop both drna_mc_run and drna_mc_run_cofold run: proposals from the replicas' own streams, the entry point's scoring of
+// all R proposals (score_all(prop) fills S), SimScore (metrics(ss, pq): pair table of the L-char structure for the targeted
+// moves, and the three rounded metrics against the target), the -sf sum, Metropolis, state update, counters and best state.
+// L is the length of the state strings (two strands: with the '&'); xs0 / xs1: per-replica state beside the usual arrays or null
+template <class ScoreAll, class Metrics>
+static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, ProposeCtx& ctx, const int32_t* shelf_index, int targeted,
+                   const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w, uint32_t* rng_state,
+                   char* seqs, char* mfe_ss, double* score, double* mcc1, double* Epf, double* Ed, double* xs0, double* xs1,
+                   int64_t* counters, char* best_seq, char* best_ss, double* best, McScored& S, ScoreAll&& score_all,
+                   Metrics&& metrics) {
   using namespace drna_host;
-  if (!e) return DRNA_ERR_ARG;
-  if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || n_iter < 0 || !target || !allowed_mask || !shelf_index || !temps ||
-      n_terms < 1 || !term_id || !term_w || !rng_state || !seqs || !mfe_ss || !score || !mcc1 || !Epf || !Ed || !counters ||
-      !best_seq || !best_ss || !best || e->n_targets < 1 || e->L_targets != L) {
-    e->err = "drna_mc_run: bad argument (targets installed with drna_set_targets for this L; every state array given)";
-    return DRNA_ERR_ARG;
-  }
-  const int nt = e->n_targets;
-  std::vector<char> prop((size_t)R * L), pss((size_t)R * L);
-  std::vector<double> pEpf(R), pscore(R), pmcc(R), pEdef, p_shelf(R, 0.0);
-  bool want_edef = false;                  // term 6: ensemble defect against targets[0] (utils/energy_scores.py:362-374,397-398)
-  for (int k = 0; k < n_terms; k++) {
-    want_edef |= term_id[k] == 6;
-    if (term_id[k] < 0 || term_id[k] > 6) { e->err = "drna_mc_run: unknown scoring term"; return DRNA_ERR_ARG; }
-  }
-  if (want_edef) pEdef.resize(R);
-  std::vector<int32_t> pEmfe(R), pEd((size_t)R * nt);
+  std::vector<char> prop((size_t)R * L);
+  std::vector<double> pscore(R), pmcc(R), p_shelf(R, 0.0);
   std::vector<unsigned char> acc(R), better(R);
-  ProposeCtx ctx;
-  {
-    const int rc = propose_ctx_init(ctx, L, target, partner, allowed_mask, n_snakes > 0 ? snake_of : nullptr, snake_off, snake_nodes,
-                                    snake_nstates, snake_states, n_shelves, tm_max, tm_min, targeted);
-    if (rc != DRNA_OK) { e->err = rc == DRNA_ERR_STRUCTURE ? "drna_mc_run: unbalanced target structure" : "drna_mc_run: proposal failed"; return rc; }
-  }
-  const int* pr = ctx.pt.data();
   // Per replica, of its CURRENT structure: the pair table, its SimScore against the target and the targeted-move pool (what the
   // proposal compares with the target).  Parsed once here and replaced when a proposal is accepted; a proposal whose MFE
   // structure equals the current one (most single mutations of a converged replica) reuses all three
@@ -1658,55 +1733,42 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
   };
   for (int r = 0; r < R; r++) {
     if (targeted) p_shelf[r] = shelf_probability(ctx, shelf_index[r]);
-    if (!pair_table(mfe_ss + (size_t)r * L, L, cur_pq.data() + (size_t)r * L)) { fail = DRNA_ERR_STRUCTURE; continue; }
-    cur_m[r] = sim_metrics(pr, cur_pq.data() + (size_t)r * L, L);
+    if (!metrics(mfe_ss + (size_t)r * L, cur_pq.data() + (size_t)r * L, cur_m[r])) { fail = DRNA_ERR_STRUCTURE; continue; }
     refresh_pool(r);
   }
   if (n_iter > 0 && fail == DRNA_OK) propose_all();
-  if (fail != DRNA_OK) { e->err = "drna_mc_run: proposal failed (unbalanced structure in the state, or a bad design problem)"; return fail; }
+  if (fail != DRNA_OK) { e->err = std::string(who) + ": proposal failed (unbalanced structure in the state, or a bad design problem)"; return fail; }
   static const bool mc_profile = getenv("DRNA_MC_PROFILE") != nullptr;     // diagnostics: where an iteration's host time goes (stderr)
   double prof[3] = {0, 0, 0};
   auto now_us = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; };
   for (int it = 0; it < n_iter; it++) {
     const double tp0 = mc_profile ? now_us() : 0.0;
-    int rc = drna_score_batch(e, R, L, prop.data(), flags | DRNA_NEED_PF | DRNA_NEED_MFE | DRNA_NEED_EVAL, pEpf.data(), pEmfe.data(),
-                              pss.data(), pEd.data());
+    const int rc = score_all(prop.data());
     if (rc != DRNA_OK) return rc;
     const double tp1 = mc_profile ? now_us() : 0.0;
-    if (want_edef) {                        // inside + outside recursion of every proposal (fold_outside.hpp)
-      rc = drna_ensemble_defect_batch(e, R, L, prop.data(), pEdef.data(), nullptr);
-      if (rc != DRNA_OK) return rc;
-    }
     for (int r = 0; r < R; r++) {
       // SimScore of the proposal's structure against the target (utils/sim_score.py:62-147)
       int* ppq = prop_pq.data() + (size_t)r * L;
-      const bool same_ss = std::memcmp(pss.data() + (size_t)r * L, mfe_ss + (size_t)r * L, (size_t)L) == 0;
+      const bool same_ss = std::memcmp(S.ss.data() + (size_t)r * L, mfe_ss + (size_t)r * L, (size_t)L) == 0;
       SimMetrics m = cur_m[r];
-      if (!same_ss) {
-        if (!pair_table(pss.data() + (size_t)r * L, L, ppq)) { fail = DRNA_ERR_STRUCTURE; continue; }
-        m = sim_metrics(pr, ppq, L);
-      }
-      const double ed = pEd[(size_t)r * nt] / 100.0;
+      if (!same_ss && !metrics(S.ss.data() + (size_t)r * L, ppq, m)) { fail = DRNA_ERR_STRUCTURE; continue; }
+      const double ed = S.ed[r];
       // -sf terms (utils/energy_scores.py:376-398): 0 Ed-Epf, 1 1-MCC, 2 sln_Epf, 3 Ed-MFE, 4 1-precision, 5 1-recall, 6 Edef
       double tot = 0.0;
       for (int k = 0; k < n_terms; k++) {
         double v = 0.0;
         switch (term_id[k]) {
-          case 0: v = ed - pEpf[r]; break;
+          case 0: v = ed - S.Epf[r]; break;
           case 1: v = (1 - m.mcc) * 10; break;
-          case 2: v = (pEpf[r] + 0.3759 * L + 5.7534) / 10; break;
-          case 3: v = ed - pEmfe[r] / 100.0; break;
+          case 2: v = (S.Epf[r] + 0.3759 * L + 5.7534) / 10; break;
+          case 3: v = ed - S.Emfe[r]; break;
           case 4: v = (1 - m.precision) * 10; break;
           case 5: v = (1 - m.recall) * 10; break;
-          case 6: v = pEdef[r]; break;
+          case 6: v = S.edef[r]; break;
         }
         tot += v * term_w[k];
       }
-      if (nt > 1) {                                           // alternative structures (:98-102)
-        double sum = 0.0;
-        for (int t = 1; t < nt; t++) sum += pEd[(size_t)r * nt + t] / 100.0;
-        tot += sum / (nt - 1) - pEpf[r];
-      }
+      if (S.has_add) tot += S.add[r];
       pscore[r] = tot; pmcc[r] = 1 - m.mcc;
       // Metropolis (utils/replica_exchange_monte_carlo.py:26-57): one draw from the replica's stream, only when the mutant is worse
       (void)drna_metropolis_batch(1, score + r, pscore.data() + r, temps + r, Lconst, rng_state + (size_t)r * RNG_WORDS, acc.data() + r,
@@ -1714,16 +1776,17 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
       if (acc[r]) {
         std::memcpy(seqs + (size_t)r * L, prop.data() + (size_t)r * L, (size_t)L);
         if (!same_ss) {
-          std::memcpy(mfe_ss + (size_t)r * L, pss.data() + (size_t)r * L, (size_t)L);
+          std::memcpy(mfe_ss + (size_t)r * L, S.ss.data() + (size_t)r * L, (size_t)L);
           std::memcpy(cur_pq.data() + (size_t)r * L, ppq, (size_t)L * sizeof(int));
           cur_m[r] = m;
           refresh_pool(r);
         }
-        score[r] = pscore[r]; mcc1[r] = pmcc[r]; Epf[r] = pEpf[r]; Ed[r] = ed;
+        score[r] = pscore[r]; mcc1[r] = pmcc[r]; Epf[r] = S.Epf[r]; Ed[r] = ed;
+        if (xs0) { xs0[r] = S.x0[r]; xs1[r] = S.x1[r]; }
       }
     }
     if (it + 1 < n_iter && fail == DRNA_OK) propose_all();          // the next iteration's proposals (same streams, after the Metropolis draw)
-    if (fail != DRNA_OK) { e->err = "drna_mc_run: unbalanced MFE structure from the engine, or a failed proposal"; return fail; }
+    if (fail != DRNA_OK) { e->err = std::string(who) + ": unbalanced MFE structure from the engine, or a failed proposal"; return fail; }
     const double tp2 = mc_profile ? now_us() : 0.0;
     // counters and the best state, replica by replica in replica order (first strictly better wins)
     for (int r = 0; r < R; r++) {
@@ -1732,6 +1795,7 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
         if (better[r]) counters[1]++;
         if (mcc1[r] < best[0] || (mcc1[r] == best[0] && score[r] < best[1])) {
           best[0] = mcc1[r]; best[1] = score[r]; best[2] = Epf[r]; best[3] = Ed[r];
+          if (xs0) { best[4] = xs0[r]; best[5] = xs1[r]; }
           std::memcpy(best_seq, seqs + (size_t)r * L, (size_t)L);
           std::memcpy(best_ss, mfe_ss + (size_t)r * L, (size_t)L);
         }
@@ -1740,7 +1804,176 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
     if (mc_profile) { prof[0] += tp1 - tp0 - e->timing[3] * 1e3; prof[1] += tp2 - tp1; prof[2] += now_us() - tp2; }
   }
   if (mc_profile && n_iter > 0)
-    fprintf(stderr, "drna_mc_run: per iteration, host us: score call beyond device time %.1f, per-replica work %.1f, bookkeeping %.1f\n",
+    fprintf(stderr, "%s: per iteration, host us: score call beyond device time %.1f, per-replica work %.1f, bookkeeping %.1f\n", who,
             prof[0] / n_iter, prof[1] / n_iter, prof[2] / n_iter);
   return DRNA_OK;
+}
+
+// the -sf term ids of the loop; sets *want_edef when the ensemble defect (term 6, utils/energy_scores.py:362-374,397-398) is among them
+static int mc_terms(drna_engine* e, const char* who, int n_terms, const int32_t* term_id, bool* want_edef) {
+  *want_edef = false;
+  for (int k = 0; k < n_terms; k++) {
+    *want_edef |= term_id[k] == 6;
+    if (term_id[k] < 0 || term_id[k] > 6) { e->err = std::string(who) + ": unknown scoring term"; return DRNA_ERR_ARG; }
+  }
+  return DRNA_OK;
+}
+
+extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char* target, const int32_t* partner,
+                           const unsigned char* allowed_mask, const int32_t* snake_of, int n_snakes, const int32_t* snake_off,
+                           const int32_t* snake_nodes, const int32_t* snake_nstates, const char* snake_states,
+                           const int32_t* shelf_index, int n_shelves, double tm_max, double tm_min, int targeted,
+                           const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w,
+                           uint32_t flags, uint32_t* rng_state, char* seqs, char* mfe_ss, double* score, double* mcc1,
+                           double* Epf, double* Ed, int64_t* counters, char* best_seq, char* best_ss, double* best) {
+  using namespace drna_host;
+  if (!e) return DRNA_ERR_ARG;
+  if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || n_iter < 0 || !target || !allowed_mask || !shelf_index || !temps ||
+      n_terms < 1 || !term_id || !term_w || !rng_state || !seqs || !mfe_ss || !score || !mcc1 || !Epf || !Ed || !counters ||
+      !best_seq || !best_ss || !best || e->n_targets < 1 || e->L_targets != L) {
+    e->err = "drna_mc_run: bad argument (targets installed with drna_set_targets for this L; every state array given)";
+    return DRNA_ERR_ARG;
+  }
+  const int nt = e->n_targets;
+  bool want_edef = false;
+  { const int rc = mc_terms(e, "drna_mc_run", n_terms, term_id, &want_edef); if (rc != DRNA_OK) return rc; }
+  McScored S;
+  S.ss.resize((size_t)R * L); S.Epf.resize(R); S.ed.resize(R); S.Emfe.resize(R);
+  if (want_edef) S.edef.resize(R);
+  S.has_add = nt > 1;
+  if (S.has_add) S.add.resize(R);
+  std::vector<int32_t> pEmfe(R), pEd((size_t)R * nt);
+  ProposeCtx ctx;
+  {
+    const int rc = propose_ctx_init(ctx, L, target, partner, allowed_mask, n_snakes > 0 ? snake_of : nullptr, snake_off, snake_nodes,
+                                    snake_nstates, snake_states, n_shelves, tm_max, tm_min, targeted);
+    if (rc != DRNA_OK) { e->err = rc == DRNA_ERR_STRUCTURE ? "drna_mc_run: unbalanced target structure" : "drna_mc_run: proposal failed"; return rc; }
+  }
+  const int* pr = ctx.pt.data();
+  auto score_all = [&](const char* prop) -> int {
+    int rc = drna_score_batch(e, R, L, prop, flags | DRNA_NEED_PF | DRNA_NEED_MFE | DRNA_NEED_EVAL, S.Epf.data(), pEmfe.data(),
+                              S.ss.data(), pEd.data());
+    if (rc != DRNA_OK) return rc;
+    if (want_edef) {                        // inside + outside recursion of every proposal (fold_outside.hpp)
+      rc = drna_ensemble_defect_batch(e, R, L, prop, S.edef.data(), nullptr);
+      if (rc != DRNA_OK) return rc;
+    }
+    for (int r = 0; r < R; r++) {
+      S.ed[r] = pEd[(size_t)r * nt] / 100.0;
+      S.Emfe[r] = pEmfe[r] / 100.0;
+      if (nt > 1) {                                           // alternative structures (:98-102)
+        double sum = 0.0;
+        for (int t = 1; t < nt; t++) sum += pEd[(size_t)r * nt + t] / 100.0;
+        S.add[r] = sum / (nt - 1) - S.Epf[r];
+      }
+    }
+    return DRNA_OK;
+  };
+  auto metrics = [&](const char* ss, int* pq, SimMetrics& m) {
+    if (!pair_table(ss, L, pq)) return false;
+    m = sim_metrics(pr, pq, L);
+    return true;
+  };
+  return mc_loop(e, "drna_mc_run", R, L, n_iter, ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs,
+                 mfe_ss, score, mcc1, Epf, Ed, nullptr, nullptr, counters, best_seq, best_ss, best, S, score_all, metrics);
+}
+
+// reference utils/dimer_multichain_energy.py:24-45: fraction of strands bound in the dimer at 1 mM, and -kT ln of a fraction
+static double oligo_fraction(double FA, double FB, double FcAB) {
+  const double KB = 0.001987204259, RHO = 55.14, TEMP = 273.15 + 37, CONC = 1e-3;
+  const double dF = FcAB - FA - FB;
+  const double rhs = CONC / RHO * std::exp(-dF / (KB * TEMP));
+  return 1 - (std::sqrt(1 + 4 * rhs) - 1) / (2 * rhs);
+}
+static double kT_log(double x) { return -0.001987204259 * (273.15 + 37) * std::log(x); }
+
+extern "C" int drna_mc_run_cofold(drna_engine* e, int R, int L, int cut, int n_iter, const char* target, const unsigned char* allowed_mask,
+                                  int oligo_state, const int32_t* shelf_index, int n_shelves, double tm_max, double tm_min,
+                                  int targeted, const double* temps, double Lconst, int n_terms, const int32_t* term_id,
+                                  const double* term_w, uint32_t* rng_state, char* seqs, char* mfe_ss, double* score, double* mcc1,
+                                  double* Epf, double* Ed, double* oligo_frac, double* bonus, int64_t* counters, char* best_seq,
+                                  char* best_ss, double* best) {
+  using namespace drna_host;
+  if (!e) return DRNA_ERR_ARG;
+  const char* who = "drna_mc_run_cofold";
+  const int Ls = L + 1;                      // the state strings carry the '&' at column cut
+  if (R < 1 || R > e->max_R || L < 2 || L > e->max_L || n_iter < 0 || !target || !allowed_mask || !shelf_index || !temps ||
+      n_terms < 1 || !term_id || !term_w || !rng_state || !seqs || !mfe_ss || !score || !mcc1 || !Epf || !Ed || !oligo_frac || !bonus ||
+      !counters || !best_seq || !best_ss || !best || (oligo_state != 1 && oligo_state != 2)) {
+    e->err = std::string(who) + ": bad argument (R, L within the engine's limits; oligo_state 1 or 2; every state array given)";
+    return DRNA_ERR_ARG;
+  }
+  if (cut < 1 || cut > L - 1 || target[cut] != '&') {
+    e->err = std::string(who) + ": cut outside [1, L - 1], or the target's '&' is not at column cut";
+    return DRNA_ERR_ARG;
+  }
+  int rc = need_targets(e, who, L);
+  if (rc == DRNA_OK) rc = fits_workspace(e, who, R);
+  bool want_edef = false;
+  if (rc == DRNA_OK) rc = mc_terms(e, who, n_terms, term_id, &want_edef);
+  if (rc != DRNA_OK) return rc;
+  const int nt = e->n_targets;
+  McScored S;
+  S.ss.resize((size_t)R * Ls); S.Epf.resize(R); S.ed.resize(R); S.Emfe.resize(R); S.add.resize(R); S.x0.resize(R); S.x1.resize(R);
+  S.has_add = true;
+  if (want_edef) S.edef.resize(R);
+  std::vector<char> flat(want_edef ? (size_t)R * L : 0);
+  ProposeCtx ctx;
+  rc = propose_ctx_init(ctx, Ls, target, nullptr, allowed_mask, nullptr, nullptr, nullptr, nullptr, nullptr, n_shelves, tm_max, tm_min,
+                        targeted);
+  if (rc == DRNA_OK) rc = propose_ctx_two_strands(ctx, target, oligo_state);
+  if (rc != DRNA_OK || ctx.amp != cut) {
+    e->err = rc == DRNA_ERR_STRUCTURE ? std::string(who) + ": unbalanced target structure" : std::string(who) + ": bad design problem";
+    return rc != DRNA_OK ? rc : DRNA_ERR_ARG;
+  }
+  // oligomer bonus for a hetero-dimer or a homodimer of two different sub-structures, else the monomer-fraction term
+  // (utils/energy_scores.py:110-118)
+  const bool oligomer = oligo_state == 1 || !ctx.ss_equal;
+  // SimScore with the reference's '&' -> "Ee" substitution (utils/energy_scores.py:79): the nick becomes a pair of its own in the
+  // target and in every structure, so the compared strings are one longer than the state strings
+  std::vector<char> xs(Ls + 1);
+  std::vector<int> xr(Ls + 1), xq(Ls + 1);
+  auto expand = [&](const char* ss) {
+    std::memcpy(xs.data(), ss, (size_t)cut);
+    xs[cut] = 'E'; xs[cut + 1] = 'e';
+    std::memcpy(xs.data() + cut + 2, ss + cut + 1, (size_t)(Ls - cut - 1));
+  };
+  expand(target);
+  if (!pair_table(xs.data(), Ls + 1, xr.data())) { e->err = std::string(who) + ": unbalanced target structure"; return DRNA_ERR_STRUCTURE; }
+  auto metrics = [&](const char* ss, int* pq, SimMetrics& m) {
+    if (ss[cut] != '&' || !pair_table(ss, Ls, pq)) return false;
+    expand(ss);
+    if (!pair_table(xs.data(), Ls + 1, xq.data())) return false;
+    m = sim_metrics(xr.data(), xq.data(), Ls + 1);
+    return true;
+  };
+  auto score_all = [&](const char* prop) -> int {
+    for (int r = 0; r < R; r++) {             // the letters of both strands, without the '&', straight into the mapped buffer
+      std::memcpy(e->hm_seqs + (size_t)r * L, prop + (size_t)r * Ls, (size_t)cut);
+      std::memcpy(e->hm_seqs + (size_t)r * L + cut, prop + (size_t)r * Ls + cut + 1, (size_t)(L - cut));
+    }
+    if (want_edef) std::memcpy(flat.data(), e->hm_seqs, (size_t)R * L);
+    int rc2 = cofold_batch_mapped(e, R, L, cut, true, true, true);
+    if (rc2 != DRNA_OK) return rc2;
+    for (int r = 0; r < R; r++) {
+      const double* F = e->hm_F4 + (size_t)4 * r;
+      S.Epf[r] = F[3];
+      S.ed[r] = e->hm_Ed[(size_t)r * nt] / 100.0;
+      S.Emfe[r] = e->hm_Emfe[r] / 100.0;
+      char* o = S.ss.data() + (size_t)r * Ls;
+      std::memcpy(o, e->hm_ss + (size_t)r * L, (size_t)cut);
+      o[cut] = '&';
+      std::memcpy(o + cut + 1, e->hm_ss + (size_t)r * L + cut, (size_t)(L - cut));
+      S.x0[r] = oligo_fraction(F[0], F[1], F[2]);
+      S.x1[r] = oligomer ? kT_log(S.x0[r]) : kT_log(1 - S.x0[r]);
+      S.add[r] = S.x1[r];
+    }
+    if (want_edef) {                          // inside + outside recursion under the co-fold rules (fold_cofold_outside.hpp)
+      rc2 = drna_cofold_ensemble_defect_batch(e, R, L, cut, flat.data(), S.edef.data(), nullptr);
+      if (rc2 != DRNA_OK) return rc2;
+    }
+    return DRNA_OK;
+  };
+  return mc_loop(e, who, R, Ls, n_iter, ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs, mfe_ss,
+                 score, mcc1, Epf, Ed, oligo_frac, bonus, counters, best_seq, best_ss, best, S, score_all, metrics);
 }

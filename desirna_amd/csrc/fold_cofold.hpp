@@ -58,21 +58,17 @@ __device__ __forceinline__ int co_endstem(const int* mm, const SM& sm, int t, bo
   return 0;
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT) void cofold_mfe_kernel(CoArgs A) {
-  __shared__ CoMfeSmem sm;
+// fill + traceback of pair r by the calling workgroup.  The three tables (Wc, FML diagonal-major, EXT by (j, i); pitch ld >= n + 2,
+// n + 1 rows) live where the caller put them: in the pair's workspace slot (cofold_mfe_kernel) or in LDS (fold_cofold_lds.hpp);
+// sm is the kernel's shared memory with the members of CoMfeSmem
+template <int NT, class SM>
+__device__ __forceinline__ void cofold_mfe_body(SM& sm, const CoArgs& A, int r, int32_t* Wc, int32_t* FML, int32_t* EXT, int ld) {
   const MfeTables& T = *A.T;
   const Plan& P = *A.plan;
-  const int r = blockIdx.x;
-  const int n = A.L, cut = A.cut, ld = A.ld;
+  const int n = A.L, cut = A.cut;
   const int tid = threadIdx.x, lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
   const int INF = INF_DEV, HALF = INF_DEV / 2;
-  int32_t* base = A.wsm + (long long)r * A.wsm_stride;
-  const long long tab = (long long)ld * ld;
-  int32_t* Wc = base;
-  int32_t* FML = base + tab;
-  int32_t* EXT = base + 2 * tab;
 
   stage_energy_tables<NT>(sm, T, tid);
   for (int k = tid; k < n; k += NT) sm.ssw[k] = '.';
@@ -348,6 +344,15 @@ __global__ __launch_bounds__(NT) void cofold_mfe_kernel(CoArgs A) {
   if (lane == 0) A.status[r] = ok ? ST_OK : ST_TRACEBACK;
 }
 
+template <int NT>
+__global__ __launch_bounds__(NT) void cofold_mfe_kernel(CoArgs A) {
+  __shared__ CoMfeSmem sm;
+  const int r = blockIdx.x;
+  int32_t* base = A.wsm + (long long)r * A.wsm_stride;
+  const long long tab = (long long)A.ld * A.ld;
+  cofold_mfe_body<NT>(sm, A, r, base, base + tab, base + 2 * tab, A.ld);
+}
+
 // ---------------------------------------------------------------- partition function
 
 struct CoPfSmem : PfSmem {
@@ -356,7 +361,8 @@ struct CoPfSmem : PfSmem {
 
 // Boltzmann factor of the interior loop (u1,u2) between a pair of type t and the inner pair given by its info byte,
 // scale[u1+u2+2] included
-__device__ __forceinline__ double co_pf_intloop(const PfSmem& sm, const PfTables& T, const double* scale, int u1, int u2, int t,
+template <class SM>
+__device__ __forceinline__ double co_pf_intloop(const SM& sm, const PfTables& T, const double* scale, int u1, int u2, int t,
                                                 int si1, int sj1, int info) {
   const int t2 = info >> 4, sq1 = (info >> 2) & 3, sp1 = info & 3;
   const int nl = u1 > u2 ? u1 : u2, ns = u1 > u2 ? u2 : u1;
@@ -381,28 +387,24 @@ __device__ __forceinline__ double co_pf_intloop(const PfSmem& sm, const PfTables
   return T.interior[nl + ns] * T.eninio[nl - ns] * sm.mmI[t * 16 + si1 * 4 + sj1] * sm.mmI[info] * sc;
 }
 
-__device__ __forceinline__ double co_pf_endstem(const double* mm, const PfSmem& sm, int t, bool h5, int s5, bool h3, int s3) {
+template <class SM>
+__device__ __forceinline__ double co_pf_endstem(const double* mm, const SM& sm, int t, bool h5, int s5, bool h3, int s3) {
   if (h5 && h3) return mm[t * 16 + s5 * 4 + s3];
   if (h5) return sm.d5[t * 4 + s5];
   if (h3) return sm.d3[t * 4 + s3];
   return 1.0;
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT) void cofold_pf_kernel(CoArgs A) {
-  __shared__ CoPfSmem sm;
+// partition function of pair r by the calling workgroup; QB, QM, QM1 (doubles) and INFO (bytes), diagonal-major with pitch
+// ld >= n + 2, live where the caller put them (workspace slot or LDS); sm holds the members of CoPfSmem
+template <int NT, class SM>
+__device__ __forceinline__ void cofold_pf_body(SM& sm, const CoArgs& A, int r, double* QB, double* QM, double* QM1, unsigned char* INFO,
+                                               int ld) {
   const PfTables& T = *A.F;
   const Plan& P = *A.plan;
-  const int r = blockIdx.x;
-  const int n = A.L, cut = A.cut, ld = A.ld;
+  const int n = A.L, cut = A.cut;
   const int tid = threadIdx.x, lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
-  double* base = A.wsp + (long long)r * A.wsp_stride;
-  const long long tab = (long long)ld * ld;
-  double* QB = base;
-  double* QM = base + tab;
-  double* QM1 = base + 2 * tab;
-  unsigned char* INFO = reinterpret_cast<unsigned char*>(base + 3 * tab);
   int32_t* status = A.status_pf;
 
   stage_energy_tables<NT>(sm, T, tid);
@@ -544,6 +546,15 @@ __global__ __launch_bounds__(NT) void cofold_pf_kernel(CoArgs A) {
       out[3] = -kT * (log(QA * QB_ + QAB) + n * lsc);
     }
   }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void cofold_pf_kernel(CoArgs A) {
+  __shared__ CoPfSmem sm;
+  const int r = blockIdx.x;
+  double* base = A.wsp + (long long)r * A.wsp_stride;
+  const long long tab = (long long)A.ld * A.ld;
+  cofold_pf_body<NT>(sm, A, r, base, base + tab, base + 2 * tab, reinterpret_cast<unsigned char*>(base + 3 * tab), A.ld);
 }
 
 }  // namespace drna

@@ -59,7 +59,8 @@ struct PfSmem {
   f64x2 plan_pW[NPAIR_MAX];
 };
 
-__device__ __forceinline__ double pf_hairpin(const PfSmem& sm, const PfArgs& A, int i, int j, int t) {
+template <class SM>
+__device__ __forceinline__ double pf_hairpin(const SM& sm, const PfArgs& A, int i, int j, int t) {
   const PfTables& T = *A.T;
   const int u = j - i - 1;
   const double q = A.hp_w[u];

@@ -21,9 +21,10 @@ processes (it iterates over ``set`` objects of strings, whose order depends on P
 Alternative structures: "snake" moves (connected components of the pair graph of target + alternative structures
 switch between their Watson-Crick colourings) as in the reference (:143-388, :1081-1095).
 
-``-acgu on`` (weighted letter choices) is available in the Python driver (``DesignProblem(acgu=...)``).
+``-acgu on`` (weighted letter choices), ``-nd on``, ``-oa on`` and motifs are available in the Python driver (``run_design``).
 
-Not supported here (raises): ``-nd``.
+Two strands (hetero-dimer, ``-d on`` homodimer) run through both drivers; together with alternative structures through
+``run_design`` only.
 """
 import argparse
 import random
@@ -383,7 +384,7 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
 
 def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                     scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
-                    device=0, engine=None, keep_records=True, native_loop=None, shards=None, num_results=None):
+                    device=0, engine=None, keep_records=True, native_loop=None, shards=None, num_results=None, dimer="off"):
     """Same loop as :func:`run_design` with the per-replica host work in native code and no per-step Python objects:
     proposals, SimScore and Metropolis run batched in the C library, the replica state lives in numpy arrays.  The
     per-replica random streams are the reference's (MT19937 seeded with the replica index at every exchange step, CPython's
@@ -392,14 +393,21 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
     ``shards`` (``replica_exchange.ReplicaShards``): this rank holds replicas ``shards.local`` only (its engine needs
     ``max_R >= len(shards.local)``); per exchange step ONE all-gather carries the scores and the stop flags, every rank
     replays the swaps on the whole ladder.  Results do not depend on the sharding (streams are seeded by the GLOBAL
-    replica index and the kernels' results do not depend on the batch composition)."""
+    replica index and the kernels' results do not depend on the batch composition).
+
+    Two-strand targets (one ``&``; ``dimer="on"`` = homodimer, else hetero-dimer) take ``HostKernels.propose_co`` and
+    ``Engine.cofold_batch`` per iteration, or ``Engine.mc_run_cofold`` for the whole inner loop; their records carry the
+    ``oligo_fraction`` and ``oligomer_bonus`` :func:`run_design` writes.  Alternative structures with two strands raise."""
     from . import engine as _engine
     if stop_when_solved and num_results is not None and not keep_records:
         raise ValueError("the -sws rule with num_results ranks the recorded sequences: it needs keep_records=True "
                          "(without records the stop test could never fire and the run would only end at its step / time limit)")
     prob = DesignProblem(input_file.sec_struct, input_file.seq_restr, input_file.alt_sec_structs)
-    if prob.two_strands:
-        raise NotImplementedError("two-strand inputs run through run_design (the native batched proposer is one-strand)")
+    two = prob.two_strands
+    if two and input_file.alt_sec_structs:
+        raise NotImplementedError("two strands with alternative structures run through run_design (the native two-strand "
+                                  "proposer has no snake moves)")
+    oligo_state = ("homodimer" if dimer == "on" else "heterodimer") if two else "none"
     n_alt = len(input_file.alt_sec_structs) if input_file.alt_sec_structs else 0
     sf = es.parse_scoring_functions(scoring_f)
     for name, _ in sf:
@@ -408,19 +416,48 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
     shards = shards or rx.ReplicaShards(replicas, 0, 1)
     local = np.array(shards.local, dtype=np.int64)
     R, L, Rl = replicas, prob.n, len(shards.local)
-    eng = engine or _engine.Engine(max_R=max(1, Rl), max_L=L, device=device)
+    eng = engine or _engine.Engine(max_R=max(1, Rl), max_L=L - 1 if two else L, device=device)      # L counts the '&'
     hk = _engine.HostKernels()
-    eng.set_targets([input_file.sec_struct] + list(input_file.alt_sec_structs or []))
+    eng.set_targets([input_file.sec_struct.replace("&", "")] + list(input_file.alt_sec_structs or []))
     flags = _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL
     if set(input_file.sec_struct) - set(".()&"):
         flags |= _engine.NEED_PK
-    amask = np.array([sum(1 << "ACGU".index(c) for c in a) for a in prob.allowed], dtype=np.uint8)
     temps = np.array(rx.get_rep_temps(R, t_min, t_max), dtype=np.float64)      # the whole ladder, replayed on every rank
     shelves = temps.copy()
     main_rng = random.Random(shards.broadcast_seed(2137 + seed if seed else random.random()))
     ref_ss = input_file.sec_struct
+    if two:
+        ss1, ss2 = ref_ss.split("&")
+        oligomer = oligo_state == "heterodimer" or ss1 != ss2        # else the monomer-fraction term (reference :110-118)
+        cut = len(ss1)
+        want_edef = any(name == "Edef" for name, _ in sf)
+
+    def with_Ee(a):
+        """(R, L) uint8 strings with the '&' at column cut -> the reference's '&' -> 'Ee' substitution (R, L + 1)"""
+        return np.concatenate([a[:, :cut], np.full((len(a), 1), ord("E"), np.uint8), np.full((len(a), 1), ord("e"), np.uint8),
+                               a[:, cut + 1:]], axis=1)
+
+    def score_two(seqs_u8):
+        """ReplicaScorer._score_two_strands on arrays: (total, 1-MCC, structures, Epf = FAB, Ed, oligo_fraction, bonus)"""
+        seqs = [bytes(r).decode() for r in seqs_u8]
+        out = eng.cofold_batch(seqs, _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL)
+        ss = np.frombuffer("".join(out["mfe_ss"]).encode(), dtype=np.uint8).reshape(len(seqs), L).copy()
+        mcc, rec, prec = hk.simscore(ref_ss.replace("&", "Ee"), with_Ee(ss))
+        Epf = np.array(out["FAB"], dtype=np.float64)
+        ed = out["Ed"][:, 0] / 100.0
+        terms = {"Ed-Epf": lambda: ed - Epf, "1-MCC": lambda: (1 - mcc) * 10, "sln_Epf": lambda: (Epf + 0.3759 * L + 5.7534) / 10,
+                 "Ed-MFE": lambda: ed - out["Emfe"] / 100.0, "1-precision": lambda: (1 - prec) * 10,
+                 "1-recall": lambda: (1 - rec) * 10, "Edef": lambda: eng.cofold_ensemble_defect(seqs)}
+        total = np.zeros(len(seqs))
+        for name, w in sf:
+            total += terms[name]() * w
+        frac = np.array([float(es.oligo_fraction(out["FA"][k], out["FB"][k], out["FcAB"][k])) for k in range(len(seqs))])
+        bonus = np.array([float(es.kTlog_oligo_fraction(f) if oligomer else es.kTlog_monomer_fraction(f)) for f in frac])
+        return total + bonus, 1 - mcc, ss, Epf, ed, frac, bonus
 
     def score(seqs_u8):
+        if two:
+            return score_two(seqs_u8)
         Epf, Emfe, ss, Ed = eng.score_batch_arrays(seqs_u8, flags)
         mcc, rec, prec = hk.simscore(ref_ss, ss)
         ed = Ed[:, 0] / 100.0
@@ -442,14 +479,20 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                 total += eng.ensemble_defect_arrays(seqs_u8) * w
         if n_alt:                                                 # reference energy_scores.py:98-102
             total += Ed[:, 1:].sum(axis=1) / 100.0 / n_alt - Epf
-        return total, 1 - mcc, ss, Epf, ed
+        return total, 1 - mcc, ss, Epf, ed, None, None
 
     init = prob.initial_sequence(main_rng)
     cur = np.tile(np.frombuffer(init.encode(), dtype=np.uint8), (max(1, Rl), 1)).copy()
-    cur_score, cur_mcc, cur_ss, cur_epf, cur_ed = score(cur)
-    k0 = int(np.lexsort((cur_score, cur_mcc))[0])
-    best = dict(sequence=cur[k0].tobytes().decode(), mfe_ss=cur_ss[k0].tobytes().decode(), mcc=float(cur_mcc[k0]),
-                scoring_function=float(cur_score[k0]), Epf=float(cur_epf[k0]), edesired=float(cur_ed[k0]))
+    cur_score, cur_mcc, cur_ss, cur_epf, cur_ed, cur_frac, cur_bonus = score(cur)
+
+    def best_of(k):
+        b = dict(sequence=cur[k].tobytes().decode(), mfe_ss=cur_ss[k].tobytes().decode(), mcc=float(cur_mcc[k]),
+                 scoring_function=float(cur_score[k]), Epf=float(cur_epf[k]), edesired=float(cur_ed[k]))
+        if two:
+            b.update(oligo_fraction=float(cur_frac[k]), oligomer_bonus=float(cur_bonus[k]))
+        return b
+
+    best = best_of(int(np.lexsort((cur_score, cur_mcc))[0]))
     stats = dict(acc_mc=0, acc_mc_better=0, rej_mc=0, acc_re=0, rej_re=0, scored=Rl)
 
     def records(step_no):
@@ -465,6 +508,9 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
             sc.get_edesired_minus_Epf(sc.Epf, sc.edesired)
             sc.mcc = float(cur_mcc[k])
             sc.get_mfe_ss(cur_ss[k].tobytes().decode())
+            if two:
+                sc.oligo_fraction = float(cur_frac[k])
+                sc.oligomer_bonus = float(cur_bonus[k])
             out.append(dict(vars(sc)))
         return out
 
@@ -472,6 +518,8 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
     if native_loop is None:
         native_loop = True
     native_loop = native_loop and all(name in eng.TERM_IDS for name, _ in sf)   # (every -sf term, Edef included, has a native id)
+    if two:
+        cur_frac = np.ascontiguousarray(cur_frac, dtype=np.float64); cur_bonus = np.ascontiguousarray(cur_bonus, dtype=np.float64)
     cur = np.ascontiguousarray(cur); cur_ss = np.ascontiguousarray(cur_ss)
     cur_score = np.ascontiguousarray(cur_score, dtype=np.float64); cur_mcc = np.ascontiguousarray(cur_mcc, dtype=np.float64)
     cur_epf = np.ascontiguousarray(cur_epf, dtype=np.float64); cur_ed = np.ascontiguousarray(cur_ed, dtype=np.float64)
@@ -492,24 +540,38 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
         tl = temps[local] if Rl else temps[:1]
         shelf_idx = np.searchsorted(shelves, tl).astype(np.int32)
         if native_loop and Rl:
-            # the whole inner loop of the exchange step in native code (drna_mc_run): one call, no per-iteration Python
+            # the whole inner loop of the exchange step in native code (drna_mc_run[_cofold]): one call, no per-iteration Python
             state = dict(seqs=cur, mfe_ss=cur_ss, score=cur_score, mcc1=cur_mcc, Epf=cur_epf, Ed=cur_ed)
             counters = np.zeros(3, dtype=np.int64)
+            vals = [best["mcc"], best["scoring_function"], best["Epf"], best["edesired"]]
+            if two:
+                vals += [best["oligo_fraction"], best["oligomer_bonus"]]
+                state.update(oligo_fraction=cur_frac, bonus=cur_bonus)
             bst = dict(seq=np.frombuffer(best["sequence"].encode(), dtype=np.uint8).copy(),
-                       ss=np.frombuffer(best["mfe_ss"].encode(), dtype=np.uint8).copy(),
-                       vals=np.array([best["mcc"], best["scoring_function"], best["Epf"], best["edesired"]], dtype=np.float64))
-            eng.mc_run(prob, exchange, shelf_idx, R, tm_max, tm_min, targeted, np.ascontiguousarray(tl), sf, flags, rng_state, state,
-                       counters, bst)
+                       ss=np.frombuffer(best["mfe_ss"].encode(), dtype=np.uint8).copy(), vals=np.array(vals, dtype=np.float64))
+            if two:
+                eng.mc_run_cofold(prob, oligo_state, exchange, shelf_idx, R, tm_max, tm_min, targeted, np.ascontiguousarray(tl), sf,
+                                  rng_state, state, counters, bst)
+            else:
+                eng.mc_run(prob, exchange, shelf_idx, R, tm_max, tm_min, targeted, np.ascontiguousarray(tl), sf, flags, rng_state,
+                           state, counters, bst)
             best = dict(sequence=bst["seq"].tobytes().decode(), mfe_ss=bst["ss"].tobytes().decode(), mcc=float(bst["vals"][0]),
                         scoring_function=float(bst["vals"][1]), Epf=float(bst["vals"][2]), edesired=float(bst["vals"][3]))
+            if two:
+                best.update(oligo_fraction=float(bst["vals"][4]), oligomer_bonus=float(bst["vals"][5]))
             stats["acc_mc"] += int(counters[0]); stats["acc_mc_better"] += int(counters[1]); stats["rej_mc"] += int(counters[2])
             stats["scored"] += Rl * exchange
         for _ in range(0 if (native_loop or not Rl) else exchange):
-            prop = hk.propose_alt(prob, cur, cur_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
-            p_score, p_mcc, p_ss, p_epf, p_ed = score(prop)
+            if two:
+                prop = hk.propose_co(prob, oligo_state, cur, cur_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
+            else:
+                prop = hk.propose_alt(prob, cur, cur_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
+            p_score, p_mcc, p_ss, p_epf, p_ed, p_frac, p_bonus = score(prop)
             acc, better = hk.metropolis(cur_score, p_score, tl, rng_state)
             cur[acc] = prop[acc]; cur_ss[acc] = p_ss[acc]
             cur_score[acc] = p_score[acc]; cur_mcc[acc] = p_mcc[acc]; cur_epf[acc] = p_epf[acc]; cur_ed[acc] = p_ed[acc]
+            if two:
+                cur_frac[acc] = p_frac[acc]; cur_bonus[acc] = p_bonus[acc]
             na = int(acc.sum())
             stats["acc_mc"] += na
             stats["acc_mc_better"] += int((acc & better).sum())
@@ -518,12 +580,11 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
             # the best state is tracked replica by replica in replica order, like the native loop (first strictly better wins)
             for kb in np.nonzero(acc)[0]:
                 if (cur_mcc[kb], cur_score[kb]) < (best["mcc"], best["scoring_function"]):
-                    best = dict(sequence=cur[kb].tobytes().decode(), mfe_ss=cur_ss[kb].tobytes().decode(), mcc=float(cur_mcc[kb]),
-                                scoring_function=float(cur_score[kb]), Epf=float(cur_epf[kb]), edesired=float(cur_ed[kb]))
+                    best = best_of(kb)
         # ONE collective per exchange step: scores + (solved, time is up); rank 0's clock decides the time limit
         ctl = [float(bool(Rl) and bool((cur_mcc[:Rl] == 0.0).any())), float(time.time() - t_start >= timelimit), 0.0]
         if stop_when_solved and num_results is not None and keep_records and step % 10 == 0:      # the reference's -sws rule
-            ctl[2] = float(_sws_reached(simulation_data + records(step * exchange), num_results, "none"))
+            ctl[2] = float(_sws_reached(simulation_data + records(step * exchange), num_results, oligo_state))
         all_scores, ex = shards.allgather_scores(cur_score[:Rl], extras=ctl)
         solved = solved or bool(ex[:, 0].any())
         new_temps, a, _, rj = rx.replica_exchange(list(temps), list(all_scores), step, main_rng)
@@ -585,8 +646,11 @@ def main(argv=None):
                     "_stats, _best_str, fasta files) into this directory")
     a = ap.parse_args(argv)
     inp = read_input(a.name)
-    two = "&" in inp.sec_struct or a.oligo == "on" or a.percs == "on" or a.subopt == "on"
-    extra = dict(dimer=a.dimer, oligo=a.oligo, subopt=a.subopt) if two else {}
+    strands2 = "&" in inp.sec_struct
+    # the Python driver's own features: -oa, -acgu, -nd, and two strands together with alternative structures
+    two = a.oligo == "on" or a.percs == "on" or a.subopt == "on" or (strands2 and bool(inp.alt_sec_structs))
+    extra = dict(dimer=a.dimer, oligo=a.oligo, subopt=a.subopt) if (two or (strands2 and a.python_host)) else \
+        (dict(dimer=a.dimer) if strands2 else {})
     if a.percs == "on":
         vals = [int(x) for x in a.acgu_content.split(",")] if a.acgu_content else [15, 30, 30, 15]
         if sum(vals) != 100:

@@ -54,6 +54,9 @@ _SIGNATURES = {
     "drna_propose_batch_alt": (_ci, [_ci, _ci, _str, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci,
                                      _vp, _vp]),
     "drna_metropolis_batch": (_ci, [_ci, _vp, _vp, _vp, _dbl, _vp, _vp, _vp]),
+    "drna_propose_batch_co": (_ci, [_ci, _ci, _str, _vp, _ci, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci, _vp, _vp]),
+    "drna_mc_run_cofold": (_ci, [_vp, _ci, _ci, _ci, _ci, _str, _vp, _ci, _vp, _ci, _dbl, _dbl, _ci, _vp, _dbl, _ci, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "drna_rng_seed": (_ci, [_ci, _vp, _vp]),
     "drna_rng_random": (_ci, [_ci, _vp, _vp]),
 }
@@ -62,6 +65,13 @@ EXPORTS = tuple(_SIGNATURES)
 ABI_VERSION = 3        # DRNA_ABI_VERSION this binding was written against (include/desirna_amd.h)
 
 RNG_WORDS = 625        # DRNA_RNG_WORDS: uint32 words of one replica's MT19937 stream
+
+OLIGO_STATES = {"heterodimer": 1, "homodimer": 2}      # oligo_state of drna_propose_batch_co / drna_mc_run_cofold
+
+
+def co_allowed_mask(prob):
+    """allowed-letter mask of a two-strand design.DesignProblem for the native proposer: bit0 A .. bit3 U, 0 for the '&' column"""
+    return np.array([sum(1 << "ACGU".index(c) for c in a if c != "&") for a in prob.allowed], dtype=np.uint8)
 
 
 class EngineError(RuntimeError):
@@ -283,6 +293,28 @@ class Engine:
                                         p(rng_state), p(state["seqs"]), p(state["mfe_ss"]), p(state["score"]), p(state["mcc1"]),
                                         p(state["Epf"]), p(state["Ed"]), p(counters), p(best["seq"]), p(best["ss"]), p(best["vals"])))
 
+    def mc_run_cofold(self, prob, oligo_state, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state,
+                      state, counters, best, L_const=504.12):
+        """:meth:`mc_run` for a two-strand ``design.DesignProblem`` (drna_mc_run_cofold).  The strings of `state` (seqs, mfe_ss:
+        uint8 R x (L + 1)) and of `best` carry the '&'; `state` also holds oligo_fraction and bonus (float64 R), `best["vals"]` six
+        values (1-MCC, score, Epf, Ed, oligo_fraction, bonus); set_targets() holds the target without the '&'."""
+        R, Ls = state["seqs"].shape
+        cut = prob.sec_struct.index("&")
+        assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
+        assert best["vals"].shape == (6,)
+        am = co_allowed_mask(prob)
+        ids = np.array([self.TERM_IDS[n] for n, _ in scoring_f], dtype=np.int32)
+        ws = np.array([w for _, w in scoring_f], dtype=np.float64)
+        sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
+        tt = np.ascontiguousarray(temps, dtype=np.float64)
+        p = lambda a: a.ctypes.data
+        self._check(self._L.drna_mc_run_cofold(self._h, R, Ls - 1, cut, int(n_iter), prob.sec_struct.encode("ascii"), p(am),
+                                               OLIGO_STATES[oligo_state], p(sh), int(n_shelves), float(tm_max), float(tm_min),
+                                               int(bool(targeted)), p(tt), float(L_const), len(ids), p(ids), p(ws), p(rng_state),
+                                               p(state["seqs"]), p(state["mfe_ss"]), p(state["score"]), p(state["mcc1"]),
+                                               p(state["Epf"]), p(state["Ed"]), p(state["oligo_fraction"]), p(state["bonus"]),
+                                               p(counters), p(best["seq"]), p(best["ss"]), p(best["vals"])))
+
     def subopt_energy(self, seqs, want_both=False):
         """Energy (dcal/mol) of the second-best structure of each sequence as the reference's -nd on path takes it from
         ViennaRNA's subopt (0 if none within 49 kcal/mol); with want_both also the (R, 2) array of the two lowest energies."""
@@ -460,6 +492,23 @@ class HostKernels:
                                             rng_state.ctypes.data, out.ctypes.data)
         if rc != 0:
             raise EngineError(rc, "drna_propose_batch_alt")
+        return out
+
+    def propose_co(self, prob, oligo_state, seqs_u8, ss_u8, shelf_index, n_shelves, tm_max, tm_min, targeted, rng_state):
+        """Proposals for a two-strand ``design.DesignProblem`` (drna_propose_batch_co): the strings keep the '&';
+        oligo_state "heterodimer" or "homodimer" (the reference's strand-copy rules follow every move)."""
+        s = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
+        R, L = s.shape
+        out = np.empty_like(s)
+        ss = np.ascontiguousarray(ss_u8, dtype=np.uint8)
+        am = co_allowed_mask(prob)
+        sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
+        assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
+        rc = self._L.drna_propose_batch_co(R, L, prob.sec_struct.encode("ascii"), am.ctypes.data, OLIGO_STATES[oligo_state],
+                                           s.ctypes.data, ss.ctypes.data, sh.ctypes.data, int(n_shelves), float(tm_max),
+                                           float(tm_min), int(bool(targeted)), rng_state.ctypes.data, out.ctypes.data)
+        if rc != 0:
+            raise EngineError(rc, "drna_propose_batch_co")
         return out
 
     def metropolis(self, score_o, score_m, temps, rng_state, L_const=504.12):

@@ -216,6 +216,8 @@ int drna_last_edef_timing(const drna_engine *e, float out[2]);
  * (min,+) tile products); results are identical either way.
  * "mfe_split" (default 2): with pseudoknot rounds the strip path takes a fill launch and a traceback launch per round; a batch of
  * >= 32 sequences then goes in two halves on two streams so that one half's traceback runs under the other's fill; 1 = one part.
+ * "cofold_lds" (default 1): drna_cofold_batch and drna_mc_run_cofold fold pairs of at most 64 nt ("cofold_lds_max" reads the bound)
+ * with every table in LDS (fold_cofold_lds.hpp); 0 = the general co-fold kernels.  Results are bit-identical either way.
  */
 int drna_set_option(drna_engine *e, const char *name, int value);
 
@@ -314,6 +316,36 @@ int drna_mc_run(drna_engine *e, int R, int L, int n_iter, const char *target, co
                 double Lconst, int n_terms, const int32_t *term_id, const double *term_w, uint32_t flags,
                 uint32_t *rng_state, char *seqs, char *mfe_ss, double *score, double *mcc1, double *Epf, double *Ed,
                 int64_t *counters, char *best_seq, char *best_ss, double *best);
+
+/*
+ * Two strands.  drna_propose_batch_co: the move set of drna_propose_batch for targets that contain one '&' (the reference's
+ * hetero-dimer and homodimer modes).  Every string (target, seqs, mfe_ss, out_seqs; L chars) keeps the '&' at the target's
+ * column as a fixed, unpaired letter: positions, the +-3 window and its bounds and the draw counts include it, and a targeted
+ * move that lands on it (or on another fixed position) changes nothing after the same draws.  allowed_mask of the '&' column is 0.
+ *   oligo_state   1 hetero-dimer, 2 homodimer: the reference's strand-copy rules follow every move (utils/sequence_utils.py:
+ *                 1104-1126): two equal sub-structures -- the strand that changed is copied over the other; two different ones --
+ *                 the two ends of a pair move are crossed over between the strands
+ */
+int drna_propose_batch_co(int R, int L, const char *target, const unsigned char *allowed_mask, int oligo_state,
+                          const char *seqs, const char *mfe_ss, const int32_t *shelf_index, int n_shelves, double tm_max,
+                          double tm_min, int targeted, uint32_t *rng_state, char *out_seqs);
+
+/*
+ * drna_mc_run_cofold: drna_mc_run for a two-strand target.  L = nucleotides of both strands, cut = length of the first; the
+ * state strings (target, seqs, mfe_ss, best_seq, best_ss) have L + 1 chars with the '&' at column cut; drna_set_targets holds
+ * the target without it.  Scoring step of the reference's two-strand branch (utils/energy_scores.py:70-118): co-fold MFE +
+ * traceback, partition function and two-strand evaluation of the R proposals (pairs of at most 64 nt with their tables in LDS,
+ * option "cofold_lds"); Epf = FAB; SimScore with the '&' -> "Ee" substitution; the -sf terms of drna_mc_run (Ed-MFE against the
+ * co-fold MFE, Edef in the co-fold ensemble); oligo_fraction from FA, FB, FcAB; then -kT ln(oligo_fraction) for a hetero-dimer or
+ * a homodimer of two different sub-structures, -kT ln(1 - oligo_fraction) for two equal ones, added after the -sf sum.
+ *   in/out per replica: as drna_mc_run, and oligo_frac, bonus (R doubles)
+ *   best[6] = {1-MCC, score, Epf, Ed, oligo_fraction, bonus}
+ */
+int drna_mc_run_cofold(drna_engine *e, int R, int L, int cut, int n_iter, const char *target, const unsigned char *allowed_mask,
+                       int oligo_state, const int32_t *shelf_index, int n_shelves, double tm_max, double tm_min, int targeted,
+                       const double *temps, double Lconst, int n_terms, const int32_t *term_id, const double *term_w,
+                       uint32_t *rng_state, char *seqs, char *mfe_ss, double *score, double *mcc1, double *Epf, double *Ed,
+                       double *oligo_frac, double *bonus, int64_t *counters, char *best_seq, char *best_ss, double *best);
 
 #ifdef __cplusplus
 }

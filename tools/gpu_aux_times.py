@@ -3,6 +3,8 @@ Per shape the first round warms up and the median of the others is kept."""
 import json
 import os
 import sys
+import time
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -49,7 +51,54 @@ def subopt_structs(eng, seqs):
     return out
 
 
+def cofold_paths(eng, seqs):
+    """both co-fold folds with the tables in LDS (option cofold_lds = 1) and on the general kernels (0), same process and engine;
+    a pair beyond the bound takes the general kernels either way"""
+    out = {}
+    for lds in (0, 1):
+        eng.set_option("cofold_lds", lds)
+        eng.cofold_batch(seqs, E.NEED_MFE | E.NEED_PF)
+        t = eng.last_timing()
+        out["mfe_ms_lds%d" % lds], out["pf_ms_lds%d" % lds] = t["mfe"], t["pf"]
+    eng.set_option("cofold_lds", 1)
+    return out
+
+
+MC_TARGET = "((((((..((((......&......))))..))))))"       # 18 + 18 nt
+MC_RESTR = "N" * 18 + "&" + "N" * 18
+MC_ITERS = 200
+
+
+def mc_cofold(eng, seqs):
+    """wall time per iteration of drna_mc_run_cofold (64 replicas of 18 + 18 nt, -sf Ed-Epf, targeted moves on), and the same
+    design (same seed, 2 exchange steps of 20 iterations) through run_design_fast's native loop and through run_design"""
+    from desirna_amd import design
+    R = len(seqs)
+    prob = design.DesignProblem(MC_TARGET, MC_RESTR)
+    hk = E.HostKernels()
+    eng.set_targets([MC_TARGET.replace("&", "")])
+    cur = np.frombuffer("".join(seqs).encode(), dtype=np.uint8).reshape(R, -1).copy()
+    co = eng.cofold_batch(seqs)
+    state = dict(seqs=cur, mfe_ss=np.frombuffer("".join(co["mfe_ss"]).encode(), dtype=np.uint8).reshape(R, -1).copy(),
+                 score=np.full(R, 1e3), mcc1=np.ones(R), Epf=np.zeros(R), Ed=np.zeros(R), oligo_fraction=np.zeros(R), bonus=np.zeros(R))
+    best = dict(seq=cur[0].copy(), ss=state["mfe_ss"][0].copy(), vals=np.array([1.0, 1e3, 0, 0, 0, 0]))
+    rng_state = hk.rng_seed(np.arange(R))
+    temps = np.linspace(10.0, 150.0, R)
+    t0 = time.perf_counter()
+    eng.mc_run_cofold(prob, "heterodimer", MC_ITERS, np.arange(R, dtype=np.int32), R, 0.7, 0.0, True, temps, [("Ed-Epf", 1.0)],
+                      rng_state, state, np.zeros(3, dtype=np.int64), best)
+    out = {"mc_iter_wall_ms": (time.perf_counter() - t0) * 1e3 / MC_ITERS}
+    inp = SimpleNamespace(name="pair", sec_struct=MC_TARGET, seq_restr=MC_RESTR, seed_seq=None, alt_sec_struct=None, alt_sec_structs=None)
+    kw = dict(replicas=R, exchange=20, steps=2, seed=3, timelimit=600)
+    for key, run in (("native", lambda: design.run_design_fast(inp, engine=eng, **kw)), ("python", lambda: design.run_design(inp, **kw))):
+        t0 = time.perf_counter()
+        res = run()
+        out["design_%s_iter_per_s" % key] = res["steps"] * 20 / (time.perf_counter() - t0)
+    return out
+
+
 PAIRS = ((64, 18, 18), (64, 50, 50), (64, 100, 100))
+CO_HALF = 32          # CO_LDS_MAX / 2 (fold_cofold_lds.hpp)
 # one round of a section -> (shapes (R, strand lengths ...), seed, a fresh generator per shape, rounds, derived figure)
 SECTIONS = {
     edef: (((64, 200), (128, 400)), 20260101, True, 3,
@@ -58,6 +107,10 @@ SECTIONS = {
     cofold_edef: (PAIRS, 5, False, 5, lambda R, v: ("ratio", v["cofold_outside_ms"] / v["cofold_pf_ms"])),
     subopt_energy: (((64, 36), (64, 100), (64, 200)), 5, False, 5, lambda R, v: ("folds_per_s", R / (v["subopt_ms"] * 1e-3))),
     subopt_structs: (((16, 100), (16, 200)), 5, False, 5, lambda R, v: ("ratio", v["kbest8_ms"] / v["kbest4_ms"])),
+    cofold_paths: (((64, 18, 18), (64, CO_HALF, CO_HALF), (64, CO_HALF + 1, CO_HALF)), 5, False, 7,
+                   lambda R, v: ("lds_over_general", (v["mfe_ms_lds1"] + v["pf_ms_lds1"]) / (v["mfe_ms_lds0"] + v["pf_ms_lds0"]))),
+    mc_cofold: (((64, 18, 18),), 5, False, 3,
+                lambda R, v: ("native_over_python", v["design_native_iter_per_s"] / v["design_python_iter_per_s"])),
 }
 
 
