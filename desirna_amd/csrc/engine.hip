@@ -30,6 +30,7 @@
 #include "fold_pf_strip.hpp"
 #include "fold_subopt.hpp"
 #include "fold_cofold_subopt.hpp"
+#include "fold_subopt_lds.hpp"
 #include "fold_cofold_outside.hpp"
 #include "host_driver.hpp"
 #include "tables.hpp"
@@ -87,6 +88,7 @@ struct drna_engine {
   double* d_F4 = nullptr;   // co-fold free energies (FA, FB, FcAB, FAB per pair)
   double *hm_F4 = nullptr, *dm_F4 = nullptr;   // ... of drna_cofold_batch and drna_mc_run_cofold: host-mapped like hm_Epf, allocated on first use
   bool cofold_lds = true;   // option "cofold_lds": pairs of at most CO_LDS_MAX nt fold with their tables in LDS (fold_cofold_lds.hpp)
+  bool subopt_lds = true;   // option "subopt_lds": second-best folds of at most SUB_LDS_MAX nt keep their tables in LDS (fold_subopt_lds.hpp)
   // K-best structures: workspace for kb_chunk sequences, allocated on first use
   int32_t* d_ws_kb = nullptr;
   int32_t* d_kbE = nullptr;
@@ -411,6 +413,7 @@ extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!strcmp(name, "strips")) { e->strips = value < 0 ? 0 : value > 2 ? 2 : value; return DRNA_OK; }
   if (!strcmp(name, "pf_helper")) { e->pf_helper = value != 0; return DRNA_OK; }
   if (!strcmp(name, "cofold_lds")) { e->cofold_lds = value != 0; return DRNA_OK; }
+  if (!strcmp(name, "subopt_lds")) { e->subopt_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "helper_fault")) { e->helper_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "strip_fault")) { e->strip_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "mfe_fark_min_strips")) { e->mfe_fark_min_strips = value < 1 ? 1 : value; return DRNA_OK; }
@@ -437,6 +440,8 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "fused")) { *value = e->fused ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "cofold_lds")) { *value = e->cofold_lds ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "cofold_lds_max")) { *value = CO_LDS_MAX; return DRNA_OK; }
+  if (!strcmp(name, "subopt_lds")) { *value = e->subopt_lds ? 1 : 0; return DRNA_OK; }
+  if (!strcmp(name, "subopt_lds_max")) { *value = SUB_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "last_fused")) { *value = e->last_fused ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "fused_blocks_per_cu")) { *value = e->fused_blocks_per_cu; return DRNA_OK; }
   if (!strcmp(name, "pair_blocks_per_cu")) { *value = e->pair_blocks_per_cu; return DRNA_OK; }
@@ -1273,6 +1278,18 @@ static SuboptArgs subopt_args(const drna_engine* e, int L, int cut, int K) {
   }
   return a;
 }
+// the second-best fold of R sequences (a.cut > 0: pairs) on the MFE stream: sequences of at most SUB_LDS_MAX nucleotides keep their
+// tables in LDS (option "subopt_lds"), longer ones in the workspace slots
+static void launch_second_best(drna_engine* e, const SuboptArgs& a, int R) {
+  const bool lds = e->subopt_lds && a.L <= SUB_LDS_MAX;
+  if (a.cut) {
+    if (lds) hipLaunchKernelGGL(cofold_subopt_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
+    else hipLaunchKernelGGL(cofold_subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
+  } else {
+    if (lds) hipLaunchKernelGGL(subopt_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
+    else hipLaunchKernelGGL(subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a);
+  }
+}
 // upload, launch() on the MFE stream (timed as "mfe"), status, E2 and (optional) E12 back
 template <class Launch>
 static int second_best_batch(drna_engine* e, int R, int L, const char* seqs, int32_t* E2, int32_t* E12, const char* internal_msg,
@@ -1302,7 +1319,7 @@ extern "C" int drna_subopt_energy_batch(drna_engine* e, int R, int L, const char
   { const int rc = second_best_check(e, "drna_subopt_energy_batch", R, L, nullptr, seqs && E2); if (rc != DRNA_OK) return rc; }
   const SuboptArgs a = subopt_args(e, L, 0, 2);
   return second_best_batch(e, R, L, seqs, E2, E12, "unexpected status of the second-best fold",
-                           [&] { hipLaunchKernelGGL(subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a); });
+                           [&] { launch_second_best(e, a, R); });
 }
 
 extern "C" int drna_cofold_subopt_energy_batch(drna_engine* e, int R, int L, int cut, const char* seqs, int32_t* E2, int32_t* E12) {
@@ -1310,7 +1327,20 @@ extern "C" int drna_cofold_subopt_energy_batch(drna_engine* e, int R, int L, int
   { const int rc = second_best_check(e, "drna_cofold_subopt_energy_batch", R, L, &cut, seqs && E2); if (rc != DRNA_OK) return rc; }
   const SuboptArgs a = subopt_args(e, L, cut, 2);
   return second_best_batch(e, R, L, seqs, E2, E12, "unexpected status of the second-best co-fold",
-                           [&] { hipLaunchKernelGGL(cofold_subopt_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, a); });
+                           [&] { launch_second_best(e, a, R); });
+}
+
+// The negative-design step of the native loops: H sequences (L letters each; cut > 0: pairs without the '&') the caller has put
+// into hm_seqs; E2 comes back in hm_Emfe, so the step costs one launch and no hipMemcpy
+static int second_best_mapped(drna_engine* e, int H, int L, int cut) {
+  HIP_TRY(hipSetDevice(e->device));
+  reset_status(e);
+  SuboptArgs a = subopt_args(e, L, cut, 2);
+  a.seqs = e->dm_seqs; a.E2 = e->dm_Emfe; a.E12 = nullptr;
+  launch_second_best(e, a, H);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->s_mfe));
+  return fold_status(e, H, true, false, nullptr, 0, cut ? "unexpected status of the second-best co-fold" : "unexpected status of the second-best fold");
 }
 
 extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const char* seqs, int K, int32_t* E, char* ss) {
@@ -1695,25 +1725,33 @@ extern "C" int drna_metropolis_batch(int R, const double* score_o, const double*
 struct McScored {
   std::vector<char> ss;                          // R x L MFE structures, in the layout of the state strings
   std::vector<double> Epf, ed, Emfe, edef;       // kcal/mol: ensemble free energy, E(targets[0]), MFE energy; ensemble defect
-  std::vector<double> add;                       // added to the -sf sum (alternative structures; oligomer / monomer-fraction bonus)
-  std::vector<double> x0, x1;                    // two strands: oligo_fraction and the bonus, kept with an accepted state
+  std::vector<double> add;                       // added to the -sf sum: the alternative-structure term
+  std::vector<double> x0, x1;                    // two strands: oligo_fraction and the bonus, kept with an accepted state; the bonus is
+                                                 // added last, after the negative-design term (the reference's order of additions)
   bool has_add = false;
 };
 
 // The loop both drna_mc_run and drna_mc_run_cofold run: proposals from the replicas' own streams, the entry point's scoring of
 // all R proposals (score_all(prop) fills S), SimScore (metrics(ss, pq): pair table of the L-char structure for the targeted
 // moves, and the three rounded metrics against the target), the -sf sum, Metropolis, state update, counters and best state.
-// L is the length of the state strings (two strands: with the '&'); xs0 / xs1: per-replica state beside the usual arrays or null
-template <class ScoreAll, class Metrics>
+// L is the length of the state strings (two strands: with the '&'); xs0 / xs1: per-replica state beside the usual arrays or null.
+// Negative design (sub given: the _nd entry points; utils/energy_scores.py:104-108): between scoring and Metropolis the proposals
+// whose 1 - MCC is exactly 0 get their second-best fold in ONE launch (second_best(prop, hits, H) leaves E2 of hit h in
+// e->hm_Emfe[h]) and lose E2 / 100 - Epf; sub[r] is the second-best energy of replica r's current state (0 where it is unsolved)
+// and best[4] (two strands: best[6]) that of the best state.  So an iteration is two passes over the replicas: scores of all R
+// proposals first, then the Metropolis draws in replica order, each from its replica's own stream as before
+template <class ScoreAll, class Metrics, class SecondBest>
 static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, ProposeCtx& ctx, const int32_t* shelf_index, int targeted,
                    const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w, uint32_t* rng_state,
-                   char* seqs, char* mfe_ss, double* score, double* mcc1, double* Epf, double* Ed, double* xs0, double* xs1,
+                   char* seqs, char* mfe_ss, double* score, double* mcc1, double* Epf, double* Ed, double* xs0, double* xs1, double* sub,
                    int64_t* counters, char* best_seq, char* best_ss, double* best, McScored& S, ScoreAll&& score_all,
-                   Metrics&& metrics) {
+                   Metrics&& metrics, SecondBest&& second_best) {
   using namespace drna_host;
   std::vector<char> prop((size_t)R * L);
-  std::vector<double> pscore(R), pmcc(R), p_shelf(R, 0.0);
-  std::vector<unsigned char> acc(R), better(R);
+  std::vector<double> pscore(R), pmcc(R), p_shelf(R, 0.0), psub(sub ? R : 0);
+  std::vector<unsigned char> acc(R), better(R), same(R), bad(R);
+  std::vector<SimMetrics> pm(R);
+  std::vector<int> hits;
   // Per replica, of its CURRENT structure: the pair table, its SimScore against the target and the targeted-move pool (what the
   // proposal compares with the target).  Parsed once here and replaced when a proposal is accepted; a proposal whose MFE
   // structure equals the current one (most single mutations of a converged replica) reuses all three
@@ -1746,12 +1784,14 @@ static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, Pr
     const int rc = score_all(prop.data());
     if (rc != DRNA_OK) return rc;
     const double tp1 = mc_profile ? now_us() : 0.0;
+    hits.clear();
     for (int r = 0; r < R; r++) {
       // SimScore of the proposal's structure against the target (utils/sim_score.py:62-147)
-      int* ppq = prop_pq.data() + (size_t)r * L;
-      const bool same_ss = std::memcmp(S.ss.data() + (size_t)r * L, mfe_ss + (size_t)r * L, (size_t)L) == 0;
-      SimMetrics m = cur_m[r];
-      if (!same_ss && !metrics(S.ss.data() + (size_t)r * L, ppq, m)) { fail = DRNA_ERR_STRUCTURE; continue; }
+      same[r] = std::memcmp(S.ss.data() + (size_t)r * L, mfe_ss + (size_t)r * L, (size_t)L) == 0;
+      SimMetrics& m = pm[r];
+      m = cur_m[r];
+      bad[r] = !same[r] && !metrics(S.ss.data() + (size_t)r * L, prop_pq.data() + (size_t)r * L, m);
+      if (bad[r]) { fail = DRNA_ERR_STRUCTURE; continue; }
       const double ed = S.ed[r];
       // -sf terms (utils/energy_scores.py:376-398): 0 Ed-Epf, 1 1-MCC, 2 sln_Epf, 3 Ed-MFE, 4 1-precision, 5 1-recall, 6 Edef
       double tot = 0.0;
@@ -1770,6 +1810,27 @@ static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, Pr
       }
       if (S.has_add) tot += S.add[r];
       pscore[r] = tot; pmcc[r] = 1 - m.mcc;
+      if (sub && pmcc[r] == 0) hits.push_back(r);             // solved: the test of ReplicaScorer._negative_design, on the rounded metric
+    }
+    if (sub) {
+      std::fill(psub.begin(), psub.end(), 0.0);
+      if (!hits.empty()) {
+        const int rc2 = second_best(prop.data(), hits.data(), (int)hits.size());
+        if (rc2 != DRNA_OK) return rc2;
+        for (size_t h = 0; h < hits.size(); h++) {
+          const int r = hits[h];
+          psub[r] = e->hm_Emfe[h] / 100.0;
+          pscore[r] -= psub[r] - S.Epf[r];
+        }
+      }
+    }
+    for (int r = 0; r < R; r++) {
+      if (bad[r]) continue;
+      if (xs0) pscore[r] += S.x1[r];                          // oligomer / monomer-fraction bonus: the last addition
+      const bool same_ss = same[r];
+      const SimMetrics& m = pm[r];
+      int* ppq = prop_pq.data() + (size_t)r * L;
+      const double ed = S.ed[r];
       // Metropolis (utils/replica_exchange_monte_carlo.py:26-57): one draw from the replica's stream, only when the mutant is worse
       (void)drna_metropolis_batch(1, score + r, pscore.data() + r, temps + r, Lconst, rng_state + (size_t)r * RNG_WORDS, acc.data() + r,
                                   better.data() + r);
@@ -1783,6 +1844,7 @@ static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, Pr
         }
         score[r] = pscore[r]; mcc1[r] = pmcc[r]; Epf[r] = S.Epf[r]; Ed[r] = ed;
         if (xs0) { xs0[r] = S.x0[r]; xs1[r] = S.x1[r]; }
+        if (sub) sub[r] = psub[r];
       }
     }
     if (it + 1 < n_iter && fail == DRNA_OK) propose_all();          // the next iteration's proposals (same streams, after the Metropolis draw)
@@ -1796,6 +1858,7 @@ static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, Pr
         if (mcc1[r] < best[0] || (mcc1[r] == best[0] && score[r] < best[1])) {
           best[0] = mcc1[r]; best[1] = score[r]; best[2] = Epf[r]; best[3] = Ed[r];
           if (xs0) { best[4] = xs0[r]; best[5] = xs1[r]; }
+          if (sub) best[xs0 ? 6 : 4] = sub[r];
           std::memcpy(best_seq, seqs + (size_t)r * L, (size_t)L);
           std::memcpy(best_ss, mfe_ss + (size_t)r * L, (size_t)L);
         }
@@ -1819,24 +1882,25 @@ static int mc_terms(drna_engine* e, const char* who, int n_terms, const int32_t*
   return DRNA_OK;
 }
 
-extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char* target, const int32_t* partner,
-                           const unsigned char* allowed_mask, const int32_t* snake_of, int n_snakes, const int32_t* snake_off,
-                           const int32_t* snake_nodes, const int32_t* snake_nstates, const char* snake_states,
-                           const int32_t* shelf_index, int n_shelves, double tm_max, double tm_min, int targeted,
-                           const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w,
-                           uint32_t flags, uint32_t* rng_state, char* seqs, char* mfe_ss, double* score, double* mcc1,
-                           double* Epf, double* Ed, int64_t* counters, char* best_seq, char* best_ss, double* best) {
+// drna_mc_run (subopt_e null) and drna_mc_run_nd
+static int mc_run_impl(drna_engine* e, const char* who, int R, int L, int n_iter, const char* target, const int32_t* partner,
+                       const unsigned char* allowed_mask, const int32_t* snake_of, int n_snakes, const int32_t* snake_off,
+                       const int32_t* snake_nodes, const int32_t* snake_nstates, const char* snake_states,
+                       const int32_t* shelf_index, int n_shelves, double tm_max, double tm_min, int targeted,
+                       const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w,
+                       uint32_t flags, uint32_t* rng_state, char* seqs, char* mfe_ss, double* score, double* mcc1,
+                       double* Epf, double* Ed, int64_t* counters, char* best_seq, char* best_ss, double* best, double* subopt_e) {
   using namespace drna_host;
-  if (!e) return DRNA_ERR_ARG;
   if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || n_iter < 0 || !target || !allowed_mask || !shelf_index || !temps ||
       n_terms < 1 || !term_id || !term_w || !rng_state || !seqs || !mfe_ss || !score || !mcc1 || !Epf || !Ed || !counters ||
       !best_seq || !best_ss || !best || e->n_targets < 1 || e->L_targets != L) {
-    e->err = "drna_mc_run: bad argument (targets installed with drna_set_targets for this L; every state array given)";
+    e->err = std::string(who) + ": bad argument (targets installed with drna_set_targets for this L; every state array given)";
     return DRNA_ERR_ARG;
   }
   const int nt = e->n_targets;
   bool want_edef = false;
-  { const int rc = mc_terms(e, "drna_mc_run", n_terms, term_id, &want_edef); if (rc != DRNA_OK) return rc; }
+  { const int rc = mc_terms(e, who, n_terms, term_id, &want_edef); if (rc != DRNA_OK) return rc; }
+  if (subopt_e) { const int rc = fits_workspace(e, who, R); if (rc != DRNA_OK) return rc; }
   McScored S;
   S.ss.resize((size_t)R * L); S.Epf.resize(R); S.ed.resize(R); S.Emfe.resize(R);
   if (want_edef) S.edef.resize(R);
@@ -1847,7 +1911,7 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
   {
     const int rc = propose_ctx_init(ctx, L, target, partner, allowed_mask, n_snakes > 0 ? snake_of : nullptr, snake_off, snake_nodes,
                                     snake_nstates, snake_states, n_shelves, tm_max, tm_min, targeted);
-    if (rc != DRNA_OK) { e->err = rc == DRNA_ERR_STRUCTURE ? "drna_mc_run: unbalanced target structure" : "drna_mc_run: proposal failed"; return rc; }
+    if (rc != DRNA_OK) { e->err = std::string(who) + (rc == DRNA_ERR_STRUCTURE ? ": unbalanced target structure" : ": proposal failed"); return rc; }
   }
   const int* pr = ctx.pt.data();
   auto score_all = [&](const char* prop) -> int {
@@ -1874,8 +1938,36 @@ extern "C" int drna_mc_run(drna_engine* e, int R, int L, int n_iter, const char*
     m = sim_metrics(pr, pq, L);
     return true;
   };
-  return mc_loop(e, "drna_mc_run", R, L, n_iter, ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs,
-                 mfe_ss, score, mcc1, Epf, Ed, nullptr, nullptr, counters, best_seq, best_ss, best, S, score_all, metrics);
+  auto second_best = [&](const char* prop, const int* hits, int H) -> int {
+    for (int h = 0; h < H; h++) std::memcpy(e->hm_seqs + (size_t)h * L, prop + (size_t)hits[h] * L, (size_t)L);
+    return second_best_mapped(e, H, L, 0);
+  };
+  return mc_loop(e, who, R, L, n_iter, ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs,
+                 mfe_ss, score, mcc1, Epf, Ed, nullptr, nullptr, subopt_e, counters, best_seq, best_ss, best, S, score_all, metrics,
+                 second_best);
+}
+
+#define MC_RUN_PARAMS                                                                                                              \
+  drna_engine *e, int R, int L, int n_iter, const char *target, const int32_t *partner, const unsigned char *allowed_mask,         \
+      const int32_t *snake_of, int n_snakes, const int32_t *snake_off, const int32_t *snake_nodes, const int32_t *snake_nstates,  \
+      const char *snake_states, const int32_t *shelf_index, int n_shelves, double tm_max, double tm_min, int targeted,             \
+      const double *temps, double Lconst, int n_terms, const int32_t *term_id, const double *term_w, uint32_t flags,               \
+      uint32_t *rng_state, char *seqs, char *mfe_ss, double *score, double *mcc1, double *Epf, double *Ed, int64_t *counters,      \
+      char *best_seq, char *best_ss, double *best
+#define MC_RUN_ARGS                                                                                                                 \
+  R, L, n_iter, target, partner, allowed_mask, snake_of, n_snakes, snake_off, snake_nodes, snake_nstates, snake_states, shelf_index, \
+      n_shelves, tm_max, tm_min, targeted, temps, Lconst, n_terms, term_id, term_w, flags, rng_state, seqs, mfe_ss, score, mcc1, Epf, \
+      Ed, counters, best_seq, best_ss, best
+
+extern "C" int drna_mc_run(MC_RUN_PARAMS) {
+  if (!e) return DRNA_ERR_ARG;
+  return mc_run_impl(e, "drna_mc_run", MC_RUN_ARGS, nullptr);
+}
+
+extern "C" int drna_mc_run_nd(MC_RUN_PARAMS, double* subopt_e) {
+  if (!e) return DRNA_ERR_ARG;
+  if (!subopt_e) { e->err = "drna_mc_run_nd: bad argument (subopt_e required)"; return DRNA_ERR_ARG; }
+  return mc_run_impl(e, "drna_mc_run_nd", MC_RUN_ARGS, subopt_e);
 }
 
 // reference utils/dimer_multichain_energy.py:24-45: fraction of strands bound in the dimer at 1 mM, and -kT ln of a fraction
@@ -1887,15 +1979,19 @@ static double oligo_fraction(double FA, double FB, double FcAB) {
 }
 static double kT_log(double x) { return -0.001987204259 * (273.15 + 37) * std::log(x); }
 
-extern "C" int drna_mc_run_cofold(drna_engine* e, int R, int L, int cut, int n_iter, const char* target, const unsigned char* allowed_mask,
-                                  int oligo_state, const int32_t* shelf_index, int n_shelves, double tm_max, double tm_min,
-                                  int targeted, const double* temps, double Lconst, int n_terms, const int32_t* term_id,
-                                  const double* term_w, uint32_t* rng_state, char* seqs, char* mfe_ss, double* score, double* mcc1,
-                                  double* Epf, double* Ed, double* oligo_frac, double* bonus, int64_t* counters, char* best_seq,
-                                  char* best_ss, double* best) {
+#define MC_RUN_CO_PARAMS                                                                                                              \
+  drna_engine *e, int R, int L, int cut, int n_iter, const char *target, const unsigned char *allowed_mask, int oligo_state,          \
+      const int32_t *shelf_index, int n_shelves, double tm_max, double tm_min, int targeted, const double *temps, double Lconst,      \
+      int n_terms, const int32_t *term_id, const double *term_w, uint32_t *rng_state, char *seqs, char *mfe_ss, double *score,        \
+      double *mcc1, double *Epf, double *Ed, double *oligo_frac, double *bonus, int64_t *counters, char *best_seq, char *best_ss,     \
+      double *best
+#define MC_RUN_CO_ARGS                                                                                                                \
+  R, L, cut, n_iter, target, allowed_mask, oligo_state, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, Lconst, n_terms,     \
+      term_id, term_w, rng_state, seqs, mfe_ss, score, mcc1, Epf, Ed, oligo_frac, bonus, counters, best_seq, best_ss, best
+
+// drna_mc_run_cofold (subopt_e null) and drna_mc_run_cofold_nd
+static int mc_run_cofold_impl(const char* who, MC_RUN_CO_PARAMS, double* subopt_e) {
   using namespace drna_host;
-  if (!e) return DRNA_ERR_ARG;
-  const char* who = "drna_mc_run_cofold";
   const int Ls = L + 1;                      // the state strings carry the '&' at column cut
   if (R < 1 || R > e->max_R || L < 2 || L > e->max_L || n_iter < 0 || !target || !allowed_mask || !shelf_index || !temps ||
       n_terms < 1 || !term_id || !term_w || !rng_state || !seqs || !mfe_ss || !score || !mcc1 || !Epf || !Ed || !oligo_frac || !bonus ||
@@ -1914,8 +2010,7 @@ extern "C" int drna_mc_run_cofold(drna_engine* e, int R, int L, int cut, int n_i
   if (rc != DRNA_OK) return rc;
   const int nt = e->n_targets;
   McScored S;
-  S.ss.resize((size_t)R * Ls); S.Epf.resize(R); S.ed.resize(R); S.Emfe.resize(R); S.add.resize(R); S.x0.resize(R); S.x1.resize(R);
-  S.has_add = true;
+  S.ss.resize((size_t)R * Ls); S.Epf.resize(R); S.ed.resize(R); S.Emfe.resize(R); S.x0.resize(R); S.x1.resize(R);
   if (want_edef) S.edef.resize(R);
   std::vector<char> flat(want_edef ? (size_t)R * L : 0);
   ProposeCtx ctx;
@@ -1965,8 +2060,7 @@ extern "C" int drna_mc_run_cofold(drna_engine* e, int R, int L, int cut, int n_i
       o[cut] = '&';
       std::memcpy(o + cut + 1, e->hm_ss + (size_t)r * L + cut, (size_t)(L - cut));
       S.x0[r] = oligo_fraction(F[0], F[1], F[2]);
-      S.x1[r] = oligomer ? kT_log(S.x0[r]) : kT_log(1 - S.x0[r]);
-      S.add[r] = S.x1[r];
+      S.x1[r] = oligomer ? kT_log(S.x0[r]) : kT_log(1 - S.x0[r]);          // (added by the loop, after the negative-design term)
     }
     if (want_edef) {                          // inside + outside recursion under the co-fold rules (fold_cofold_outside.hpp)
       rc2 = drna_cofold_ensemble_defect_batch(e, R, L, cut, flat.data(), S.edef.data(), nullptr);
@@ -1974,6 +2068,25 @@ extern "C" int drna_mc_run_cofold(drna_engine* e, int R, int L, int cut, int n_i
     }
     return DRNA_OK;
   };
+  auto second_best = [&](const char* prop, const int* hits, int H) -> int {       // the letters of both strands, without the '&'
+    for (int h = 0; h < H; h++) {
+      const char* p = prop + (size_t)hits[h] * Ls;
+      std::memcpy(e->hm_seqs + (size_t)h * L, p, (size_t)cut);
+      std::memcpy(e->hm_seqs + (size_t)h * L + cut, p + cut + 1, (size_t)(L - cut));
+    }
+    return second_best_mapped(e, H, L, cut);
+  };
   return mc_loop(e, who, R, Ls, n_iter, ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs, mfe_ss,
-                 score, mcc1, Epf, Ed, oligo_frac, bonus, counters, best_seq, best_ss, best, S, score_all, metrics);
+                 score, mcc1, Epf, Ed, oligo_frac, bonus, subopt_e, counters, best_seq, best_ss, best, S, score_all, metrics, second_best);
+}
+
+extern "C" int drna_mc_run_cofold(MC_RUN_CO_PARAMS) {
+  if (!e) return DRNA_ERR_ARG;
+  return mc_run_cofold_impl("drna_mc_run_cofold", e, MC_RUN_CO_ARGS, nullptr);
+}
+
+extern "C" int drna_mc_run_cofold_nd(MC_RUN_CO_PARAMS, double* subopt_e) {
+  if (!e) return DRNA_ERR_ARG;
+  if (!subopt_e) { e->err = "drna_mc_run_cofold_nd: bad argument (subopt_e required)"; return DRNA_ERR_ARG; }
+  return mc_run_cofold_impl("drna_mc_run_cofold_nd", e, MC_RUN_CO_ARGS, subopt_e);
 }

@@ -21,7 +21,9 @@ processes (it iterates over ``set`` objects of strings, whose order depends on P
 Alternative structures: "snake" moves (connected components of the pair graph of target + alternative structures
 switch between their Watson-Crick colourings) as in the reference (:143-388, :1081-1095).
 
-``-acgu on`` (weighted letter choices), ``-nd on``, ``-oa on`` and motifs are available in the Python driver (``run_design``).
+``-nd on`` (negative design) runs through both drivers (``run_design_fast(negative_design="on")``: the second-best fold of the
+solved candidates per iteration, or inside the native loop); ``-acgu on`` (weighted letter choices), ``-oa on`` and motifs are
+available in the Python driver (``run_design``) only.
 
 Two strands (hetero-dimer, ``-d on`` homodimer) run through both drivers; together with alternative structures through
 ``run_design`` only.
@@ -384,7 +386,8 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
 
 def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                     scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
-                    device=0, engine=None, keep_records=True, native_loop=None, shards=None, num_results=None, dimer="off"):
+                    device=0, engine=None, keep_records=True, native_loop=None, shards=None, num_results=None, dimer="off",
+                    negative_design="off"):
     """Same loop as :func:`run_design` with the per-replica host work in native code and no per-step Python objects:
     proposals, SimScore and Metropolis run batched in the C library, the replica state lives in numpy arrays.  The
     per-replica random streams are the reference's (MT19937 seeded with the replica index at every exchange step, CPython's
@@ -397,7 +400,12 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
 
     Two-strand targets (one ``&``; ``dimer="on"`` = homodimer, else hetero-dimer) take ``HostKernels.propose_co`` and
     ``Engine.cofold_batch`` per iteration, or ``Engine.mc_run_cofold`` for the whole inner loop; their records carry the
-    ``oligo_fraction`` and ``oligomer_bonus`` :func:`run_design` writes.  Alternative structures with two strands raise."""
+    ``oligo_fraction`` and ``oligomer_bonus`` :func:`run_design` writes.  Alternative structures with two strands raise.
+
+    ``negative_design="on"`` (``-nd on``, reference ``utils/energy_scores.py:104-108``): every solved candidate (1 - MCC == 0)
+    loses ``subopt_e - Epf``, the second-best structure's energy from ``Engine.subopt_energy`` / ``Engine.cofold_subopt_energy``
+    on the solved subset, or from the negative-design step of ``Engine.mc_run[_cofold]``; for two strands before the bonus.
+    Records and ``best`` carry ``subopt_e`` and ``esubopt_minus_Epf`` as :func:`run_design`'s do."""
     from . import engine as _engine
     if stop_when_solved and num_results is not None and not keep_records:
         raise ValueError("the -sws rule with num_results ranks the recorded sequences: it needs keep_records=True "
@@ -408,6 +416,7 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
         raise NotImplementedError("two strands with alternative structures run through run_design (the native two-strand "
                                   "proposer has no snake moves)")
     oligo_state = ("homodimer" if dimer == "on" else "heterodimer") if two else "none"
+    nd = negative_design == "on"
     n_alt = len(input_file.alt_sec_structs) if input_file.alt_sec_structs else 0
     sf = es.parse_scoring_functions(scoring_f)
     for name, _ in sf:
@@ -437,8 +446,17 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
         return np.concatenate([a[:, :cut], np.full((len(a), 1), ord("E"), np.uint8), np.full((len(a), 1), ord("e"), np.uint8),
                                a[:, cut + 1:]], axis=1)
 
+    def negative_design_term(total, mcc1, Epf, strings, second_best):
+        """ReplicaScorer._negative_design on arrays: total loses subopt_e - Epf where 1 - MCC == 0; returns subopt_e (0 elsewhere)"""
+        sub = np.zeros(len(total))
+        hit = np.nonzero(mcc1 == 0)[0]
+        if nd and len(hit):
+            sub[hit] = second_best([strings(k) for k in hit]) / 100.0
+            total[hit] -= sub[hit] - Epf[hit]
+        return sub
+
     def score_two(seqs_u8):
-        """ReplicaScorer._score_two_strands on arrays: (total, 1-MCC, structures, Epf = FAB, Ed, oligo_fraction, bonus)"""
+        """ReplicaScorer._score_two_strands on arrays: (total, 1-MCC, structures, Epf = FAB, Ed, oligo_fraction, bonus, subopt_e)"""
         seqs = [bytes(r).decode() for r in seqs_u8]
         out = eng.cofold_batch(seqs, _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL)
         ss = np.frombuffer("".join(out["mfe_ss"]).encode(), dtype=np.uint8).reshape(len(seqs), L).copy()
@@ -453,7 +471,8 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
             total += terms[name]() * w
         frac = np.array([float(es.oligo_fraction(out["FA"][k], out["FB"][k], out["FcAB"][k])) for k in range(len(seqs))])
         bonus = np.array([float(es.kTlog_oligo_fraction(f) if oligomer else es.kTlog_monomer_fraction(f)) for f in frac])
-        return total + bonus, 1 - mcc, ss, Epf, ed, frac, bonus
+        sub = negative_design_term(total, 1 - mcc, Epf, lambda k: seqs[k], lambda hit: eng.cofold_subopt_energy(hit))      # before the bonus
+        return total + bonus, 1 - mcc, ss, Epf, ed, frac, bonus, sub
 
     def score(seqs_u8):
         if two:
@@ -479,17 +498,20 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                 total += eng.ensemble_defect_arrays(seqs_u8) * w
         if n_alt:                                                 # reference energy_scores.py:98-102
             total += Ed[:, 1:].sum(axis=1) / 100.0 / n_alt - Epf
-        return total, 1 - mcc, ss, Epf, ed, None, None
+        sub = negative_design_term(total, 1 - mcc, Epf, lambda k: bytes(seqs_u8[k]).decode(), lambda hit: eng.subopt_energy(hit))
+        return total, 1 - mcc, ss, Epf, ed, None, None, sub
 
     init = prob.initial_sequence(main_rng)
     cur = np.tile(np.frombuffer(init.encode(), dtype=np.uint8), (max(1, Rl), 1)).copy()
-    cur_score, cur_mcc, cur_ss, cur_epf, cur_ed, cur_frac, cur_bonus = score(cur)
+    cur_score, cur_mcc, cur_ss, cur_epf, cur_ed, cur_frac, cur_bonus, cur_sub = score(cur)
 
     def best_of(k):
         b = dict(sequence=cur[k].tobytes().decode(), mfe_ss=cur_ss[k].tobytes().decode(), mcc=float(cur_mcc[k]),
                  scoring_function=float(cur_score[k]), Epf=float(cur_epf[k]), edesired=float(cur_ed[k]))
         if two:
             b.update(oligo_fraction=float(cur_frac[k]), oligomer_bonus=float(cur_bonus[k]))
+        if nd:
+            b.update(subopt_e=float(cur_sub[k]), esubopt_minus_Epf=float(cur_sub[k] - cur_epf[k]) if cur_mcc[k] == 0 else 0.0)
         return b
 
     best = best_of(int(np.lexsort((cur_score, cur_mcc))[0]))
@@ -511,6 +533,9 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
             if two:
                 sc.oligo_fraction = float(cur_frac[k])
                 sc.oligomer_bonus = float(cur_bonus[k])
+            if nd and cur_mcc[k] == 0:
+                sc.get_subopt_e(float(cur_sub[k]))
+                sc.get_esubopt_minus_Epf(sc.Epf, sc.subopt_e)
             out.append(dict(vars(sc)))
         return out
 
@@ -523,6 +548,7 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
     cur = np.ascontiguousarray(cur); cur_ss = np.ascontiguousarray(cur_ss)
     cur_score = np.ascontiguousarray(cur_score, dtype=np.float64); cur_mcc = np.ascontiguousarray(cur_mcc, dtype=np.float64)
     cur_epf = np.ascontiguousarray(cur_epf, dtype=np.float64); cur_ed = np.ascontiguousarray(cur_ed, dtype=np.float64)
+    cur_sub = np.ascontiguousarray(cur_sub, dtype=np.float64)
     rng_state = np.empty((max(1, Rl), _engine.RNG_WORDS), dtype=np.uint32)
     t_start = time.time()
     step = 0
@@ -547,18 +573,24 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
             if two:
                 vals += [best["oligo_fraction"], best["oligomer_bonus"]]
                 state.update(oligo_fraction=cur_frac, bonus=cur_bonus)
+            if nd:
+                vals += [best["subopt_e"]]
+            nd_kw = dict(subopt_e=cur_sub) if nd else {}
             bst = dict(seq=np.frombuffer(best["sequence"].encode(), dtype=np.uint8).copy(),
                        ss=np.frombuffer(best["mfe_ss"].encode(), dtype=np.uint8).copy(), vals=np.array(vals, dtype=np.float64))
             if two:
                 eng.mc_run_cofold(prob, oligo_state, exchange, shelf_idx, R, tm_max, tm_min, targeted, np.ascontiguousarray(tl), sf,
-                                  rng_state, state, counters, bst)
+                                  rng_state, state, counters, bst, **nd_kw)
             else:
                 eng.mc_run(prob, exchange, shelf_idx, R, tm_max, tm_min, targeted, np.ascontiguousarray(tl), sf, flags, rng_state,
-                           state, counters, bst)
+                           state, counters, bst, **nd_kw)
             best = dict(sequence=bst["seq"].tobytes().decode(), mfe_ss=bst["ss"].tobytes().decode(), mcc=float(bst["vals"][0]),
                         scoring_function=float(bst["vals"][1]), Epf=float(bst["vals"][2]), edesired=float(bst["vals"][3]))
             if two:
                 best.update(oligo_fraction=float(bst["vals"][4]), oligomer_bonus=float(bst["vals"][5]))
+            if nd:
+                sub_b = float(bst["vals"][-1])
+                best.update(subopt_e=sub_b, esubopt_minus_Epf=sub_b - best["Epf"] if best["mcc"] == 0 else 0.0)
             stats["acc_mc"] += int(counters[0]); stats["acc_mc_better"] += int(counters[1]); stats["rej_mc"] += int(counters[2])
             stats["scored"] += Rl * exchange
         for _ in range(0 if (native_loop or not Rl) else exchange):
@@ -566,10 +598,11 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                 prop = hk.propose_co(prob, oligo_state, cur, cur_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
             else:
                 prop = hk.propose_alt(prob, cur, cur_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
-            p_score, p_mcc, p_ss, p_epf, p_ed, p_frac, p_bonus = score(prop)
+            p_score, p_mcc, p_ss, p_epf, p_ed, p_frac, p_bonus, p_sub = score(prop)
             acc, better = hk.metropolis(cur_score, p_score, tl, rng_state)
             cur[acc] = prop[acc]; cur_ss[acc] = p_ss[acc]
             cur_score[acc] = p_score[acc]; cur_mcc[acc] = p_mcc[acc]; cur_epf[acc] = p_epf[acc]; cur_ed[acc] = p_ed[acc]
+            cur_sub[acc] = p_sub[acc]
             if two:
                 cur_frac[acc] = p_frac[acc]; cur_bonus[acc] = p_bonus[acc]
             na = int(acc.sum())
@@ -647,16 +680,21 @@ def main(argv=None):
     a = ap.parse_args(argv)
     inp = read_input(a.name)
     strands2 = "&" in inp.sec_struct
-    # the Python driver's own features: -oa, -acgu, -nd, and two strands together with alternative structures
-    two = a.oligo == "on" or a.percs == "on" or a.subopt == "on" or (strands2 and bool(inp.alt_sec_structs))
-    extra = dict(dimer=a.dimer, oligo=a.oligo, subopt=a.subopt) if (two or (strands2 and a.python_host)) else \
-        (dict(dimer=a.dimer) if strands2 else {})
+    # the Python driver's own features: -oa, -acgu, and two strands together with alternative structures
+    two = a.oligo == "on" or a.percs == "on" or (strands2 and bool(inp.alt_sec_structs))
+    python_host = a.python_host or two
+    if python_host:
+        extra = dict(dimer=a.dimer, oligo=a.oligo, subopt=a.subopt) if (two or strands2 or a.subopt == "on") else {}
+    else:
+        extra = dict(dimer=a.dimer) if strands2 else {}
+        if a.subopt == "on":
+            extra["negative_design"] = "on"
     if a.percs == "on":
         vals = [int(x) for x in a.acgu_content.split(",")] if a.acgu_content else [15, 30, 30, 15]
         if sum(vals) != 100:
             raise SystemExit("The ACGU content should sum up to 100, check your command.")
         extra["acgu"] = dict(zip("ACGU", vals))
-    res = (run_design if (a.python_host or two) else run_design_fast)(inp, **extra, replicas=a.replicas, exchange=a.exchange, steps=a.steps, timelimit=a.timlim, t_min=a.t_min,
+    res = (run_design if python_host else run_design_fast)(inp, **extra, replicas=a.replicas, exchange=a.exchange, steps=a.steps, timelimit=a.timlim, t_min=a.t_min,
                      t_max=a.t_max, scoring_f=a.scoring_f, tm_max=a.tm_max, tm_min=a.tm_min, point_mutations=a.pm,
                      seed=a.in_seed, stop_when_solved=a.sws == "on", num_results=a.num_results if a.sws == "on" else None)
     if a.outdir:

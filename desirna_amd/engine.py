@@ -57,6 +57,10 @@ _SIGNATURES = {
     "drna_propose_batch_co": (_ci, [_ci, _ci, _str, _vp, _ci, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci, _vp, _vp]),
     "drna_mc_run_cofold": (_ci, [_vp, _ci, _ci, _ci, _ci, _str, _vp, _ci, _vp, _ci, _dbl, _dbl, _ci, _vp, _dbl, _ci, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drna_mc_run_nd": (_ci, [_vp, _ci, _ci, _ci, _str, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci, _vp,
+                             _dbl, _ci, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drna_mc_run_cofold_nd": (_ci, [_vp, _ci, _ci, _ci, _ci, _str, _vp, _ci, _vp, _ci, _dbl, _dbl, _ci, _vp, _dbl, _ci, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "drna_rng_seed": (_ci, [_ci, _vp, _vp]),
     "drna_rng_random": (_ci, [_ci, _vp, _vp]),
 }
@@ -272,9 +276,11 @@ class Engine:
     TERM_IDS = {"Ed-Epf": 0, "1-MCC": 1, "sln_Epf": 2, "Ed-MFE": 3, "1-precision": 4, "1-recall": 5, "Edef": 6}
 
     def mc_run(self, prob, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, flags, rng_state, state,
-               counters, best, L_const=504.12):
+               counters, best, L_const=504.12, subopt_e=None):
         """n_iter Monte-Carlo iterations of all replicas in native code (drna_mc_run).  `state` holds the arrays seqs, mfe_ss
-        (uint8 R x L), score, mcc1, Epf, Ed (float64 R); `best` holds seq, ss (uint8 L) and vals (float64 4); all updated in place."""
+        (uint8 R x L), score, mcc1, Epf, Ed (float64 R); `best` holds seq, ss (uint8 L) and vals (float64 4); all updated in place.
+        With `subopt_e` (float64 R, in/out: the second-best energy of every replica's state, kcal/mol) the loop runs the
+        negative-design step (drna_mc_run_nd) and `best["vals"]` holds a fifth value, the best state's subopt_e."""
         pk = getattr(prob, "_native_pack", None)
         if pk is None:
             HostKernels._pack(prob)
@@ -287,33 +293,46 @@ class Engine:
         sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
         tt = np.ascontiguousarray(temps, dtype=np.float64)
         p = lambda a: a.ctypes.data
-        self._check(self._L.drna_mc_run(self._h, R, L, int(n_iter), prob.sec_struct.encode("ascii"), p(partner), p(am), p(snake_of),
-                                        len(prob.snakes), p(off), p(nodes), p(nst), p(chars), p(sh), int(n_shelves), float(tm_max),
-                                        float(tm_min), int(bool(targeted)), p(tt), float(L_const), len(ids), p(ids), p(ws), int(flags),
-                                        p(rng_state), p(state["seqs"]), p(state["mfe_ss"]), p(state["score"]), p(state["mcc1"]),
-                                        p(state["Epf"]), p(state["Ed"]), p(counters), p(best["seq"]), p(best["ss"]), p(best["vals"])))
+        args = [self._h, R, L, int(n_iter), prob.sec_struct.encode("ascii"), p(partner), p(am), p(snake_of),
+                len(prob.snakes), p(off), p(nodes), p(nst), p(chars), p(sh), int(n_shelves), float(tm_max),
+                float(tm_min), int(bool(targeted)), p(tt), float(L_const), len(ids), p(ids), p(ws), int(flags),
+                p(rng_state), p(state["seqs"]), p(state["mfe_ss"]), p(state["score"]), p(state["mcc1"]),
+                p(state["Epf"]), p(state["Ed"]), p(counters), p(best["seq"]), p(best["ss"]), p(best["vals"])]
+        if subopt_e is None:
+            self._check(self._L.drna_mc_run(*args))
+        else:
+            assert subopt_e.dtype == np.float64 and subopt_e.shape == (R,) and subopt_e.flags.c_contiguous
+            assert best["vals"].shape == (5,)
+            self._check(self._L.drna_mc_run_nd(*args, p(subopt_e)))
 
     def mc_run_cofold(self, prob, oligo_state, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state,
-                      state, counters, best, L_const=504.12):
+                      state, counters, best, L_const=504.12, subopt_e=None):
         """:meth:`mc_run` for a two-strand ``design.DesignProblem`` (drna_mc_run_cofold).  The strings of `state` (seqs, mfe_ss:
         uint8 R x (L + 1)) and of `best` carry the '&'; `state` also holds oligo_fraction and bonus (float64 R), `best["vals"]` six
-        values (1-MCC, score, Epf, Ed, oligo_fraction, bonus); set_targets() holds the target without the '&'."""
+        values (1-MCC, score, Epf, Ed, oligo_fraction, bonus); set_targets() holds the target without the '&'.  With `subopt_e`
+        (float64 R, in/out) the loop runs the negative-design step (drna_mc_run_cofold_nd) and `best["vals"]` holds a seventh
+        value, the best state's subopt_e."""
         R, Ls = state["seqs"].shape
         cut = prob.sec_struct.index("&")
         assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
-        assert best["vals"].shape == (6,)
+        assert best["vals"].shape == ((6,) if subopt_e is None else (7,))
         am = co_allowed_mask(prob)
         ids = np.array([self.TERM_IDS[n] for n, _ in scoring_f], dtype=np.int32)
         ws = np.array([w for _, w in scoring_f], dtype=np.float64)
         sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
         tt = np.ascontiguousarray(temps, dtype=np.float64)
         p = lambda a: a.ctypes.data
-        self._check(self._L.drna_mc_run_cofold(self._h, R, Ls - 1, cut, int(n_iter), prob.sec_struct.encode("ascii"), p(am),
-                                               OLIGO_STATES[oligo_state], p(sh), int(n_shelves), float(tm_max), float(tm_min),
-                                               int(bool(targeted)), p(tt), float(L_const), len(ids), p(ids), p(ws), p(rng_state),
-                                               p(state["seqs"]), p(state["mfe_ss"]), p(state["score"]), p(state["mcc1"]),
-                                               p(state["Epf"]), p(state["Ed"]), p(state["oligo_fraction"]), p(state["bonus"]),
-                                               p(counters), p(best["seq"]), p(best["ss"]), p(best["vals"])))
+        args = [self._h, R, Ls - 1, cut, int(n_iter), prob.sec_struct.encode("ascii"), p(am),
+                OLIGO_STATES[oligo_state], p(sh), int(n_shelves), float(tm_max), float(tm_min),
+                int(bool(targeted)), p(tt), float(L_const), len(ids), p(ids), p(ws), p(rng_state),
+                p(state["seqs"]), p(state["mfe_ss"]), p(state["score"]), p(state["mcc1"]),
+                p(state["Epf"]), p(state["Ed"]), p(state["oligo_fraction"]), p(state["bonus"]),
+                p(counters), p(best["seq"]), p(best["ss"]), p(best["vals"])]
+        if subopt_e is None:
+            self._check(self._L.drna_mc_run_cofold(*args))
+        else:
+            assert subopt_e.dtype == np.float64 and subopt_e.shape == (R,) and subopt_e.flags.c_contiguous
+            self._check(self._L.drna_mc_run_cofold_nd(*args, p(subopt_e)))
 
     def subopt_energy(self, seqs, want_both=False):
         """Energy (dcal/mol) of the second-best structure of each sequence as the reference's -nd on path takes it from

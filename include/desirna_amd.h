@@ -218,6 +218,10 @@ int drna_last_edef_timing(const drna_engine *e, float out[2]);
  * >= 32 sequences then goes in two halves on two streams so that one half's traceback runs under the other's fill; 1 = one part.
  * "cofold_lds" (default 1): drna_cofold_batch and drna_mc_run_cofold fold pairs of at most 64 nt ("cofold_lds_max" reads the bound)
  * with every table in LDS (fold_cofold_lds.hpp); 0 = the general co-fold kernels.  Results are bit-identical either way.
+ * "subopt_lds" (default 1): drna_subopt_energy_batch, drna_cofold_subopt_energy_batch and the negative-design step of
+ * drna_mc_run_nd / drna_mc_run_cofold_nd fold sequences (pairs: both strands together) of at most "subopt_lds_max" nucleotides
+ * (read-only, 79) with their three two-best tables in LDS (fold_subopt_lds.hpp); 0 = the general kernels.  E2 and E12 are
+ * bit-identical either way.
  */
 int drna_set_option(drna_engine *e, const char *name, int value);
 
@@ -346,6 +350,34 @@ int drna_mc_run_cofold(drna_engine *e, int R, int L, int cut, int n_iter, const 
                        const double *temps, double Lconst, int n_terms, const int32_t *term_id, const double *term_w,
                        uint32_t *rng_state, char *seqs, char *mfe_ss, double *score, double *mcc1, double *Epf, double *Ed,
                        double *oligo_frac, double *bonus, int64_t *counters, char *best_seq, char *best_ss, double *best);
+
+/*
+ * Negative design (-nd on; utils/energy_scores.py:104-108) in the native loops.  drna_mc_run_nd and drna_mc_run_cofold_nd are
+ * drna_mc_run and drna_mc_run_cofold with one more step between the scoring of the R proposals and the Metropolis test: the
+ * proposals whose 1 - MCC is exactly 0 (H of them) get their second-best fold in one launch of H workgroups (drna_subopt_energy_batch
+ * / drna_cofold_subopt_energy_batch rules, option "subopt_lds") and lose E2 / 100 - Epf.  H = 0 launches nothing.  Order of
+ * additions: the -sf sum, the alternative-structure term, the negative-design term and, for two strands, only then the oligomer /
+ * monomer-fraction bonus.  The random draws are those of the plain entry points, so a run in which no proposal is ever solved
+ * returns the same arrays bit for bit.
+ *   subopt_e   R doubles, in/out, kcal/mol: the second-best energy that belongs to each replica's current state (0 where that
+ *              state is unsolved or no second structure lies within 49 kcal/mol); travels with an accepted state.  NULL is
+ *              DRNA_ERR_ARG
+ *   best       one value more than in the plain entry point: best[4] (two strands: best[6]) = subopt_e of the best state
+ * New symbols: no existing signature changes, DRNA_ABI_VERSION stays 3.
+ */
+int drna_mc_run_nd(drna_engine *e, int R, int L, int n_iter, const char *target, const int32_t *partner,
+                   const unsigned char *allowed_mask, const int32_t *snake_of, int n_snakes, const int32_t *snake_off,
+                   const int32_t *snake_nodes, const int32_t *snake_nstates, const char *snake_states,
+                   const int32_t *shelf_index, int n_shelves, double tm_max, double tm_min, int targeted, const double *temps,
+                   double Lconst, int n_terms, const int32_t *term_id, const double *term_w, uint32_t flags,
+                   uint32_t *rng_state, char *seqs, char *mfe_ss, double *score, double *mcc1, double *Epf, double *Ed,
+                   int64_t *counters, char *best_seq, char *best_ss, double *best, double *subopt_e);
+int drna_mc_run_cofold_nd(drna_engine *e, int R, int L, int cut, int n_iter, const char *target, const unsigned char *allowed_mask,
+                          int oligo_state, const int32_t *shelf_index, int n_shelves, double tm_max, double tm_min, int targeted,
+                          const double *temps, double Lconst, int n_terms, const int32_t *term_id, const double *term_w,
+                          uint32_t *rng_state, char *seqs, char *mfe_ss, double *score, double *mcc1, double *Epf, double *Ed,
+                          double *oligo_frac, double *bonus, int64_t *counters, char *best_seq, char *best_ss, double *best,
+                          double *subopt_e);
 
 #ifdef __cplusplus
 }

@@ -37,9 +37,17 @@ def cofold_edef(eng, seqs):
 
 
 def subopt_energy(eng, seqs):
-    """second-best structure energy of one strand (-nd on, every scoring step)"""
-    eng.subopt_energy(seqs)
-    return {"subopt_ms": eng.last_timing()["mfe"]}
+    """second-best structure energy (-nd on: every solved candidate of a scoring step), one strand or pairs, with the tables in
+    LDS (option subopt_lds = 1) and on the general kernels (0), same process and engine; a sequence beyond subopt_lds_max
+    takes the general kernels either way"""
+    fn = eng.cofold_subopt_energy if "&" in seqs[0] else eng.subopt_energy
+    out = {}
+    for lds in (0, 1):
+        eng.set_option("subopt_lds", lds)
+        fn(seqs)
+        out["subopt_ms_lds%d" % lds] = eng.last_timing()["mfe"]
+    eng.set_option("subopt_lds", 1)
+    return out
 
 
 def subopt_structs(eng, seqs):
@@ -97,7 +105,27 @@ def mc_cofold(eng, seqs):
     return out
 
 
+ND_TARGET = "((((((.((((((((....))))).)).).))))))"                # the reference's 36-nt example
+ND_RESTR = "GCCCCGGCCCCCGGCNNNNGCCGGUGGNGGCGGGGC"                 # initial sequence = a solved one: every iteration folds second-best structures
+
+
+def nd_loop(eng, seqs):
+    """scored sequences per second of a -nd on design (64 replicas x 36 nt from a solved start, 3 exchange steps of 50
+    iterations) through the native loop (drna_mc_run_nd) and through the per-iteration loop"""
+    from desirna_amd import design
+    R = len(seqs)
+    inp = SimpleNamespace(name="nd", sec_struct=ND_TARGET, seq_restr=ND_RESTR, seed_seq=None, alt_sec_struct=None, alt_sec_structs=None)
+    kw = dict(replicas=R, exchange=50, steps=3, seed=3, timelimit=600, negative_design="on", engine=eng, keep_records=False)
+    out = {}
+    for key, native in (("native", True), ("per_iteration", False)):
+        t0 = time.perf_counter()
+        res = design.run_design_fast(inp, native_loop=native, **kw)
+        out["nd_%s_scored_per_s" % key] = res["stats"]["scored"] / (time.perf_counter() - t0)
+    return out
+
+
 PAIRS = ((64, 18, 18), (64, 50, 50), (64, 100, 100))
+SUB_MAX = 79          # SUB_LDS_MAX (fold_subopt_lds.hpp)
 CO_HALF = 32          # CO_LDS_MAX / 2 (fold_cofold_lds.hpp)
 # one round of a section -> (shapes (R, strand lengths ...), seed, a fresh generator per shape, rounds, derived figure)
 SECTIONS = {
@@ -105,7 +133,10 @@ SECTIONS = {
            lambda R, v: ("defects_per_s", R / ((v["inside_ms"] + v["outside_ms"]) * 1e-3))),
     cofold_subopt: (PAIRS, 5, False, 5, lambda R, v: ("ratio", v["cofold_subopt_ms"] / v["cofold_mfe_ms"])),
     cofold_edef: (PAIRS, 5, False, 5, lambda R, v: ("ratio", v["cofold_outside_ms"] / v["cofold_pf_ms"])),
-    subopt_energy: (((64, 36), (64, 100), (64, 200)), 5, False, 5, lambda R, v: ("folds_per_s", R / (v["subopt_ms"] * 1e-3))),
+    subopt_energy: (((64, 36), (64, SUB_MAX), (64, 18, 18), (64, 100), (64, 200)), 5, False, 5,
+                    lambda R, v: ("lds_over_general", v["subopt_ms_lds1"] / v["subopt_ms_lds0"])),
+    nd_loop: (((64, 36),), 5, False, 3,
+              lambda R, v: ("native_over_per_iteration", v["nd_native_scored_per_s"] / v["nd_per_iteration_scored_per_s"])),
     subopt_structs: (((16, 100), (16, 200)), 5, False, 5, lambda R, v: ("ratio", v["kbest8_ms"] / v["kbest4_ms"])),
     cofold_paths: (((64, 18, 18), (64, CO_HALF, CO_HALF), (64, CO_HALF + 1, CO_HALF)), 5, False, 7,
                    lambda R, v: ("lds_over_general", (v["mfe_ms_lds1"] + v["pf_ms_lds1"]) / (v["mfe_ms_lds0"] + v["pf_ms_lds0"]))),
