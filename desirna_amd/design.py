@@ -18,6 +18,11 @@ What is different by design: the R chains advance in LOCK-STEP -- one proposal p
 are statistically equivalent, not draw-for-draw identical: the reference itself is not reproducible across
 processes (it iterates over ``set`` objects of strings, whose order depends on PYTHONHASHSEED).
 
+Two drivers, ``run_design`` (per-replica Python objects, ``energy_scores.ReplicaScorer``) and ``run_design_fast`` (numpy state,
+native proposals / Metropolis, or the whole inner loop in ``Engine.mc_run[_cofold]``), on one frame: ``_setup`` (problem, options,
+shards, ladder, main stream, initial sequence), ``_start``, ``_exchange_step`` (the single all-gather, the swaps, records, stop
+rule) and ``_finish`` exist once; candidates are scored by ``energy_scores.score_arrays`` in both.
+
 Alternative structures: "snake" moves (connected components of the pair graph of target + alternative structures
 switch between their Watson-Crick colourings) as in the reference (:143-388, :1081-1095).
 
@@ -287,6 +292,83 @@ def _sws_reached(simulation_data, num_results, oligo_state):
     return len(top) == num_results and all(r["mcc"] == 0.0 for r in top)
 
 
+def oligo_state_and_pks(sec_struct, dimer="off", oligo="off"):
+    """reference DesiRNA.py:474-485: (oligo_state, pks) of a target from the -d / -oa switches and its bracket families"""
+    if "&" in sec_struct:
+        oligo_state = "homodimer" if dimer == "on" else "heterodimer"
+    else:
+        oligo_state = "avoid" if oligo == "on" else "none"
+    return oligo_state, "on" if set(sec_struct) - set(".()&") else "off"
+
+
+# ---- what run_design and run_design_fast share: set-up, the exchange step after the inner iterations, the final gather.  The
+# drivers differ in their inner iterations and in how they hold the replica state only.
+
+def _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results, shards,
+           dimer="off", oligo="off", subopt="off", acgu=None, keep_records=True):
+    """The run: problem, options, shards, temperature ladder, main stream and initial sequence (the same on every rank)"""
+    prob = DesignProblem(input_file.sec_struct, input_file.seq_restr, input_file.alt_sec_structs, acgu=acgu)
+    oligo_state, pks = oligo_state_and_pks(input_file.sec_struct, dimer, oligo)
+    opts = SimpleNamespace(oligo_state=oligo_state, pks=pks, subopt=subopt, motifs=None, param="1999",
+                           scoring_f=es.parse_scoring_functions(scoring_f))
+    shards = shards or rx.ReplicaShards(replicas, 0, 1)
+    run = SimpleNamespace(prob=prob, opts=opts, shards=shards, local=shards.local, steps=steps, timelimit=timelimit,
+                          stop_when_solved=stop_when_solved, num_results=num_results, keep_records=keep_records, step=0)
+    run.temps = rx.get_rep_temps(replicas, t_min, t_max)       # temperature shelf of EVERY replica, replayed on every rank
+    run.shelves = list(run.temps)
+    # main stream (initial sequence, swap acceptance; DesiRNA.py:659-664): the same on every rank
+    run.main_rng = random.Random(shards.broadcast_seed(2137 + seed if seed else random.random()))
+    # input_file.seed_seq is read but ignored, as in the reference (SURVEY App. C3)
+    run.init = prob.initial_sequence(run.main_rng)
+    return run
+
+
+def _start(run, scores, solved, records):
+    """After the initial sequence is scored: first records, counters, clock; a solved start is made known to every rank"""
+    run.simulation_data = records() if run.keep_records else []        # reference DesiRNA.py:353: one record per replica and step
+    run.stats = dict(acc_mc=0, acc_mc_better=0, rej_mc=0, acc_re=0, rej_re=0, scored=len(run.local))
+    run.t_start = time.time()
+    if run.shards.world > 1:
+        _, ex = run.shards.allgather_scores(scores, extras=[float(solved)])
+        solved = bool(ex[:, 0].any())
+    run.solved = solved
+    run.stop = run.stop_when_solved and solved and run.num_results is None
+
+
+def _next_step(run):
+    if run.stop or (run.steps is not None and run.step >= run.steps):
+        return False
+    run.step += 1
+    return True
+
+
+def _exchange_step(run, scores, any_solved, records):
+    """Replica exchange after the inner iterations: ONE all-gather (this rank's scores + its control flags: solved, time is up
+    -- rank 0's clock decides --, -sws reached), then every rank replays the same swaps on the whole ladder.  `records()` returns
+    this rank's records (sim_step = step * exchange, reference DesiRNA.py:371-375) with the temperatures of run.temps."""
+    flags = [float(any_solved), float(time.time() - run.t_start >= run.timelimit), 0.0]
+    sws = run.stop_when_solved and run.num_results is not None
+    if sws and run.keep_records and run.step % 10 == 0:
+        flags[2] = float(_sws_reached(run.simulation_data + records(), run.num_results, run.opts.oligo_state))
+    all_scores, ex = run.shards.allgather_scores(scores, extras=flags)
+    run.solved = run.solved or bool(ex[:, 0].any())
+    run.temps, acc, _, rej = rx.replica_exchange(list(run.temps), list(all_scores), run.step, run.main_rng)
+    run.stats["acc_re"] += acc
+    run.stats["rej_re"] += rej
+    if run.keep_records:
+        run.simulation_data += records()
+    run.stop = bool(ex[0, 1]) or (run.stop_when_solved and (bool(ex[:, 2].all()) if sws else run.solved))
+
+
+def _finish(run, best):
+    """the best replica of the whole job, on every rank"""
+    if run.shards.world > 1:
+        cands = rx.gather_results({run.shards.rank: best}, run.shards.world)
+        best = min((b for b in cands.values() if b is not None), key=lambda s: (s.mcc, s.scoring_function))
+    run.stats["elapsed_s"] = time.time() - run.t_start
+    return best
+
+
 def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
                device=0, shards=None, scorer=None, progress=None, dimer="off", oligo="off", acgu=None, subopt="off",
@@ -302,48 +384,31 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
     carry ``sim_step = global_step * exchange``; ``stop_when_solved`` with ``num_results`` is the reference's ``-sws on``
     (every 10th step: stop when the best ``num_results`` distinct sequences are all solved), without it the run stops at the
     first solved replica (an extension used by the tests and by the puzzle-set driver)."""
-    prob = DesignProblem(input_file.sec_struct, input_file.seq_restr, input_file.alt_sec_structs, acgu=acgu)
-    pks = "on" if set(input_file.sec_struct) - set(".()&") else "off"
-    if prob.two_strands:
-        oligo_state = "homodimer" if dimer == "on" else "heterodimer"       # reference DesiRNA.py:474-485
-    else:
-        oligo_state = "avoid" if oligo == "on" else "none"
-    opts = SimpleNamespace(oligo_state=oligo_state, pks=pks, subopt=subopt, motifs=None, param="1999",
-                           scoring_f=es.parse_scoring_functions(scoring_f))
-    shards = shards or rx.ReplicaShards(replicas, 0, 1)
-    local = shards.local
-    scorer = scorer or es.ReplicaScorer(input_file, opts, max_replicas=max(1, len(local)), device=device)
-    temps = rx.get_rep_temps(replicas, t_min, t_max)           # temperature shelf of EVERY replica, replayed on every rank
-    shelves = list(temps)
-    # main stream (initial sequence, swap acceptance; DesiRNA.py:659-664): the same on every rank
-    main_rng = random.Random(shards.broadcast_seed(2137 + seed if seed else random.random()))
-    init = prob.initial_sequence(main_rng)
-    # input_file.seed_seq is read but ignored, as in the reference (SURVEY App. C3)
-    cur = scorer.score([init] * len(local)) if local else []
+    run = _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results,
+                 shards, dimer, oligo, subopt, acgu)
+    prob, local = run.prob, run.local
+    scorer = scorer or es.ReplicaScorer(input_file, run.opts, max_replicas=max(1, len(local)), device=device)
+    cur = scorer.score([run.init] * len(local)) if local else []
     for k, r in enumerate(local):
         cur[k].get_replica_num(r + 1)
-        cur[k].get_temp_shelf(temps[r])
+
+    def records():                                            # (also moves the replicas onto their shelves of run.temps)
+        for k, r in enumerate(local):
+            cur[k].get_temp_shelf(run.temps[r])
+            cur[k].get_sim_step(run.step * exchange)
+        return [dict(vars(s)) for s in cur]
+
     best = min(cur, key=lambda s: (s.mcc, s.scoring_function)) if cur else None
-    simulation_data = [dict(vars(s)) for s in cur]            # reference DesiRNA.py:353: one record per replica and exchange step
-    stats = dict(acc_mc=0, acc_mc_better=0, rej_mc=0, acc_re=0, rej_re=0, scored=len(local))
-    t_start = time.time()
-    global_step = 0
-    solved = best is not None and best.mcc == 0.0
-    if shards.world > 1:                                      # a solved start must be known to every rank before the loop
-        _, ex = shards.allgather_scores([s.scoring_function for s in cur], extras=[float(solved)])
-        solved = bool(ex[:, 0].any())
-    stop = stop_when_solved and solved and num_results is None
-    while not stop:
-        if steps is not None and global_step >= steps:
-            break
-        global_step += 1
+    _start(run, [s.scoring_function for s in cur], best is not None and best.mcc == 0.0, records)
+    stats = run.stats
+    while _next_step(run):
         rngs = [random.Random(r) for r in local]              # re-seeded with the replica index every exchange step
         for _ in range(exchange):
             props = []
             for k, r in enumerate(local):
-                shelf = shelves.index(cur[k].temp_shelf)
+                shelf = run.shelves.index(cur[k].temp_shelf)
                 pos = prob.mutation_position(cur[k].mfe_ss, shelf, replicas, tm_max, tm_min, point_mutations == "on", rngs[k])
-                props.append(prob.mutate(cur[k].sequence, pos, rngs[k], oligo_state))
+                props.append(prob.mutate(cur[k].sequence, pos, rngs[k], run.opts.oligo_state))
             cand = scorer.score(props)
             stats["scored"] += len(props)
             for k in range(len(local)):
@@ -351,7 +416,7 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
                 if acc:
                     cand[k].get_replica_num(cur[k].replica_num)
                     cand[k].get_temp_shelf(cur[k].temp_shelf)
-                    cand[k].get_sim_step(global_step * exchange)
+                    cand[k].get_sim_step(run.step * exchange)
                     cur[k] = cand[k]
                     stats["acc_mc"] += 1
                     stats["acc_mc_better"] += int(better)
@@ -359,29 +424,12 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
                         best = cur[k]
                 else:
                     stats["rej_mc"] += 1
-        # replica exchange: ONE all-gather (scores + control flags); all ranks replay the same swaps on the whole ladder
-        flags = [float(any(s.mcc == 0.0 for s in cur)), float(time.time() - t_start >= timelimit), 0.0]
-        for k, r in enumerate(local):
-            cur[k].get_sim_step(global_step * exchange)       # reference DesiRNA.py:371-373: stats.step = global_step * RE_attempt
-        if stop_when_solved and num_results is not None and global_step % 10 == 0:
-            flags[2] = float(_sws_reached(simulation_data + [dict(vars(s)) for s in cur], num_results, oligo_state))
-        all_scores, ex = shards.allgather_scores([s.scoring_function for s in cur], extras=flags)
-        solved = solved or bool(ex[:, 0].any())
-        temps, acc, _, rej = rx.replica_exchange(list(temps), list(all_scores), global_step, main_rng)
-        stats["acc_re"] += acc
-        stats["rej_re"] += rej
-        for k, r in enumerate(local):
-            cur[k].get_temp_shelf(temps[r])
-        simulation_data += [dict(vars(s)) for s in cur]       # reference DesiRNA.py:375
+        _exchange_step(run, [s.scoring_function for s in cur], any(s.mcc == 0.0 for s in cur), records)
         if progress:
-            progress(global_step, best, stats)
-        stop = bool(ex[0, 1]) or (stop_when_solved and (solved if num_results is None else bool(ex[:, 2].all())))
-    if shards.world > 1:                                      # the best replica of the whole job, on every rank
-        cands = rx.gather_results({shards.rank: best}, shards.world)
-        best = min((b for b in cands.values() if b is not None), key=lambda s: (s.mcc, s.scoring_function))
-    stats["elapsed_s"] = time.time() - t_start
-    return {"best": best, "solved": solved, "replicas": cur, "stats": stats, "steps": global_step, "temps": list(temps),
-            "simulation_data": simulation_data, "engine": getattr(scorer, "engine", None)}
+            progress(run.step, best, stats)
+    best = _finish(run, best)
+    return {"best": best, "solved": run.solved, "replicas": cur, "stats": stats, "steps": run.step, "temps": list(run.temps),
+            "simulation_data": run.simulation_data, "engine": getattr(scorer, "engine", None)}
 
 
 def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
@@ -389,7 +437,8 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                     device=0, engine=None, keep_records=True, native_loop=None, shards=None, num_results=None, dimer="off",
                     negative_design="off"):
     """Same loop as :func:`run_design` with the per-replica host work in native code and no per-step Python objects:
-    proposals, SimScore and Metropolis run batched in the C library, the replica state lives in numpy arrays.  The
+    proposals, SimScore and Metropolis run batched in the C library, the replica state lives in numpy arrays (the batch of
+    ``energy_scores.score_arrays``, of which it keeps what ``Engine.mc_run`` holds).  The
     per-replica random streams are the reference's (MT19937 seeded with the replica index at every exchange step, CPython's
     draw mapping: ``host_driver.hpp``), so for a fixed seed this driver and :func:`run_design` walk the same trajectory.
 
@@ -410,201 +459,85 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
     if stop_when_solved and num_results is not None and not keep_records:
         raise ValueError("the -sws rule with num_results ranks the recorded sequences: it needs keep_records=True "
                          "(without records the stop test could never fire and the run would only end at its step / time limit)")
-    prob = DesignProblem(input_file.sec_struct, input_file.seq_restr, input_file.alt_sec_structs)
-    two = prob.two_strands
+    two = "&" in input_file.sec_struct
     if two and input_file.alt_sec_structs:
         raise NotImplementedError("two strands with alternative structures run through run_design (the native two-strand "
                                   "proposer has no snake moves)")
-    oligo_state = ("homodimer" if dimer == "on" else "heterodimer") if two else "none"
-    nd = negative_design == "on"
-    n_alt = len(input_file.alt_sec_structs) if input_file.alt_sec_structs else 0
-    sf = es.parse_scoring_functions(scoring_f)
-    for name, _ in sf:
-        if name not in es.AVAILABLE_SCORING_FUNCTIONS:
-            raise ValueError("%s is not an available option for scoring function. Check your command." % name)
-    shards = shards or rx.ReplicaShards(replicas, 0, 1)
-    local = np.array(shards.local, dtype=np.int64)
-    R, L, Rl = replicas, prob.n, len(shards.local)
+    es.check_scoring_functions(es.parse_scoring_functions(scoring_f))
+    run = _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results,
+                 shards, dimer, keep_records=keep_records)
+    prob, sf, oligo_state, nd = run.prob, run.opts.scoring_f, run.opts.oligo_state, negative_design == "on"
+    local = np.array(run.local, dtype=np.int64)
+    R, L, Rl = replicas, prob.n, len(run.local)
     eng = engine or _engine.Engine(max_R=max(1, Rl), max_L=L - 1 if two else L, device=device)      # L counts the '&'
     hk = _engine.HostKernels()
     eng.set_targets([input_file.sec_struct.replace("&", "")] + list(input_file.alt_sec_structs or []))
-    flags = _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL
-    if set(input_file.sec_struct) - set(".()&"):
-        flags |= _engine.NEED_PK
-    temps = np.array(rx.get_rep_temps(R, t_min, t_max), dtype=np.float64)      # the whole ladder, replayed on every rank
-    shelves = temps.copy()
-    main_rng = random.Random(shards.broadcast_seed(2137 + seed if seed else random.random()))
-    ref_ss = input_file.sec_struct
-    if two:
-        ss1, ss2 = ref_ss.split("&")
-        oligomer = oligo_state == "heterodimer" or ss1 != ss2        # else the monomer-fraction term (reference :110-118)
-        cut = len(ss1)
-        want_edef = any(name == "Edef" for name, _ in sf)
-
-    def with_Ee(a):
-        """(R, L) uint8 strings with the '&' at column cut -> the reference's '&' -> 'Ee' substitution (R, L + 1)"""
-        return np.concatenate([a[:, :cut], np.full((len(a), 1), ord("E"), np.uint8), np.full((len(a), 1), ord("e"), np.uint8),
-                               a[:, cut + 1:]], axis=1)
-
-    def negative_design_term(total, mcc1, Epf, strings, second_best):
-        """ReplicaScorer._negative_design on arrays: total loses subopt_e - Epf where 1 - MCC == 0; returns subopt_e (0 elsewhere)"""
-        sub = np.zeros(len(total))
-        hit = np.nonzero(mcc1 == 0)[0]
-        if nd and len(hit):
-            sub[hit] = second_best([strings(k) for k in hit]) / 100.0
-            total[hit] -= sub[hit] - Epf[hit]
-        return sub
-
-    def score_two(seqs_u8):
-        """ReplicaScorer._score_two_strands on arrays: (total, 1-MCC, structures, Epf = FAB, Ed, oligo_fraction, bonus, subopt_e)"""
-        seqs = [bytes(r).decode() for r in seqs_u8]
-        out = eng.cofold_batch(seqs, _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL)
-        ss = np.frombuffer("".join(out["mfe_ss"]).encode(), dtype=np.uint8).reshape(len(seqs), L).copy()
-        mcc, rec, prec = hk.simscore(ref_ss.replace("&", "Ee"), with_Ee(ss))
-        Epf = np.array(out["FAB"], dtype=np.float64)
-        ed = out["Ed"][:, 0] / 100.0
-        terms = {"Ed-Epf": lambda: ed - Epf, "1-MCC": lambda: (1 - mcc) * 10, "sln_Epf": lambda: (Epf + 0.3759 * L + 5.7534) / 10,
-                 "Ed-MFE": lambda: ed - out["Emfe"] / 100.0, "1-precision": lambda: (1 - prec) * 10,
-                 "1-recall": lambda: (1 - rec) * 10, "Edef": lambda: eng.cofold_ensemble_defect(seqs)}
-        total = np.zeros(len(seqs))
-        for name, w in sf:
-            total += terms[name]() * w
-        frac = np.array([float(es.oligo_fraction(out["FA"][k], out["FB"][k], out["FcAB"][k])) for k in range(len(seqs))])
-        bonus = np.array([float(es.kTlog_oligo_fraction(f) if oligomer else es.kTlog_monomer_fraction(f)) for f in frac])
-        sub = negative_design_term(total, 1 - mcc, Epf, lambda k: seqs[k], lambda hit: eng.cofold_subopt_energy(hit))      # before the bonus
-        return total + bonus, 1 - mcc, ss, Epf, ed, frac, bonus, sub
-
-    def score(seqs_u8):
-        if two:
-            return score_two(seqs_u8)
-        Epf, Emfe, ss, Ed = eng.score_batch_arrays(seqs_u8, flags)
-        mcc, rec, prec = hk.simscore(ref_ss, ss)
-        ed = Ed[:, 0] / 100.0
-        total = np.zeros(len(Epf))
-        for name, w in sf:
-            if name == "Ed-Epf":
-                total += (ed - Epf) * w
-            elif name == "1-MCC":
-                total += (1 - mcc) * 10 * w
-            elif name == "sln_Epf":
-                total += (Epf + 0.3759 * L + 5.7534) / 10 * w
-            elif name == "Ed-MFE":
-                total += (ed - Emfe / 100.0) * w
-            elif name == "1-precision":
-                total += (1 - prec) * 10 * w
-            elif name == "1-recall":
-                total += (1 - rec) * 10 * w
-            elif name == "Edef":
-                total += eng.ensemble_defect_arrays(seqs_u8) * w
-        if n_alt:                                                 # reference energy_scores.py:98-102
-            total += Ed[:, 1:].sum(axis=1) / 100.0 / n_alt - Epf
-        sub = negative_design_term(total, 1 - mcc, Epf, lambda k: bytes(seqs_u8[k]).decode(), lambda hit: eng.subopt_energy(hit))
-        return total, 1 - mcc, ss, Epf, ed, None, None, sub
-
-    init = prob.initial_sequence(main_rng)
-    cur = np.tile(np.frombuffer(init.encode(), dtype=np.uint8), (max(1, Rl), 1)).copy()
-    cur_score, cur_mcc, cur_ss, cur_epf, cur_ed, cur_frac, cur_bonus, cur_sub = score(cur)
+    score = lambda seqs_u8: es.score_arrays(eng, hk, input_file.sec_struct, sf, seqs_u8, oligo_state, run.opts.pks, nd)
+    # the replica state: the arrays of the scored batch that Engine.mc_run[_cofold] holds, under its names
+    b = score(np.tile(np.frombuffer(run.init.encode(), dtype=np.uint8), (max(1, Rl), 1)))
+    keys = ["seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"] + ["oligo_fraction", "bonus"] * two + ["subopt_e"] * nd
+    cur = SimpleNamespace(**{k: np.array(getattr(b, k), dtype=np.uint8 if k in keys[:2] else np.float64) for k in keys})
+    # fields of `best`; after the strings, in the order of mc_run's best["vals"] (esubopt_minus_Epf follows from them)
+    fields = (["sequence", "mfe_ss", "mcc", "scoring_function", "Epf", "edesired"] + ["oligo_fraction", "oligomer_bonus"] * two
+              + ["subopt_e", "esubopt_minus_Epf"] * nd)
+    vals = [f for f in fields[2:] if f != "esubopt_minus_Epf"]
 
     def best_of(k):
-        b = dict(sequence=cur[k].tobytes().decode(), mfe_ss=cur_ss[k].tobytes().decode(), mcc=float(cur_mcc[k]),
-                 scoring_function=float(cur_score[k]), Epf=float(cur_epf[k]), edesired=float(cur_ed[k]))
-        if two:
-            b.update(oligo_fraction=float(cur_frac[k]), oligomer_bonus=float(cur_bonus[k]))
-        if nd:
-            b.update(subopt_e=float(cur_sub[k]), esubopt_minus_Epf=float(cur_sub[k] - cur_epf[k]) if cur_mcc[k] == 0 else 0.0)
-        return b
+        sc = es.record(cur, k)
+        return SimpleNamespace(**{f: getattr(sc, f) if f in fields[:2] else float(getattr(sc, f)) for f in fields})
 
-    best = best_of(int(np.lexsort((cur_score, cur_mcc))[0]))
-    stats = dict(acc_mc=0, acc_mc_better=0, rej_mc=0, acc_re=0, rej_re=0, scored=Rl)
-
-    def records(step_no):
+    def records():
         out = []
         for k in range(Rl):
-            sc = es.ScoreSeq(cur[k].tobytes().decode())
-            sc.scoring_function = float(cur_score[k])
+            sc = es.record(cur, k)
             sc.get_replica_num(int(local[k]) + 1)
-            sc.get_temp_shelf(float(temps[local[k]]))
-            sc.get_sim_step(step_no)
-            sc.get_Epf(float(cur_epf[k]))
-            sc.get_edesired(float(cur_ed[k]))
-            sc.get_edesired_minus_Epf(sc.Epf, sc.edesired)
-            sc.mcc = float(cur_mcc[k])
-            sc.get_mfe_ss(cur_ss[k].tobytes().decode())
-            if two:
-                sc.oligo_fraction = float(cur_frac[k])
-                sc.oligomer_bonus = float(cur_bonus[k])
-            if nd and cur_mcc[k] == 0:
-                sc.get_subopt_e(float(cur_sub[k]))
-                sc.get_esubopt_minus_Epf(sc.Epf, sc.subopt_e)
+            sc.get_temp_shelf(float(run.temps[local[k]]))
+            sc.get_sim_step(run.step * exchange)          # reference: stats.step = global_step * RE_attempt
             out.append(dict(vars(sc)))
         return out
 
-    simulation_data = records(0) if keep_records else []
+    best = best_of(int(np.lexsort((cur.score, cur.mcc1))[0]))
+    _start(run, cur.score[:Rl], best.mcc == 0.0, records)
+    stats = run.stats
     if native_loop is None:
         native_loop = True
     native_loop = native_loop and all(name in eng.TERM_IDS for name, _ in sf)   # (every -sf term, Edef included, has a native id)
-    if two:
-        cur_frac = np.ascontiguousarray(cur_frac, dtype=np.float64); cur_bonus = np.ascontiguousarray(cur_bonus, dtype=np.float64)
-    cur = np.ascontiguousarray(cur); cur_ss = np.ascontiguousarray(cur_ss)
-    cur_score = np.ascontiguousarray(cur_score, dtype=np.float64); cur_mcc = np.ascontiguousarray(cur_mcc, dtype=np.float64)
-    cur_epf = np.ascontiguousarray(cur_epf, dtype=np.float64); cur_ed = np.ascontiguousarray(cur_ed, dtype=np.float64)
-    cur_sub = np.ascontiguousarray(cur_sub, dtype=np.float64)
+    flags = _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL | (_engine.NEED_PK if run.opts.pks == "on" else 0)
     rng_state = np.empty((max(1, Rl), _engine.RNG_WORDS), dtype=np.uint32)
-    t_start = time.time()
-    step = 0
-    solved = best["mcc"] == 0.0
-    if shards.world > 1:
-        _, ex = shards.allgather_scores(cur_score[:Rl], extras=[float(solved)])
-        solved = bool(ex[:, 0].any())
+    shelves = np.array(run.shelves)
     targeted = point_mutations == "on"
-    stop = stop_when_solved and solved and num_results is None
-    while not stop:
-        if steps is not None and step >= steps:
-            break
-        step += 1
+    while _next_step(run):
         hk.rng_seed(local if Rl else [0], out=rng_state)        # random.seed(replica index) at every exchange step (App. C2)
-        tl = temps[local] if Rl else temps[:1]
+        tl = np.array(run.temps, dtype=np.float64)[local if Rl else [0]]
         shelf_idx = np.searchsorted(shelves, tl).astype(np.int32)
         if native_loop and Rl:
             # the whole inner loop of the exchange step in native code (drna_mc_run[_cofold]): one call, no per-iteration Python
-            state = dict(seqs=cur, mfe_ss=cur_ss, score=cur_score, mcc1=cur_mcc, Epf=cur_epf, Ed=cur_ed)
             counters = np.zeros(3, dtype=np.int64)
-            vals = [best["mcc"], best["scoring_function"], best["Epf"], best["edesired"]]
+            nd_kw = dict(subopt_e=cur.subopt_e) if nd else {}
+            bst = dict(seq=np.frombuffer(best.sequence.encode(), dtype=np.uint8).copy(),
+                       ss=np.frombuffer(best.mfe_ss.encode(), dtype=np.uint8).copy(),
+                       vals=np.array([getattr(best, f) for f in vals], dtype=np.float64))
             if two:
-                vals += [best["oligo_fraction"], best["oligomer_bonus"]]
-                state.update(oligo_fraction=cur_frac, bonus=cur_bonus)
-            if nd:
-                vals += [best["subopt_e"]]
-            nd_kw = dict(subopt_e=cur_sub) if nd else {}
-            bst = dict(seq=np.frombuffer(best["sequence"].encode(), dtype=np.uint8).copy(),
-                       ss=np.frombuffer(best["mfe_ss"].encode(), dtype=np.uint8).copy(), vals=np.array(vals, dtype=np.float64))
-            if two:
-                eng.mc_run_cofold(prob, oligo_state, exchange, shelf_idx, R, tm_max, tm_min, targeted, np.ascontiguousarray(tl), sf,
-                                  rng_state, state, counters, bst, **nd_kw)
+                eng.mc_run_cofold(prob, oligo_state, exchange, shelf_idx, R, tm_max, tm_min, targeted, tl, sf, rng_state, vars(cur),
+                                  counters, bst, **nd_kw)
             else:
-                eng.mc_run(prob, exchange, shelf_idx, R, tm_max, tm_min, targeted, np.ascontiguousarray(tl), sf, flags, rng_state,
-                           state, counters, bst, **nd_kw)
-            best = dict(sequence=bst["seq"].tobytes().decode(), mfe_ss=bst["ss"].tobytes().decode(), mcc=float(bst["vals"][0]),
-                        scoring_function=float(bst["vals"][1]), Epf=float(bst["vals"][2]), edesired=float(bst["vals"][3]))
-            if two:
-                best.update(oligo_fraction=float(bst["vals"][4]), oligomer_bonus=float(bst["vals"][5]))
+                eng.mc_run(prob, exchange, shelf_idx, R, tm_max, tm_min, targeted, tl, sf, flags, rng_state, vars(cur), counters, bst,
+                           **nd_kw)
+            best = SimpleNamespace(sequence=bst["seq"].tobytes().decode(), mfe_ss=bst["ss"].tobytes().decode(),
+                                   **{f: float(v) for f, v in zip(vals, bst["vals"])})
             if nd:
-                sub_b = float(bst["vals"][-1])
-                best.update(subopt_e=sub_b, esubopt_minus_Epf=sub_b - best["Epf"] if best["mcc"] == 0 else 0.0)
+                best.esubopt_minus_Epf = best.subopt_e - best.Epf if best.mcc == 0 else 0.0
             stats["acc_mc"] += int(counters[0]); stats["acc_mc_better"] += int(counters[1]); stats["rej_mc"] += int(counters[2])
             stats["scored"] += Rl * exchange
         for _ in range(0 if (native_loop or not Rl) else exchange):
             if two:
-                prop = hk.propose_co(prob, oligo_state, cur, cur_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
+                prop = hk.propose_co(prob, oligo_state, cur.seqs, cur.mfe_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
             else:
-                prop = hk.propose_alt(prob, cur, cur_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
-            p_score, p_mcc, p_ss, p_epf, p_ed, p_frac, p_bonus, p_sub = score(prop)
-            acc, better = hk.metropolis(cur_score, p_score, tl, rng_state)
-            cur[acc] = prop[acc]; cur_ss[acc] = p_ss[acc]
-            cur_score[acc] = p_score[acc]; cur_mcc[acc] = p_mcc[acc]; cur_epf[acc] = p_epf[acc]; cur_ed[acc] = p_ed[acc]
-            cur_sub[acc] = p_sub[acc]
-            if two:
-                cur_frac[acc] = p_frac[acc]; cur_bonus[acc] = p_bonus[acc]
+                prop = hk.propose_alt(prob, cur.seqs, cur.mfe_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
+            p = score(prop)
+            acc, better = hk.metropolis(cur.score, p.score, tl, rng_state)
+            for k in keys:
+                getattr(cur, k)[acc] = getattr(p, k)[acc]
             na = int(acc.sum())
             stats["acc_mc"] += na
             stats["acc_mc_better"] += int((acc & better).sum())
@@ -612,27 +545,12 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
             stats["scored"] += Rl
             # the best state is tracked replica by replica in replica order, like the native loop (first strictly better wins)
             for kb in np.nonzero(acc)[0]:
-                if (cur_mcc[kb], cur_score[kb]) < (best["mcc"], best["scoring_function"]):
+                if (cur.mcc1[kb], cur.score[kb]) < (best.mcc, best.scoring_function):
                     best = best_of(kb)
-        # ONE collective per exchange step: scores + (solved, time is up); rank 0's clock decides the time limit
-        ctl = [float(bool(Rl) and bool((cur_mcc[:Rl] == 0.0).any())), float(time.time() - t_start >= timelimit), 0.0]
-        if stop_when_solved and num_results is not None and keep_records and step % 10 == 0:      # the reference's -sws rule
-            ctl[2] = float(_sws_reached(simulation_data + records(step * exchange), num_results, oligo_state))
-        all_scores, ex = shards.allgather_scores(cur_score[:Rl], extras=ctl)
-        solved = solved or bool(ex[:, 0].any())
-        new_temps, a, _, rj = rx.replica_exchange(list(temps), list(all_scores), step, main_rng)
-        temps = np.array(new_temps, dtype=np.float64)
-        stats["acc_re"] += a
-        stats["rej_re"] += rj
-        if keep_records:
-            simulation_data += records(step * exchange)          # reference: stats.step = global_step * RE_attempt
-        stop = bool(ex[0, 1]) or (stop_when_solved and (solved if num_results is None else bool(ex[:, 2].all())))
-    if shards.world > 1:
-        cands = rx.gather_results({shards.rank: best if Rl else None}, shards.world)
-        best = min((b for b in cands.values() if b is not None), key=lambda b: (b["mcc"], b["scoring_function"]))
-    stats["elapsed_s"] = time.time() - t_start
-    return {"best": SimpleNamespace(**best), "solved": solved, "stats": stats, "steps": step, "simulation_data": simulation_data,
-            "engine": eng, "temps": [float(t) for t in temps], "local": [int(r) for r in local],
+        _exchange_step(run, cur.score[:Rl], bool(Rl) and bool((cur.mcc1[:Rl] == 0.0).any()), records)
+    best = _finish(run, best if Rl else None)
+    return {"best": best, "solved": run.solved, "stats": stats, "steps": run.step, "simulation_data": run.simulation_data,
+            "engine": eng, "temps": [float(t) for t in run.temps], "local": [int(r) for r in local],
             "used_native_loop": bool(native_loop)}
 
 
@@ -702,14 +620,13 @@ def main(argv=None):
         from . import outputs
         os.makedirs(a.outdir, exist_ok=True)
         sf = es.parse_scoring_functions(a.scoring_f)
-        pks = "on" if set(inp.sec_struct) - set(".()&") else "off"
+        oligo_state, pks = oligo_state_and_pks(inp.sec_struct, a.dimer, a.oligo)
         outname = outputs.get_outname(os.path.basename(a.name), a.replicas, a.exchange, a.timlim, pks, "off", a.t_min, a.t_max,
                                       "1999", sf, "off", "off", a.pm)
         st = res["stats"]
         stats = SimpleNamespace(step=st["acc_mc"] + st["rej_mc"], global_step=res["steps"], acc_mc_step=st["acc_mc"],
                                 acc_mc_better_e=st["acc_mc_better"], rej_mc_step=st["rej_mc"], acc_re_step=st["acc_re"],
                                 rej_re_step=st["rej_re"])
-        oligo_state = ("homodimer" if a.dimer == "on" else "heterodimer") if "&" in inp.sec_struct else ("avoid" if a.oligo == "on" else "none")
         outputs.write_all(res["simulation_data"], inp.name, os.path.basename(a.name), outname, stats, st["elapsed_s"], a.timlim,
                           time.strftime("%Y%m%d.%H%M%S"), num_results=a.num_results, directory=a.outdir,
                           alt_sec_structs=list(inp.alt_sec_structs or []) or None, engine=res.get("engine"),

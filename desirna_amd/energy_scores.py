@@ -4,12 +4,18 @@ Counterpart of the reference's ``utils/energy_scores.py``: ``score_sequence`` (:
 ``get_mfe_e_ss`` (:128-159) and ``ScoreSeq`` (:162-450).  The ``-sf`` plug-in surface is unchanged:
 the same term names (``Ed-Epf``, ``1-MCC``, ``sln_Epf``, ``Ed-MFE``, ``1-precision``, ``1-recall``,
 ``Edef``) with the same weights and x10 factors (:376-398), the alt-structure term (:98-102) and the
-motif bonus (:121-123, :443-450).  What changes is where the numbers come from: one
-``Engine.score_batch`` call returns Epf, the MFE (or pk-annotated) structure, the MFE energy and
-E(target), E(alt targets) for every replica of the batch, instead of 3-8 ViennaRNA calls per
-sequence inside a forked worker.
+motif bonus (:121-123, :443-450).  What changes is where the numbers come from: one engine call returns
+Epf, the MFE (or pk-annotated) structure, the MFE energy and E(target), E(alt targets) for every replica
+of the batch, instead of 3-8 ViennaRNA calls per sequence inside a forked worker.
 
-``Edef`` is served by ``Engine.ensemble_defect`` (inside + outside recursion on the GPU), for two strands by
+There is ONE scorer and it works on arrays: ``SF_TERMS`` is the ``-sf`` table (name, native id, formula),
+:func:`score_arrays` scores an (R, L) uint8 batch of candidates -- one strand, two strands, alternative structures,
+``-nd on`` -- in the reference's order of additions, and :func:`record` turns one row of its result into a ``ScoreSeq``.
+``ReplicaScorer.score`` (``design.run_design``) is ``record`` over every row, plus ``-oa`` and the motifs;
+``design.run_design_fast`` keeps the arrays as its replica state and calls ``record`` for its records only.  The native
+loop (``mc_loop`` in ``csrc/engine.hip``) is the same sum in C, on the same term ids.
+
+``Edef`` is served by ``Engine.ensemble_defect_arrays`` (inside + outside recursion on the GPU), for two strands by
 ``Engine.cofold_ensemble_defect`` (the outside recursion under the co-fold rules; no golden in the reference: checked against
 exhaustive enumeration); two-strand ``Ed-MFE`` takes the co-fold MFE energy.
 
@@ -21,8 +27,11 @@ Two strands (``oligo_state`` heterodimer / homodimer, and ``avoid`` = ``-o on``)
 dynamic programme on the GPU; no golden in the reference: checked against exhaustive enumeration), for two strands from
 ``Engine.cofold_subopt_energy`` (the same programme under the co-fold rules).
 """
+from types import SimpleNamespace
+
+import numpy as np
+
 from . import engine as _engine
-from .sim_score import batch_metrics
 
 # reference utils/dimer_multichain_energy.py:24-28
 KB = 0.001987204259
@@ -33,23 +42,44 @@ CONC = 1e-3
 
 def oligo_fraction(FA, FB, FcAB):
     """reference dimer_multichain_energy.oligo_fraction (:30-45): fraction of strands bound in the dimer at 1 mM."""
-    import numpy as np
     dF = FcAB - FA - FB
     rhs = CONC / RHO * np.exp(-dF / (KB * TEMP))
     return 1 - (np.sqrt(1 + 4 * rhs) - 1) / (2 * rhs)
 
 
 def kTlog_oligo_fraction(frac):
-    import numpy as np
     return -KB * TEMP * np.log(frac)
 
 
 def kTlog_monomer_fraction(frac):
-    import numpy as np
     return -KB * TEMP * np.log(1 - frac)
 
 
-AVAILABLE_SCORING_FUNCTIONS = ['Ed-Epf', '1-MCC', 'sln_Epf', 'Ed-MFE', '1-precision', '1-recall', 'Edef']
+# THE -sf table (reference :376-398): name, native id (the case mc_loop switches on, = Engine.TERM_IDS), and the term's value from
+# v.Epf, v.Ed = E(target), v.Emfe (kcal/mol), the rounded v.mcc1 = 1 - MCC, v.recall1, v.precision1, the ensemble defect v.Edef and
+# the string length v.n (two strands: with the '&'): a batch's arrays (score_arrays) or one record's numbers (ScoreSeq)
+SF_TERMS = (("Ed-Epf", 0, lambda v: v.Ed - v.Epf), ("1-MCC", 1, lambda v: v.mcc1 * 10),
+            ("sln_Epf", 2, lambda v: (v.Epf + 0.3759 * v.n + 5.7534) / 10), ("Ed-MFE", 3, lambda v: v.Ed - v.Emfe),
+            ("1-precision", 4, lambda v: v.precision1 * 10), ("1-recall", 5, lambda v: v.recall1 * 10),
+            ("Edef", 6, lambda v: v.Edef))
+AVAILABLE_SCORING_FUNCTIONS = [name for name, _, _ in SF_TERMS]
+_TERM = {name: value for name, _, value in SF_TERMS}
+
+
+def check_scoring_functions(scoring_f):
+    for function, _ in scoring_f:
+        if function not in _TERM:
+            raise ValueError("%s is not an available option for scoring function. Check your command." % function)
+
+
+def sf_sum(scoring_f, v):
+    """the -sf sum, from 0, in -sf order, of the values `v` (see SF_TERMS); a name that is not in the table adds nothing, as in
+    the reference"""
+    total = 0
+    for function, weight in scoring_f:
+        if function in _TERM:
+            total += _TERM[function](v) * weight
+    return total
 
 
 def parse_scoring_functions(scoring_f_str, first_term_only=True):
@@ -79,11 +109,6 @@ class ScoreSeq:
                ("edesired_minus_Epf", 0), ("Epf", 0), ("edesired", 0), ("mcc", 0), ("mcc_alt", 0), ("mfe_ss", None),
                ("subopt_e", 0), ("esubopt_minus_Epf", 0), ("sln_Epf", 0), ("MFE", 0), ("edesired_minus_MFE", 0), ("recall", 0),
                ("precision", 0), ("edesired2", 0), ("edesired2_minus_Epf", 0))
-    # -sf term -> value taken from the record (reference :376-398); a name that is not listed contributes nothing, as there
-    _TERMS = {"Ed-Epf": lambda r: r.edesired_minus_Epf, "1-MCC": lambda r: r.mcc * 10, "sln_Epf": lambda r: r.sln_Epf,
-              "Ed-MFE": lambda r: r.edesired_minus_MFE, "1-precision": lambda r: r.precision * 10,
-              "1-recall": lambda r: r.recall * 10, "Edef": lambda r: r.ensemble_defect}
-
     def __init__(self, sequence):
         for name, value in self._SCHEMA:
             setattr(self, name, value)
@@ -99,12 +124,9 @@ class ScoreSeq:
         self.scoring_function = self.scoring_function - self.esubopt_minus_Epf
 
     def get_scoring_function(self, scoring_f):
-        total = 0
-        for function, weight in scoring_f:
-            term = self._TERMS.get(function)
-            if term is not None:
-                total += term(self) * weight
-        self.scoring_function = total
+        self.scoring_function = sf_sum(scoring_f, SimpleNamespace(
+            Epf=self.Epf, Ed=self.edesired, Emfe=self.MFE, mcc1=self.mcc, recall1=self.recall, precision1=self.precision,
+            Edef=getattr(self, "ensemble_defect", None), n=len(self.sequence)))
 
     def get_scoring_function_w_alt_ss(self):
         self.scoring_function = self.scoring_function + self.edesired2_minus_Epf
@@ -153,8 +175,101 @@ def score_motifs(seq, sim_options):
     return motif_score
 
 
+def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pks="off", nd=False):
+    """THE scorer (reference score_sequence(), :70-118, for a whole batch): `eng` an ``engine.Engine`` whose targets are
+    sec_struct (+ the alternative structures) without the '&', `hk` an ``engine.HostKernels``, seqs_u8 the (R, L) uint8 candidates
+    (two strands -- oligo_state heterodimer / homodimer --: with the '&' column).  Returns the batch as arrays, named like the
+    state of ``Engine.mc_run``: seqs, mfe_ss (uint8 R x L), score, mcc1, recall1, precision1, Epf (two strands: FAB), Ed, and where
+    they apply (else None) sln_Epf, Emfe (``-sf Ed-MFE``; kcal/mol), Edef, Ed2 (mean E(alternative structures)), subopt_e (`nd`;
+    0 where 1 - MCC != 0), oligo_fraction, bonus (two strands).
+
+    The reference's order of additions: the -sf sum; + (Ed2 - Epf) with alternative structures, every energy / 100 first, then
+    the sum, then / count (one strand only, as the two-strand scorer always had it); - (subopt_e - Epf) on the candidates with
+    1 - MCC == 0 (`nd`: ONE second-best call for that subset); + the oligomer bonus (hetero-dimer, or homodimer with two different
+    structures) or the monomer-fraction term (two equal structures)."""
+    names = [function for function, _ in scoring_f]
+    two = oligo_state in ("heterodimer", "homodimer")
+    seqs_u8 = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
+    R, L = seqs_u8.shape
+    strings = lambda rows: [bytes(seqs_u8[k]).decode() for k in rows]
+    b = SimpleNamespace(seqs=seqs_u8, n=L, sln_Epf=None, Emfe=None, Edef=None, Ed2=None, subopt_e=None, oligo_fraction=None, bonus=None)
+    ref = sec_struct.replace("&", "Ee")
+    if two:
+        seqs = strings(range(R))
+        out = eng.cofold_batch(seqs, _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL)
+        b.mfe_ss = np.frombuffer("".join(out["mfe_ss"]).encode(), dtype=np.uint8).reshape(R, L).copy()
+        cut = sec_struct.index("&")                       # SimScore on the reference's '&' -> 'Ee' substitution
+        Ee = np.broadcast_to(np.frombuffer(b"Ee", dtype=np.uint8), (R, 2))
+        mcc, rec, prec = hk.simscore(ref, np.concatenate([b.mfe_ss[:, :cut], Ee, b.mfe_ss[:, cut + 1:]], axis=1))
+        b.Epf, Emfe, Ed = np.array(out["FAB"], dtype=np.float64), out["Emfe"], out["Ed"][:, :1]
+    else:
+        flags = _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL | (_engine.NEED_PK if pks == "on" else 0)
+        b.Epf, Emfe, b.mfe_ss, Ed = eng.score_batch_arrays(seqs_u8, flags)
+        mcc, rec, prec = hk.simscore(ref, b.mfe_ss)
+    b.mcc1, b.recall1, b.precision1 = 1 - mcc, 1 - rec, 1 - prec
+    b.Ed = Ed[:, 0] / 100.0
+    if "Ed-MFE" in names:
+        b.Emfe = Emfe / 100.0
+    if "Edef" in names:                                   # reference :93-94
+        b.Edef = eng.cofold_ensemble_defect(seqs) if two else eng.ensemble_defect_arrays(seqs_u8)
+    if "sln_Epf" in names:
+        b.sln_Epf = _TERM["sln_Epf"](b)
+    b.score = np.zeros(R) + sf_sum(scoring_f, b)
+    if Ed.shape[1] > 1:                                   # reference :98-102
+        total = 0
+        for t in range(1, Ed.shape[1]):
+            total = total + Ed[:, t] / 100.0
+        b.Ed2 = total / (Ed.shape[1] - 1)
+        b.score = b.score + (b.Ed2 - b.Epf)
+    if nd:                                                # reference :104-108
+        b.subopt_e = np.zeros(R)
+        hit = np.nonzero(b.mcc1 == 0)[0]
+        if len(hit):
+            b.subopt_e[hit] = (eng.cofold_subopt_energy if two else eng.subopt_energy)(strings(hit)) / 100.0
+            b.score[hit] -= b.subopt_e[hit] - b.Epf[hit]
+    if two:                                               # reference :109-116, utils/dimer_multichain_energy.py
+        ss1, ss2 = sec_struct.split("&")
+        kTlog = kTlog_oligo_fraction if oligo_state == "heterodimer" or ss1 != ss2 else kTlog_monomer_fraction
+        b.oligo_fraction = np.array([float(oligo_fraction(out["FA"][k], out["FB"][k], out["FcAB"][k])) for k in range(R)])
+        b.bonus = np.array([float(kTlog(f)) for f in b.oligo_fraction])
+        b.score = b.score + b.bonus
+    return b
+
+
+def record(b, k):
+    """Row k of a batch of :func:`score_arrays` (or of the arrays ``design.run_design_fast`` keeps of it: what is not there
+    stays at the ScoreSeq default) -> ScoreSeq"""
+    col = lambda name: None if getattr(b, name, None) is None else float(getattr(b, name)[k])
+    sc = ScoreSeq(sequence=bytes(b.seqs[k]).decode())
+    sc.scoring_function = col("score")
+    sc.get_Epf(col("Epf"))
+    sc.get_mfe_ss(bytes(b.mfe_ss[k]).decode())
+    sc.get_edesired(col("Ed"))
+    sc.get_edesired_minus_Epf(sc.Epf, sc.edesired)
+    sc.mcc = col("mcc1")
+    if col("recall1") is not None:
+        sc.recall, sc.precision = col("recall1"), col("precision1")
+    if col("sln_Epf") is not None:
+        sc.get_sln_Epf()
+    if col("Emfe") is not None:
+        sc.get_MFE(col("Emfe"))
+        sc.get_edesired_minus_MFE()
+    if col("Edef") is not None:
+        sc.get_ensemble_defect(col("Edef"))
+    if col("Ed2") is not None:
+        sc.get_edesired2(col("Ed2"))
+        sc.get_edesired2_minus_Epf(sc.Epf, sc.edesired2)
+    if col("subopt_e") is not None and sc.mcc == 0:
+        sc.get_subopt_e(col("subopt_e"))
+        sc.get_esubopt_minus_Epf(sc.Epf, sc.subopt_e)
+    if col("oligo_fraction") is not None:
+        sc.oligo_fraction, sc.oligomer_bonus = col("oligo_fraction"), col("bonus")
+    return sc
+
+
 class ReplicaScorer:
-    """Binds an engine to one design problem (target + alt structures + options) and scores batches."""
+    """Binds an engine to one design problem (target + alt structures + options) and scores batches: :func:`score_arrays` and
+    :func:`record`, plus what only ``design.run_design`` has (-oa on and the motifs)."""
 
     def __init__(self, input_file, sim_options, max_replicas, device=0, engine=None):
         self.oligo_state = getattr(sim_options, "oligo_state", "none")
@@ -167,6 +282,7 @@ class ReplicaScorer:
         L = len(self.target)
         self.engine = engine or _engine.Engine(max_R=max_replicas, max_L=L, device=device,
                                                params=str(getattr(sim_options, "param", "1999")))
+        self.hk = _engine.HostKernels()
         # -oa on folds every candidate against itself (s & s: 2 L nucleotides, reference :411-418): that needs an engine
         # sized for 2 L; the scoring engine stays sized for L (its workspace pitch follows max_L)
         self.dimer_engine = self.engine
@@ -177,68 +293,15 @@ class ReplicaScorer:
         if getattr(input_file, "alt_sec_struct", None) is not None:
             targets += [a.replace("&", "") for a in input_file.alt_sec_structs]
         self.engine.set_targets(targets)
-        self.flags = _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL
-        if getattr(sim_options, "pks", "off") == "on":
-            self.flags |= _engine.NEED_PK
-        for function, _ in sim_options.scoring_f:
-            if function not in AVAILABLE_SCORING_FUNCTIONS:
-                raise ValueError("%s is not an available option for scoring function. Check your command." % function)
-        # reference :93-94: get_ensemble_defect(input_file.sec_struct) whenever 'Edef' is among the -sf terms
-        self.want_edef = any(function == 'Edef' for function, _ in sim_options.scoring_f)
-
-    def _candidate(self, seq, k, out, Epf, metrics, edef):
-        """ScoreSeq of candidate k of a scored batch, up to the -sf terms (reference score_sequence(), :70-96); Epf is the
-        batch's column of ensemble free energies"""
-        sc = ScoreSeq(sequence=seq)
-        sc.get_Epf(float(Epf[k]))
-        sc.get_mfe_ss(out["mfe_ss"][k])
-        sc.get_edesired(int(out["Ed"][k, 0]) / 100.0)
-        sc.get_edesired_minus_Epf(sc.Epf, sc.edesired)
-        mcc, recall, precision = metrics[k]
-        sc.get_precision(precision)
-        sc.get_recall(recall)
-        sc.get_mcc(mcc)
-        for function, _ in self.sim_options.scoring_f:
-            if function == 'sln_Epf':
-                sc.get_sln_Epf()
-            if function == 'Ed-MFE':
-                sc.get_MFE(int(out["Emfe"][k]) / 100.0)
-                sc.get_edesired_minus_MFE()
-            if function == 'Edef':
-                sc.get_ensemble_defect(float(edef[k]))
-        sc.get_scoring_function(self.sim_options.scoring_f)
-        return sc
-
-    def _negative_design(self, seqs, res, second_best):
-        """reference :105-108 (-nd on): for solved candidates (1-MCC == 0) the energy of the first sub-optimal structure, which
-        second_best (Engine.subopt_energy, or Engine.cofold_subopt_energy for two strands) returns for a list of sequences"""
-        hit = [k for k, sc in enumerate(res) if sc.mcc == 0]
-        if hit:
-            e2 = second_best([seqs[k] for k in hit])
-            for k, v in zip(hit, e2):
-                res[k].get_subopt_e(int(v) / 100.0)
-                res[k].get_esubopt_minus_Epf(res[k].Epf, res[k].subopt_e)
-                res[k].get_scoring_function_w_subopt()
+        check_scoring_functions(sim_options.scoring_f)
 
     def score(self, seqs):
         """list of sequences -> list of ScoreSeq (reference score_sequence(), once per replica)."""
-        if self.oligo_state in ("heterodimer", "homodimer"):
-            return self._score_two_strands(list(seqs))
-        out = self.engine.score_batch(list(seqs), self.flags)
-        metrics = batch_metrics(self.input_file.sec_struct.replace("&", "Ee"),
-                                [s.replace("&", "Ee") for s in out["mfe_ss"]])
-        edef = self.engine.ensemble_defect(list(seqs)) if self.want_edef else None
-        res = []
-        for k, seq in enumerate(seqs):
-            sc = self._candidate(seq, k, out, out["Epf"], metrics, edef)
-            if getattr(self.input_file, "alt_sec_struct", None) is not None:
-                energies = [int(e) / 100.0 for e in out["Ed"][k, 1:]]
-                sc.get_edesired2(sum(energies) / len(energies))
-                sc.get_edesired2_minus_Epf(sc.Epf, sc.edesired2)
-                sc.get_scoring_function_w_alt_ss()
-            res.append(sc)
-        if self.subopt:
-            self._negative_design(seqs, res, self.engine.subopt_energy)
+        seqs = list(seqs)
+        b = score_arrays(self.engine, self.hk, self.input_file.sec_struct, self.sim_options.scoring_f,
+                         np.frombuffer("".join(seqs).encode(), dtype=np.uint8).reshape(len(seqs), -1), self.oligo_state,
+                         getattr(self.sim_options, "pks", "off"), self.subopt)
+        res = [record(b, k) for k in range(len(seqs))]
         if self.oligo_state == "avoid":
             # reference get_scoring_function_monomer (:411-418): homodimer of the sequence with itself, monomer fraction bonus
             # (applied before the motif bonus in the reference; both are additive)
@@ -249,34 +312,6 @@ class ReplicaScorer:
                 sc.scoring_function = sc.scoring_function + sc.monomer_bonus
         if getattr(self.sim_options, "motifs", None):
             for seq, sc in zip(seqs, res):
-                sc.update_scoring_function_w_motifs(score_motifs(seq, self.sim_options))
-        return res
-
-    def _score_two_strands(self, seqs):
-        """reference score_sequence() for oligo_state heterodimer / homodimer (:70-118): Epf = pf_dimer()[-1] (FAB), MFE
-        structure of mfe_dimer() with the '&' re-inserted, E(target) of the two-strand evaluation, Ed-MFE against the co-fold MFE energy and
-        Edef in the co-fold ensemble (the reference calls get_MFE / get_ensemble_defect whatever the oligo_state), with -nd on the second-best
-        co-fold energy of the solved candidates, then the oligomer bonus (hetero-dimer, or homodimer with two different
-        structures) or the monomer-fraction term (two equal structures), then the motifs -- the reference's order of additions."""
-        out = self.engine.cofold_batch(seqs, _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL)
-        metrics = batch_metrics(self.input_file.sec_struct.replace("&", "Ee"),
-                                [s.replace("&", "Ee") for s in out["mfe_ss"]])
-        ss1, ss2 = self.input_file.sec_struct.split("&")
-        edef = self.engine.cofold_ensemble_defect(seqs) if self.want_edef else None
-        res = []
-        for k, seq in enumerate(seqs):
-            sc = self._candidate(seq, k, out, out["FAB"], metrics, edef)
-            sc.oligo_fraction = float(oligo_fraction(out["FA"][k], out["FB"][k], out["FcAB"][k]))
-            if self.oligo_state == "heterodimer" or ss1 != ss2:
-                sc.oligomer_bonus = float(kTlog_oligo_fraction(sc.oligo_fraction))
-            else:
-                sc.oligomer_bonus = float(kTlog_monomer_fraction(sc.oligo_fraction))
-            res.append(sc)
-        if self.subopt:                   # on the dimer fold compound, before the oligomer / monomer bonus
-            self._negative_design(seqs, res, self.engine.cofold_subopt_energy)
-        for seq, sc in zip(seqs, res):
-            sc.scoring_function = sc.scoring_function + sc.oligomer_bonus
-            if getattr(self.sim_options, "motifs", None):
                 sc.update_scoring_function_w_motifs(score_motifs(seq, self.sim_options))
         return res
 

@@ -74,8 +74,19 @@ OLIGO_STATES = {"heterodimer": 1, "homodimer": 2}      # oligo_state of drna_pro
 
 
 def co_allowed_mask(prob):
-    """allowed-letter mask of a two-strand design.DesignProblem for the native proposer: bit0 A .. bit3 U, 0 for the '&' column"""
+    """allowed-letter mask of a design.DesignProblem for the native proposers: bit0 A .. bit3 U, 0 for the '&' column of two strands"""
     return np.array([sum(1 << "ACGU".index(c) for c in a if c != "&") for a in prob.allowed], dtype=np.uint8)
+
+
+def _packed(prob):
+    """the arrays of HostKernels._pack, made on first use"""
+    if getattr(prob, "_native_pack", None) is None:
+        HostKernels._pack(prob)
+    return prob._native_pack
+
+
+def _check_rng(rng_state, R):
+    assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
 
 
 class EngineError(RuntimeError):
@@ -106,6 +117,11 @@ def _equal_length(seqs):
     if any(len(s) != L for s in seqs):
         raise ValueError("all sequences of a batch must have the same length")
     return R, L
+
+
+def _as_u8(seqs):
+    """list of equal-length strings -> (R, L) uint8 array of their ASCII letters"""
+    return np.frombuffer("".join(seqs).encode("ascii"), dtype=np.uint8).reshape(_equal_length(seqs))
 
 
 def _split_pairs(seqs):
@@ -191,19 +207,12 @@ class Engine:
         self.n_targets, self.L = len(targets), L
 
     def score_batch(self, seqs, flags=NEED_PF | NEED_MFE | NEED_EVAL):
-        """seqs: list of equal-length strings.  Returns dict(Epf, Emfe, mfe_ss, Ed) (None if not requested);
-        energies in ViennaRNA's units: Epf kcal/mol (float), Emfe / Ed int dcal/mol."""
-        R, L = _equal_length(seqs)
-        sb = "".join(seqs).encode("ascii")
-        Epf = np.zeros(R, dtype=np.float64) if flags & NEED_PF else None
+        """String form of :meth:`score_batch_arrays`: seqs is a list of equal-length strings.  Returns dict(Epf, Emfe, mfe_ss, Ed)
+        (None if not requested); energies in ViennaRNA's units: Epf kcal/mol (float), Emfe / Ed int dcal/mol."""
+        Epf, Emfe, ss, Ed = self.score_batch_arrays(_as_u8(seqs), flags)
         want_mfe = flags & (NEED_MFE | NEED_PK)
-        Emfe = np.zeros(R, dtype=np.int32) if want_mfe else None
-        ss = np.zeros((R, L), dtype=np.uint8) if want_mfe else None
-        Ed = np.zeros((R, max(1, self.n_targets)), dtype=np.int32) if flags & NEED_EVAL else None
-        ptr = lambda a: a.ctypes.data if a is not None else None
-        self._check(self._L.drna_score_batch(self._h, R, L, sb, flags, ptr(Epf), ptr(Emfe), ptr(ss), ptr(Ed)))
-        return {"Epf": Epf, "Emfe": Emfe,
-                "mfe_ss": [bytes(r).decode("ascii") for r in ss] if ss is not None else None, "Ed": Ed}
+        return {"Epf": Epf if flags & NEED_PF else None, "Emfe": Emfe if want_mfe else None,
+                "mfe_ss": [bytes(r).decode("ascii") for r in ss] if want_mfe else None, "Ed": Ed if flags & NEED_EVAL else None}
 
     def score_batch_arrays(self, seqs_u8, flags=NEED_PF | NEED_MFE | NEED_EVAL):
         """Array form for hot host loops: seqs_u8 is an (R, L) uint8 array of ASCII letters; returns
@@ -275,35 +284,39 @@ class Engine:
 
     TERM_IDS = {"Ed-Epf": 0, "1-MCC": 1, "sln_Epf": 2, "Ed-MFE": 3, "1-precision": 4, "1-recall": 5, "Edef": 6}
 
+    def _mc_run(self, name, head, mid, keys, n_vals, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state,
+                state, counters, best, L_const, subopt_e):
+        """drna_mc_run / drna_mc_run_cofold (`name`; with `subopt_e` their _nd forms): `head` are the arguments between R and the
+        shelf indices, `mid` those between the term weights and the random streams, `keys` the arrays of `state` in call order"""
+        R = state["seqs"].shape[0]
+        nd = subopt_e is not None
+        _check_rng(rng_state, R)
+        assert best["vals"].shape == (n_vals + nd,)
+        ids = np.array([self.TERM_IDS[n] for n, _ in scoring_f], dtype=np.int32)
+        ws = np.array([w for _, w in scoring_f], dtype=np.float64)
+        sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
+        tt = np.ascontiguousarray(temps, dtype=np.float64)
+        p = lambda a: a.ctypes.data
+        args = [self._h, R] + head + [p(sh), int(n_shelves), float(tm_max), float(tm_min), int(bool(targeted)), p(tt), float(L_const),
+                                      len(ids), p(ids), p(ws)] + mid + [p(rng_state)] + [p(state[k]) for k in keys] + [
+                                          p(counters), p(best["seq"]), p(best["ss"]), p(best["vals"])]
+        if nd:
+            assert subopt_e.dtype == np.float64 and subopt_e.shape == (R,) and subopt_e.flags.c_contiguous
+            args.append(p(subopt_e))
+        self._check(getattr(self._L, name + "_nd" if nd else name)(*args))
+
     def mc_run(self, prob, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, flags, rng_state, state,
                counters, best, L_const=504.12, subopt_e=None):
         """n_iter Monte-Carlo iterations of all replicas in native code (drna_mc_run).  `state` holds the arrays seqs, mfe_ss
         (uint8 R x L), score, mcc1, Epf, Ed (float64 R); `best` holds seq, ss (uint8 L) and vals (float64 4); all updated in place.
         With `subopt_e` (float64 R, in/out: the second-best energy of every replica's state, kcal/mol) the loop runs the
         negative-design step (drna_mc_run_nd) and `best["vals"]` holds a fifth value, the best state's subopt_e."""
-        pk = getattr(prob, "_native_pack", None)
-        if pk is None:
-            HostKernels._pack(prob)
-            pk = prob._native_pack
-        am, partner, snake_of, off, nodes, nst, chars = pk
-        R, L = state["seqs"].shape
-        assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
-        ids = np.array([self.TERM_IDS[n] for n, _ in scoring_f], dtype=np.int32)
-        ws = np.array([w for _, w in scoring_f], dtype=np.float64)
-        sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
-        tt = np.ascontiguousarray(temps, dtype=np.float64)
+        am, partner, snake_of, off, nodes, nst, chars = _packed(prob)
         p = lambda a: a.ctypes.data
-        args = [self._h, R, L, int(n_iter), prob.sec_struct.encode("ascii"), p(partner), p(am), p(snake_of),
-                len(prob.snakes), p(off), p(nodes), p(nst), p(chars), p(sh), int(n_shelves), float(tm_max),
-                float(tm_min), int(bool(targeted)), p(tt), float(L_const), len(ids), p(ids), p(ws), int(flags),
-                p(rng_state), p(state["seqs"]), p(state["mfe_ss"]), p(state["score"]), p(state["mcc1"]),
-                p(state["Epf"]), p(state["Ed"]), p(counters), p(best["seq"]), p(best["ss"]), p(best["vals"])]
-        if subopt_e is None:
-            self._check(self._L.drna_mc_run(*args))
-        else:
-            assert subopt_e.dtype == np.float64 and subopt_e.shape == (R,) and subopt_e.flags.c_contiguous
-            assert best["vals"].shape == (5,)
-            self._check(self._L.drna_mc_run_nd(*args, p(subopt_e)))
+        head = [state["seqs"].shape[1], int(n_iter), prob.sec_struct.encode("ascii"), p(partner), p(am), p(snake_of),
+                len(prob.snakes), p(off), p(nodes), p(nst), p(chars)]
+        self._mc_run("drna_mc_run", head, [int(flags)], ("seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"), 4, shelf_index, n_shelves,
+                     tm_max, tm_min, targeted, temps, scoring_f, rng_state, state, counters, best, L_const, subopt_e)
 
     def mc_run_cofold(self, prob, oligo_state, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state,
                       state, counters, best, L_const=504.12, subopt_e=None):
@@ -312,27 +325,12 @@ class Engine:
         values (1-MCC, score, Epf, Ed, oligo_fraction, bonus); set_targets() holds the target without the '&'.  With `subopt_e`
         (float64 R, in/out) the loop runs the negative-design step (drna_mc_run_cofold_nd) and `best["vals"]` holds a seventh
         value, the best state's subopt_e."""
-        R, Ls = state["seqs"].shape
-        cut = prob.sec_struct.index("&")
-        assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
-        assert best["vals"].shape == ((6,) if subopt_e is None else (7,))
         am = co_allowed_mask(prob)
-        ids = np.array([self.TERM_IDS[n] for n, _ in scoring_f], dtype=np.int32)
-        ws = np.array([w for _, w in scoring_f], dtype=np.float64)
-        sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
-        tt = np.ascontiguousarray(temps, dtype=np.float64)
-        p = lambda a: a.ctypes.data
-        args = [self._h, R, Ls - 1, cut, int(n_iter), prob.sec_struct.encode("ascii"), p(am),
-                OLIGO_STATES[oligo_state], p(sh), int(n_shelves), float(tm_max), float(tm_min),
-                int(bool(targeted)), p(tt), float(L_const), len(ids), p(ids), p(ws), p(rng_state),
-                p(state["seqs"]), p(state["mfe_ss"]), p(state["score"]), p(state["mcc1"]),
-                p(state["Epf"]), p(state["Ed"]), p(state["oligo_fraction"]), p(state["bonus"]),
-                p(counters), p(best["seq"]), p(best["ss"]), p(best["vals"])]
-        if subopt_e is None:
-            self._check(self._L.drna_mc_run_cofold(*args))
-        else:
-            assert subopt_e.dtype == np.float64 and subopt_e.shape == (R,) and subopt_e.flags.c_contiguous
-            self._check(self._L.drna_mc_run_cofold_nd(*args, p(subopt_e)))
+        head = [state["seqs"].shape[1] - 1, prob.sec_struct.index("&"), int(n_iter), prob.sec_struct.encode("ascii"), am.ctypes.data,
+                OLIGO_STATES[oligo_state]]
+        self._mc_run("drna_mc_run_cofold", head, [], ("seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed", "oligo_fraction", "bonus"), 6,
+                     shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state, state, counters, best, L_const,
+                     subopt_e)
 
     def subopt_energy(self, seqs, want_both=False):
         """Energy (dcal/mol) of the second-best structure of each sequence as the reference's -nd on path takes it from
@@ -369,15 +367,8 @@ class Engine:
         return E, [[raw[(r * K + k) * L:(r * K + k + 1) * L] for k in range(K)] for r in range(R)]
 
     def ensemble_defect(self, seqs, want_bpp=False):
-        """Ensemble defect of each sequence against targets[0] (reference ScoreSeq.get_ensemble_defect,
-        utils/energy_scores.py:362-374).  Returns float64[R]; with want_bpp also the (R, L+1, L+1) base-pair
-        probability matrices (1-based, upper triangle)."""
-        R, L = _equal_length(seqs)
-        ed = np.zeros(R, dtype=np.float64)
-        bpp = np.zeros((R, L + 1, L + 1), dtype=np.float64) if want_bpp else None
-        self._check(self._L.drna_ensemble_defect_batch(self._h, R, L, "".join(seqs).encode("ascii"), ed.ctypes.data,
-                                                       bpp.ctypes.data if want_bpp else None))
-        return (ed, bpp) if want_bpp else ed
+        """String form of :meth:`ensemble_defect_arrays` (seqs: list of equal-length strings)."""
+        return self.ensemble_defect_arrays(_as_u8(seqs), want_bpp)
 
     def cofold_ensemble_defect(self, seqs, want_bpp=False):
         """Two strands: ensemble defect of each 'AAAA&BBBB' pair against targets[0] ('&' removed) in the ensemble of
@@ -391,14 +382,17 @@ class Engine:
                                                               bpp.ctypes.data if want_bpp else None))
         return (ed, bpp) if want_bpp else ed
 
-    def ensemble_defect_arrays(self, seqs_u8):
-        """Array form of :meth:`ensemble_defect`: (R, L) uint8 ASCII letters -> float64[R]."""
+    def ensemble_defect_arrays(self, seqs_u8, want_bpp=False):
+        """Ensemble defect of each sequence ((R, L) uint8 ASCII letters) against targets[0] (reference
+        ScoreSeq.get_ensemble_defect, utils/energy_scores.py:362-374).  Returns float64[R]; with want_bpp also the
+        (R, L+1, L+1) base-pair probability matrices (1-based, upper triangle)."""
         seqs_u8 = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
         R, L = seqs_u8.shape
         ed = np.zeros(R, dtype=np.float64)
-        self._check(self._L.drna_ensemble_defect_batch(self._h, R, L, seqs_u8.ctypes.data_as(C.c_char_p),
-                                                       ed.ctypes.data, None))
-        return ed
+        bpp = np.zeros((R, L + 1, L + 1), dtype=np.float64) if want_bpp else None
+        self._check(self._L.drna_ensemble_defect_batch(self._h, R, L, seqs_u8.ctypes.data_as(C.c_char_p), ed.ctypes.data,
+                                                       bpp.ctypes.data if want_bpp else None))
+        return (ed, bpp) if want_bpp else ed
 
     def last_edef_timing(self):
         out = (C.c_float * 2)()
@@ -433,7 +427,7 @@ class HostKernels:
     @staticmethod
     def _pack(prob):
         """arrays of a design.DesignProblem in the layout of drna_propose_batch_alt / drna_mc_run (cached on the problem)"""
-        am = np.array([sum(1 << "ACGU".index(c) for c in a) for a in prob.allowed], dtype=np.uint8)
+        am = co_allowed_mask(prob)
         partner = np.ascontiguousarray(prob.partner, dtype=np.int32)
         snake_of = np.ascontiguousarray(prob.snake_of, dtype=np.int32)
         off, nodes, nst, chars = [0], [], [], b""
@@ -476,66 +470,47 @@ class HostKernels:
             raise EngineError(rc, "drna_simscore_batch")
         return mcc, rec, prec
 
-    def propose(self, target, allowed_mask, seqs_u8, ss_u8, shelf_index, n_shelves, tm_max, tm_min, targeted, rng_state):
+    def _propose(self, name, struct, problem, seqs_u8, ss_u8, shelf_index, n_shelves, tm_max, tm_min, targeted, rng_state):
+        """drna_propose_batch[_alt|_co] (`name`): `problem` are the arguments between the structure and the sequences"""
         s = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
         R, L = s.shape
         out = np.empty_like(s)
         ss = np.ascontiguousarray(ss_u8, dtype=np.uint8)
-        am = np.ascontiguousarray(allowed_mask, dtype=np.uint8)
         sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
-        assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
-        rc = self._L.drna_propose_batch(R, L, target.encode("ascii"), am.ctypes.data, s.ctypes.data, ss.ctypes.data,
-                                        sh.ctypes.data, int(n_shelves), float(tm_max), float(tm_min), int(bool(targeted)),
-                                        rng_state.ctypes.data, out.ctypes.data)
+        _check_rng(rng_state, R)
+        rc = getattr(self._L, name)(R, L, struct.encode("ascii"), *problem, s.ctypes.data, ss.ctypes.data, sh.ctypes.data,
+                                    int(n_shelves), float(tm_max), float(tm_min), int(bool(targeted)), rng_state.ctypes.data,
+                                    out.ctypes.data)
         if rc != 0:
-            raise EngineError(rc, "drna_propose_batch")
+            raise EngineError(rc, name)
         return out
+
+    def propose(self, target, allowed_mask, seqs_u8, ss_u8, shelf_index, n_shelves, tm_max, tm_min, targeted, rng_state):
+        am = np.ascontiguousarray(allowed_mask, dtype=np.uint8)
+        return self._propose("drna_propose_batch", target, [am.ctypes.data], seqs_u8, ss_u8, shelf_index, n_shelves, tm_max, tm_min,
+                             targeted, rng_state)
 
     def propose_alt(self, prob, seqs_u8, ss_u8, shelf_index, n_shelves, tm_max, tm_min, targeted, rng_state):
         """Proposals for a ``design.DesignProblem`` that may hold alternative-structure snakes."""
-        s = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
-        R, L = s.shape
-        out = np.empty_like(s)
-        ss = np.ascontiguousarray(ss_u8, dtype=np.uint8)
-        pk = getattr(prob, "_native_pack", None)
-        if pk is None:
-            HostKernels._pack(prob)
-            pk = prob._native_pack
-        am, partner, snake_of, off, nodes, nst, chars = pk
-        sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
-        assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
-        rc = self._L.drna_propose_batch_alt(R, L, prob.sec_struct.encode("ascii"), partner.ctypes.data, am.ctypes.data,
-                                            snake_of.ctypes.data, len(prob.snakes), off.ctypes.data, nodes.ctypes.data,
-                                            nst.ctypes.data, chars.ctypes.data, s.ctypes.data, ss.ctypes.data, sh.ctypes.data,
-                                            int(n_shelves), float(tm_max), float(tm_min), int(bool(targeted)),
-                                            rng_state.ctypes.data, out.ctypes.data)
-        if rc != 0:
-            raise EngineError(rc, "drna_propose_batch_alt")
-        return out
+        am, partner, snake_of, off, nodes, nst, chars = _packed(prob)
+        problem = [partner.ctypes.data, am.ctypes.data, snake_of.ctypes.data, len(prob.snakes), off.ctypes.data, nodes.ctypes.data,
+                   nst.ctypes.data, chars.ctypes.data]
+        return self._propose("drna_propose_batch_alt", prob.sec_struct, problem, seqs_u8, ss_u8, shelf_index, n_shelves, tm_max,
+                             tm_min, targeted, rng_state)
 
     def propose_co(self, prob, oligo_state, seqs_u8, ss_u8, shelf_index, n_shelves, tm_max, tm_min, targeted, rng_state):
         """Proposals for a two-strand ``design.DesignProblem`` (drna_propose_batch_co): the strings keep the '&';
         oligo_state "heterodimer" or "homodimer" (the reference's strand-copy rules follow every move)."""
-        s = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
-        R, L = s.shape
-        out = np.empty_like(s)
-        ss = np.ascontiguousarray(ss_u8, dtype=np.uint8)
         am = co_allowed_mask(prob)
-        sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
-        assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
-        rc = self._L.drna_propose_batch_co(R, L, prob.sec_struct.encode("ascii"), am.ctypes.data, OLIGO_STATES[oligo_state],
-                                           s.ctypes.data, ss.ctypes.data, sh.ctypes.data, int(n_shelves), float(tm_max),
-                                           float(tm_min), int(bool(targeted)), rng_state.ctypes.data, out.ctypes.data)
-        if rc != 0:
-            raise EngineError(rc, "drna_propose_batch_co")
-        return out
+        return self._propose("drna_propose_batch_co", prob.sec_struct, [am.ctypes.data, OLIGO_STATES[oligo_state]], seqs_u8, ss_u8,
+                             shelf_index, n_shelves, tm_max, tm_min, targeted, rng_state)
 
     def metropolis(self, score_o, score_m, temps, rng_state, L_const=504.12):
         so = np.ascontiguousarray(score_o, dtype=np.float64)
         sm = np.ascontiguousarray(score_m, dtype=np.float64)
         tt = np.ascontiguousarray(temps, dtype=np.float64)
         R = so.shape[0]
-        assert rng_state.dtype == np.uint32 and rng_state.shape == (R, RNG_WORDS) and rng_state.flags.c_contiguous
+        _check_rng(rng_state, R)
         acc = np.zeros(R, dtype=np.uint8)
         bet = np.zeros(R, dtype=np.uint8)
         rc = self._L.drna_metropolis_batch(R, so.ctypes.data, sm.ctypes.data, tt.ctypes.data, float(L_const),

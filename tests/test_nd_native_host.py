@@ -20,15 +20,11 @@ HAIRPIN14 = "((((......))))"
 
 
 class NdEngine(OracleEngine):
-    """one strand: + the dict form of score_batch ReplicaScorer takes, and subopt_energy"""
+    """one strand: + subopt_energy"""
 
     def __init__(self, oracle):
         super().__init__(oracle)
         self.calls = self.folded = 0
-
-    def score_batch(self, seqs, flags=0):
-        Epf, Emfe, ss, Ed = self.o.score_batch(list(seqs), self.targets, threads=4)
-        return {"Epf": Epf, "Emfe": Emfe, "mfe_ss": ss, "Ed": Ed}
 
     def subopt_energy(self, seqs):
         self.calls += 1
