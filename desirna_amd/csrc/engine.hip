@@ -20,6 +20,7 @@
 #include "fold_mfe.hpp"
 #include "fold_cofold.hpp"
 #include "fold_cofold_lds.hpp"
+#include "fold_self_dimer.hpp"
 #include "fold_mfe_lds.hpp"
 #include "fold_mfe_dual.hpp"
 #include "fold_fused.hpp"
@@ -88,6 +89,7 @@ struct drna_engine {
   double* d_F4 = nullptr;   // co-fold free energies (FA, FB, FcAB, FAB per pair)
   double *hm_F4 = nullptr, *dm_F4 = nullptr;   // ... of drna_cofold_batch and drna_mc_run_cofold: host-mapped like hm_Epf, allocated on first use
   bool cofold_lds = true;   // option "cofold_lds": pairs of at most CO_LDS_MAX nt fold with their tables in LDS (fold_cofold_lds.hpp)
+  bool self_dimer_lds = true;   // option "self_dimer_lds": self-dimers of at most SD_LDS_MAX nt keep their tables in LDS (fold_self_dimer.hpp)
   bool subopt_lds = true;   // option "subopt_lds": second-best folds of at most SUB_LDS_MAX nt keep their tables in LDS (fold_subopt_lds.hpp)
   // K-best structures: workspace for kb_chunk sequences, allocated on first use
   int32_t* d_ws_kb = nullptr;
@@ -414,6 +416,7 @@ extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!strcmp(name, "pf_helper")) { e->pf_helper = value != 0; return DRNA_OK; }
   if (!strcmp(name, "cofold_lds")) { e->cofold_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds")) { e->subopt_lds = value != 0; return DRNA_OK; }
+  if (!strcmp(name, "self_dimer_lds")) { e->self_dimer_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "helper_fault")) { e->helper_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "strip_fault")) { e->strip_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "mfe_fark_min_strips")) { e->mfe_fark_min_strips = value < 1 ? 1 : value; return DRNA_OK; }
@@ -442,6 +445,8 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "cofold_lds_max")) { *value = CO_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds")) { *value = e->subopt_lds ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds_max")) { *value = SUB_LDS_MAX; return DRNA_OK; }
+  if (!strcmp(name, "self_dimer_lds")) { *value = e->self_dimer_lds ? 1 : 0; return DRNA_OK; }
+  if (!strcmp(name, "self_dimer_lds_max")) { *value = SD_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "last_fused")) { *value = e->last_fused ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "fused_blocks_per_cu")) { *value = e->fused_blocks_per_cu; return DRNA_OK; }
   if (!strcmp(name, "pair_blocks_per_cu")) { *value = e->pair_blocks_per_cu; return DRNA_OK; }
@@ -1394,12 +1399,15 @@ extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const cha
 // R pairs whose letters the caller has put into hm_seqs (L each, no '&'): both folds side by side on their streams and the
 // two-strand evaluation, every result written by the kernels into the host-mapped buffers (hm_F4, hm_Emfe, hm_ss, hm_Ed), so a
 // batch costs no hipMemcpy.  Pairs of at most CO_LDS_MAX nucleotides take the LDS-resident kernels (option "cofold_lds")
+static int mapped_F4(drna_engine* e) {
+  if (e->hm_F4) return DRNA_OK;
+  HIP_TRY(hipHostMalloc((void**)&e->hm_F4, (size_t)4 * e->max_R * sizeof(double), hipHostMallocMapped));
+  HIP_TRY(hipHostGetDevicePointer((void**)&e->dm_F4, e->hm_F4, 0));
+  return DRNA_OK;
+}
 static int cofold_batch_mapped(drna_engine* e, int R, int L, int cut, bool want_pf, bool want_mfe, bool want_ev) {
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->hm_F4) {
-    HIP_TRY(hipHostMalloc((void**)&e->hm_F4, (size_t)4 * e->max_R * sizeof(double), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&e->dm_F4, e->hm_F4, 0));
-  }
+  { const int rc = mapped_F4(e); if (rc != DRNA_OK) return rc; }
   if (want_ev) { const int rc = mapped_Ed(e); if (rc != DRNA_OK) return rc; }
   reset_status(e);
   CoArgs a = co_args(e, e->dm_seqs, L, cut, L + 2);
@@ -1452,6 +1460,60 @@ extern "C" int drna_cofold_batch(drna_engine* e, int R, int L, int cut, const ch
     std::memcpy(mfe_ss, e->hm_ss, (size_t)R * L);
   }
   if (want_ev) std::memcpy(Ed, e->hm_Ed, (size_t)R * e->n_targets * sizeof(int32_t));
+  return DRNA_OK;
+}
+
+// ---------------------------------------------------------------- a sequence against a copy of itself (-oa on)
+
+// reference utils/dimer_multichain_energy.py:24-45: fraction of strands bound in the dimer at 1 mM, and -kT ln of a fraction
+static double oligo_fraction(double FA, double FB, double FcAB) {
+  const double KB = 0.001987204259, RHO = 55.14, TEMP = 273.15 + 37, CONC = 1e-3;
+  const double dF = FcAB - FA - FB;
+  const double rhs = CONC / RHO * std::exp(-dF / (KB * TEMP));
+  return 1 - (std::sqrt(1 + 4 * rhs) - 1) / (2 * rhs);
+}
+static double kT_log(double x) { return -0.001987204259 * (273.15 + 37) * std::log(x); }
+
+// H sequences (L letters each) the caller has put into hm_seqs: the partition function of each against a copy of itself in ONE
+// launch on the partition function's stream, F4 into hm_F4 (no hipMemcpy).  The caller's other launches have drained: the kernel
+// is never resident beside the fused / two-workgroup folds, which size their grids against the whole chip.  Sequences of at most
+// SD_LDS_MAX nucleotides keep their tables in LDS (option "self_dimer_lds"); longer ones use the partition function's workspace
+// slots, which hold more than the ~1.5 L^2 cells of the three tables (4.7 L^2 against 7.1 (L + 2)^2 doubles)
+static int self_dimer_mapped(drna_engine* e, int H, int L) {
+  HIP_TRY(hipSetDevice(e->device));
+  { const int rc = mapped_F4(e); if (rc != DRNA_OK) return rc; }
+  if (sd_ws_stride(L) > (long long)pf_ws_stride(e->max_L + 2)) { e->err = "self-dimer: workspace slot too small"; return DRNA_ERR_INTERNAL; }
+  reset_status(e);
+  CoArgs a = co_args(e, e->dm_seqs, L, L, L + 2);
+  a.wsp_stride = (long long)pf_ws_stride(e->max_L + 2);
+  a.F4 = e->dm_F4;
+  HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
+  if (e->self_dimer_lds && L <= SD_LDS_MAX) hipLaunchKernelGGL(self_dimer_pf_lds_kernel<1024>, dim3(H), dim3(1024), 0, e->s_pf, a);
+  else hipLaunchKernelGGL(self_dimer_pf_kernel<1024>, dim3(H), dim3(1024), 0, e->s_pf, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_p1, e->s_pf));
+  HIP_TRY(hipStreamSynchronize(e->s_pf));
+  HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
+  e->timing[0] = e->timing[2] = 0.f; e->timing[3] = e->timing[1];
+  return fold_status(e, H, false, true, nullptr, 0, "unexpected status of the self-dimer partition function");
+}
+
+extern "C" int drna_self_dimer_batch(drna_engine* e, int R, int L, const char* seqs, double* F4, double* oligo_frac) {
+  if (!e) return DRNA_ERR_ARG;
+  // (no upper limit on R: the batch goes through the workspace slots in chunks)
+  { const int rc = aux_check(e, "drna_self_dimer_batch", std::min(R, e->max_R), L, nullptr, seqs && F4, "seqs and F4 required"); if (rc != DRNA_OK) return rc; }
+  float ms = 0.f;
+  for (int r0 = 0; r0 < R; r0 += e->ws_slots) {
+    const int m = std::min(R - r0, e->ws_slots);
+    std::memcpy(e->hm_seqs, seqs + (size_t)r0 * L, (size_t)m * L);
+    const int rc = self_dimer_mapped(e, m, L);
+    if (rc != DRNA_OK) return rc;
+    std::memcpy(F4 + (size_t)4 * r0, e->hm_F4, (size_t)4 * m * sizeof(double));
+    ms += e->timing[1];
+  }
+  e->timing[1] = e->timing[3] = ms;
+  if (oligo_frac)
+    for (int r = 0; r < R; r++) oligo_frac[r] = oligo_fraction(F4[4 * (size_t)r], F4[4 * (size_t)r + 1], F4[4 * (size_t)r + 2]);
   return DRNA_OK;
 }
 
@@ -1882,14 +1944,15 @@ static int mc_terms(drna_engine* e, const char* who, int n_terms, const int32_t*
   return DRNA_OK;
 }
 
-// drna_mc_run (subopt_e null) and drna_mc_run_nd
+// drna_mc_run (subopt_e null), drna_mc_run_nd and, with oligo_frac / bonus, drna_mc_run_oa
 static int mc_run_impl(drna_engine* e, const char* who, int R, int L, int n_iter, const char* target, const int32_t* partner,
                        const unsigned char* allowed_mask, const int32_t* snake_of, int n_snakes, const int32_t* snake_off,
                        const int32_t* snake_nodes, const int32_t* snake_nstates, const char* snake_states,
                        const int32_t* shelf_index, int n_shelves, double tm_max, double tm_min, int targeted,
                        const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w,
                        uint32_t flags, uint32_t* rng_state, char* seqs, char* mfe_ss, double* score, double* mcc1,
-                       double* Epf, double* Ed, int64_t* counters, char* best_seq, char* best_ss, double* best, double* subopt_e) {
+                       double* Epf, double* Ed, int64_t* counters, char* best_seq, char* best_ss, double* best, double* subopt_e,
+                       double* oligo_frac = nullptr, double* bonus = nullptr) {
   using namespace drna_host;
   if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || n_iter < 0 || !target || !allowed_mask || !shelf_index || !temps ||
       n_terms < 1 || !term_id || !term_w || !rng_state || !seqs || !mfe_ss || !score || !mcc1 || !Epf || !Ed || !counters ||
@@ -1900,9 +1963,10 @@ static int mc_run_impl(drna_engine* e, const char* who, int R, int L, int n_iter
   const int nt = e->n_targets;
   bool want_edef = false;
   { const int rc = mc_terms(e, who, n_terms, term_id, &want_edef); if (rc != DRNA_OK) return rc; }
-  if (subopt_e) { const int rc = fits_workspace(e, who, R); if (rc != DRNA_OK) return rc; }
+  if (subopt_e || oligo_frac) { const int rc = fits_workspace(e, who, R); if (rc != DRNA_OK) return rc; }
   McScored S;
   S.ss.resize((size_t)R * L); S.Epf.resize(R); S.ed.resize(R); S.Emfe.resize(R);
+  if (oligo_frac) { S.x0.resize(R); S.x1.resize(R); }
   if (want_edef) S.edef.resize(R);
   S.has_add = nt > 1;
   if (S.has_add) S.add.resize(R);
@@ -1931,6 +1995,18 @@ static int mc_run_impl(drna_engine* e, const char* who, int R, int L, int n_iter
         S.add[r] = sum / (nt - 1) - S.Epf[r];
       }
     }
+    if (oligo_frac) {
+      // -oa on (utils/energy_scores.py:118-119, :412-419): every proposal against a copy of itself, one launch now that the
+      // score batch has drained; the monomer-fraction term is added by the loop, after the negative-design term
+      std::memcpy(e->hm_seqs, prop, (size_t)R * L);
+      rc = self_dimer_mapped(e, R, L);
+      if (rc != DRNA_OK) return rc;
+      for (int r = 0; r < R; r++) {
+        const double* F = e->hm_F4 + (size_t)4 * r;
+        S.x0[r] = oligo_fraction(F[0], F[1], F[2]);
+        S.x1[r] = kT_log(1 - S.x0[r]);
+      }
+    }
     return DRNA_OK;
   };
   auto metrics = [&](const char* ss, int* pq, SimMetrics& m) {
@@ -1943,7 +2019,7 @@ static int mc_run_impl(drna_engine* e, const char* who, int R, int L, int n_iter
     return second_best_mapped(e, H, L, 0);
   };
   return mc_loop(e, who, R, L, n_iter, ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs,
-                 mfe_ss, score, mcc1, Epf, Ed, nullptr, nullptr, subopt_e, counters, best_seq, best_ss, best, S, score_all, metrics,
+                 mfe_ss, score, mcc1, Epf, Ed, oligo_frac, bonus, subopt_e, counters, best_seq, best_ss, best, S, score_all, metrics,
                  second_best);
 }
 
@@ -1970,14 +2046,11 @@ extern "C" int drna_mc_run_nd(MC_RUN_PARAMS, double* subopt_e) {
   return mc_run_impl(e, "drna_mc_run_nd", MC_RUN_ARGS, subopt_e);
 }
 
-// reference utils/dimer_multichain_energy.py:24-45: fraction of strands bound in the dimer at 1 mM, and -kT ln of a fraction
-static double oligo_fraction(double FA, double FB, double FcAB) {
-  const double KB = 0.001987204259, RHO = 55.14, TEMP = 273.15 + 37, CONC = 1e-3;
-  const double dF = FcAB - FA - FB;
-  const double rhs = CONC / RHO * std::exp(-dF / (KB * TEMP));
-  return 1 - (std::sqrt(1 + 4 * rhs) - 1) / (2 * rhs);
+extern "C" int drna_mc_run_oa(MC_RUN_PARAMS, double* subopt_e, double* oligo_frac, double* bonus) {
+  if (!e) return DRNA_ERR_ARG;
+  if (!oligo_frac || !bonus) { e->err = "drna_mc_run_oa: bad argument (oligo_frac and bonus required)"; return DRNA_ERR_ARG; }
+  return mc_run_impl(e, "drna_mc_run_oa", MC_RUN_ARGS, subopt_e, oligo_frac, bonus);
 }
-static double kT_log(double x) { return -0.001987204259 * (273.15 + 37) * std::log(x); }
 
 #define MC_RUN_CO_PARAMS                                                                                                              \
   drna_engine *e, int R, int L, int cut, int n_iter, const char *target, const unsigned char *allowed_mask, int oligo_state,          \

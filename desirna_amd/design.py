@@ -27,8 +27,9 @@ Alternative structures: "snake" moves (connected components of the pair graph of
 switch between their Watson-Crick colourings) as in the reference (:143-388, :1081-1095).
 
 ``-nd on`` (negative design) runs through both drivers (``run_design_fast(negative_design="on")``: the second-best fold of the
-solved candidates per iteration, or inside the native loop); ``-acgu on`` (weighted letter choices), ``-oa on`` and motifs are
-available in the Python driver (``run_design``) only.
+solved candidates per iteration, or inside the native loop), and so does ``-oa on`` (``run_design_fast(oligo="on")``: every
+candidate folded against a copy of itself, ``Engine.self_dimer`` per iteration or inside the native loop); ``-acgu on``
+(weighted letter choices) and motifs are available in the Python driver (``run_design``) only.
 
 Two strands (hetero-dimer, ``-d on`` homodimer) run through both drivers; together with alternative structures through
 ``run_design`` only.
@@ -435,7 +436,7 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
 def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                     scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
                     device=0, engine=None, keep_records=True, native_loop=None, shards=None, num_results=None, dimer="off",
-                    negative_design="off"):
+                    negative_design="off", oligo="off"):
     """Same loop as :func:`run_design` with the per-replica host work in native code and no per-step Python objects:
     proposals, SimScore and Metropolis run batched in the C library, the replica state lives in numpy arrays (the batch of
     ``energy_scores.score_arrays``, of which it keeps what ``Engine.mc_run`` holds).  The
@@ -454,7 +455,13 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
     ``negative_design="on"`` (``-nd on``, reference ``utils/energy_scores.py:104-108``): every solved candidate (1 - MCC == 0)
     loses ``subopt_e - Epf``, the second-best structure's energy from ``Engine.subopt_energy`` / ``Engine.cofold_subopt_energy``
     on the solved subset, or from the negative-design step of ``Engine.mc_run[_cofold]``; for two strands before the bonus.
-    Records and ``best`` carry ``subopt_e`` and ``esubopt_minus_Epf`` as :func:`run_design`'s do."""
+    Records and ``best`` carry ``subopt_e`` and ``esubopt_minus_Epf`` as :func:`run_design`'s do.
+
+    ``oligo="on"`` (``-oa on``, the reference's ``oligo_state == "avoid"``, ``utils/energy_scores.py:118-119``, ``:412-419``):
+    every candidate is folded against a copy of itself (``Engine.self_dimer`` per iteration, or the self-dimer step of
+    ``Engine.mc_run(self_dimer=True)``) and ``-kT ln(1 - oligo_fraction)`` is the last addition to its score, after the
+    negative-design term.  Records and ``best`` carry ``oligo_fraction`` and ``monomer_bonus`` as :func:`run_design`'s do.  With a
+    two-strand target the ``&`` decides, as in ``oligo_state_and_pks``: the switch is then without effect."""
     from . import engine as _engine
     if stop_when_solved and num_results is not None and not keep_records:
         raise ValueError("the -sws rule with num_results ranks the recorded sequences: it needs keep_records=True "
@@ -465,20 +472,24 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                                   "proposer has no snake moves)")
     es.check_scoring_functions(es.parse_scoring_functions(scoring_f))
     run = _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results,
-                 shards, dimer, keep_records=keep_records)
+                 shards, dimer, oligo, keep_records=keep_records)
     prob, sf, oligo_state, nd = run.prob, run.opts.scoring_f, run.opts.oligo_state, negative_design == "on"
+    oa = oligo_state == "avoid"
     local = np.array(run.local, dtype=np.int64)
     R, L, Rl = replicas, prob.n, len(run.local)
     eng = engine or _engine.Engine(max_R=max(1, Rl), max_L=L - 1 if two else L, device=device)      # L counts the '&'
     hk = _engine.HostKernels()
     eng.set_targets([input_file.sec_struct.replace("&", "")] + list(input_file.alt_sec_structs or []))
-    score = lambda seqs_u8: es.score_arrays(eng, hk, input_file.sec_struct, sf, seqs_u8, oligo_state, run.opts.pks, nd)
+    score = lambda seqs_u8: es.score_arrays(eng, hk, input_file.sec_struct, sf, seqs_u8, oligo_state, run.opts.pks, nd, self_dimer=oa)
     # the replica state: the arrays of the scored batch that Engine.mc_run[_cofold] holds, under its names
     b = score(np.tile(np.frombuffer(run.init.encode(), dtype=np.uint8), (max(1, Rl), 1)))
-    keys = ["seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"] + ["oligo_fraction", "bonus"] * two + ["subopt_e"] * nd
+    keys = ["seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"] + ["oligo_fraction", "bonus"] * (two or oa) + ["subopt_e"] * nd
     cur = SimpleNamespace(**{k: np.array(getattr(b, k), dtype=np.uint8 if k in keys[:2] else np.float64) for k in keys})
+    bonus_name = "monomer_bonus" if oa else "oligomer_bonus"
+    if oa:
+        cur.bonus_field = bonus_name                      # (energy_scores.record names the bonus of its records by it)
     # fields of `best`; after the strings, in the order of mc_run's best["vals"] (esubopt_minus_Epf follows from them)
-    fields = (["sequence", "mfe_ss", "mcc", "scoring_function", "Epf", "edesired"] + ["oligo_fraction", "oligomer_bonus"] * two
+    fields = (["sequence", "mfe_ss", "mcc", "scoring_function", "Epf", "edesired"] + ["oligo_fraction", bonus_name] * (two or oa)
               + ["subopt_e", "esubopt_minus_Epf"] * nd)
     vals = [f for f in fields[2:] if f != "esubopt_minus_Epf"]
 
@@ -522,7 +533,7 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                                   counters, bst, **nd_kw)
             else:
                 eng.mc_run(prob, exchange, shelf_idx, R, tm_max, tm_min, targeted, tl, sf, flags, rng_state, vars(cur), counters, bst,
-                           **nd_kw)
+                           **nd_kw, **(dict(self_dimer=True) if oa else {}))
             best = SimpleNamespace(sequence=bst["seq"].tobytes().decode(), mfe_ss=bst["ss"].tobytes().decode(),
                                    **{f: float(v) for f, v in zip(vals, bst["vals"])})
             if nd:
@@ -598,15 +609,17 @@ def main(argv=None):
     a = ap.parse_args(argv)
     inp = read_input(a.name)
     strands2 = "&" in inp.sec_struct
-    # the Python driver's own features: -oa, -acgu, and two strands together with alternative structures
-    two = a.oligo == "on" or a.percs == "on" or (strands2 and bool(inp.alt_sec_structs))
+    # the Python driver's own features: -acgu, and two strands together with alternative structures
+    two = a.percs == "on" or (strands2 and bool(inp.alt_sec_structs))
     python_host = a.python_host or two
     if python_host:
-        extra = dict(dimer=a.dimer, oligo=a.oligo, subopt=a.subopt) if (two or strands2 or a.subopt == "on") else {}
+        extra = dict(dimer=a.dimer, oligo=a.oligo, subopt=a.subopt) if (two or strands2 or a.subopt == "on" or a.oligo == "on") else {}
     else:
         extra = dict(dimer=a.dimer) if strands2 else {}
         if a.subopt == "on":
             extra["negative_design"] = "on"
+        if a.oligo == "on":
+            extra["oligo"] = "on"
     if a.percs == "on":
         vals = [int(x) for x in a.acgu_content.split(",")] if a.acgu_content else [15, 30, 30, 15]
         if sum(vals) != 100:

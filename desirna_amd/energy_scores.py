@@ -11,7 +11,8 @@ of the batch, instead of 3-8 ViennaRNA calls per sequence inside a forked worker
 There is ONE scorer and it works on arrays: ``SF_TERMS`` is the ``-sf`` table (name, native id, formula),
 :func:`score_arrays` scores an (R, L) uint8 batch of candidates -- one strand, two strands, alternative structures,
 ``-nd on`` -- in the reference's order of additions, and :func:`record` turns one row of its result into a ``ScoreSeq``.
-``ReplicaScorer.score`` (``design.run_design``) is ``record`` over every row, plus ``-oa`` and the motifs;
+``ReplicaScorer.score`` (``design.run_design``) is ``record`` over every row, plus ``-oa`` (through its own 2 L engine;
+``score_arrays(self_dimer=True)`` is the fast driver's form, ``Engine.self_dimer``) and the motifs;
 ``design.run_design_fast`` keeps the arrays as its replica state and calls ``record`` for its records only.  The native
 loop (``mc_loop`` in ``csrc/engine.hip``) is the same sum in C, on the same term ids.
 
@@ -175,13 +176,17 @@ def score_motifs(seq, sim_options):
     return motif_score
 
 
-def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pks="off", nd=False):
+def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pks="off", nd=False, self_dimer=False):
     """THE scorer (reference score_sequence(), :70-118, for a whole batch): `eng` an ``engine.Engine`` whose targets are
     sec_struct (+ the alternative structures) without the '&', `hk` an ``engine.HostKernels``, seqs_u8 the (R, L) uint8 candidates
     (two strands -- oligo_state heterodimer / homodimer --: with the '&' column).  Returns the batch as arrays, named like the
     state of ``Engine.mc_run``: seqs, mfe_ss (uint8 R x L), score, mcc1, recall1, precision1, Epf (two strands: FAB), Ed, and where
     they apply (else None) sln_Epf, Emfe (``-sf Ed-MFE``; kcal/mol), Edef, Ed2 (mean E(alternative structures)), subopt_e (`nd`;
-    0 where 1 - MCC != 0), oligo_fraction, bonus (two strands).
+    0 where 1 - MCC != 0), oligo_fraction, bonus (two strands; one strand with `self_dimer`).
+
+    `self_dimer` (opt-in, with oligo_state "avoid" = -oa on only): oligo_fraction of every candidate folded against a copy of
+    itself from ``eng.self_dimer`` and bonus = -kT ln(1 - oligo_fraction), added last (reference :118-119, :412-419).  Off by
+    default: ``ReplicaScorer.score`` adds that term itself.
 
     The reference's order of additions: the -sf sum; + (Ed2 - Epf) with alternative structures, every energy / 100 first, then
     the sum, then / count (one strand only, as the two-strand scorer always had it); - (subopt_e - Epf) on the candidates with
@@ -233,6 +238,11 @@ def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pk
         b.oligo_fraction = np.array([float(oligo_fraction(out["FA"][k], out["FB"][k], out["FcAB"][k])) for k in range(R)])
         b.bonus = np.array([float(kTlog(f)) for f in b.oligo_fraction])
         b.score = b.score + b.bonus
+    elif self_dimer and oligo_state == "avoid":           # reference :118-119, get_scoring_function_monomer (:412-419)
+        b.oligo_fraction = np.array(eng.self_dimer(strings(range(R)))["oligo_fraction"], dtype=np.float64)
+        b.bonus = np.array([float(kTlog_monomer_fraction(f)) for f in b.oligo_fraction])
+        b.bonus_field = "monomer_bonus"
+        b.score = b.score + b.bonus
     return b
 
 
@@ -263,7 +273,8 @@ def record(b, k):
         sc.get_subopt_e(col("subopt_e"))
         sc.get_esubopt_minus_Epf(sc.Epf, sc.subopt_e)
     if col("oligo_fraction") is not None:
-        sc.oligo_fraction, sc.oligomer_bonus = col("oligo_fraction"), col("bonus")
+        sc.oligo_fraction = col("oligo_fraction")
+        setattr(sc, getattr(b, "bonus_field", "oligomer_bonus"), col("bonus"))     # (-oa on: monomer_bonus, as ReplicaScorer.score names it)
     return sc
 
 

@@ -61,6 +61,9 @@ _SIGNATURES = {
                              _dbl, _ci, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "drna_mc_run_cofold_nd": (_ci, [_vp, _ci, _ci, _ci, _ci, _str, _vp, _ci, _vp, _ci, _dbl, _dbl, _ci, _vp, _dbl, _ci, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drna_self_dimer_batch": (_ci, [_vp, _ci, _ci, _str, _vp, _vp]),
+    "drna_mc_run_oa": (_ci, [_vp, _ci, _ci, _ci, _str, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci, _vp,
+                             _dbl, _ci, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "drna_rng_seed": (_ci, [_ci, _vp, _vp]),
     "drna_rng_random": (_ci, [_ci, _vp, _vp]),
 }
@@ -285,9 +288,10 @@ class Engine:
     TERM_IDS = {"Ed-Epf": 0, "1-MCC": 1, "sln_Epf": 2, "Ed-MFE": 3, "1-precision": 4, "1-recall": 5, "Edef": 6}
 
     def _mc_run(self, name, head, mid, keys, n_vals, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state,
-                state, counters, best, L_const, subopt_e):
+                state, counters, best, L_const, subopt_e, oa=False):
         """drna_mc_run / drna_mc_run_cofold (`name`; with `subopt_e` their _nd forms): `head` are the arguments between R and the
-        shelf indices, `mid` those between the term weights and the random streams, `keys` the arrays of `state` in call order"""
+        shelf indices, `mid` those between the term weights and the random streams, `keys` the arrays of `state` in call order.
+        `oa`: drna_mc_run_oa, which takes subopt_e (or NULL), then the state's oligo_fraction and bonus, after `best`"""
         R = state["seqs"].shape[0]
         nd = subopt_e is not None
         _check_rng(rng_state, R)
@@ -303,20 +307,28 @@ class Engine:
         if nd:
             assert subopt_e.dtype == np.float64 and subopt_e.shape == (R,) and subopt_e.flags.c_contiguous
             args.append(p(subopt_e))
-        self._check(getattr(self._L, name + "_nd" if nd else name)(*args))
+        if oa:
+            for k in ("oligo_fraction", "bonus"):
+                assert state[k].dtype == np.float64 and state[k].shape == (R,) and state[k].flags.c_contiguous
+            args += [None] * (not nd) + [p(state["oligo_fraction"]), p(state["bonus"])]
+        self._check(getattr(self._L, name + "_oa" if oa else name + "_nd" if nd else name)(*args))
 
     def mc_run(self, prob, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, flags, rng_state, state,
-               counters, best, L_const=504.12, subopt_e=None):
+               counters, best, L_const=504.12, subopt_e=None, self_dimer=False):
         """n_iter Monte-Carlo iterations of all replicas in native code (drna_mc_run).  `state` holds the arrays seqs, mfe_ss
         (uint8 R x L), score, mcc1, Epf, Ed (float64 R); `best` holds seq, ss (uint8 L) and vals (float64 4); all updated in place.
         With `subopt_e` (float64 R, in/out: the second-best energy of every replica's state, kcal/mol) the loop runs the
-        negative-design step (drna_mc_run_nd) and `best["vals"]` holds a fifth value, the best state's subopt_e."""
+        negative-design step (drna_mc_run_nd) and `best["vals"]` holds a fifth value, the best state's subopt_e.
+        With `self_dimer` (-oa on: drna_mc_run_oa) every proposal is also folded against a copy of itself and
+        -kT ln(1 - oligo_fraction) is the last addition to its score; `state` then holds oligo_fraction and bonus (float64 R,
+        in/out) and `best["vals"]` has the two-strand layout: 1-MCC, score, Epf, Ed, oligo_fraction, bonus[, subopt_e]."""
         am, partner, snake_of, off, nodes, nst, chars = _packed(prob)
         p = lambda a: a.ctypes.data
         head = [state["seqs"].shape[1], int(n_iter), prob.sec_struct.encode("ascii"), p(partner), p(am), p(snake_of),
                 len(prob.snakes), p(off), p(nodes), p(nst), p(chars)]
-        self._mc_run("drna_mc_run", head, [int(flags)], ("seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"), 4, shelf_index, n_shelves,
-                     tm_max, tm_min, targeted, temps, scoring_f, rng_state, state, counters, best, L_const, subopt_e)
+        self._mc_run("drna_mc_run", head, [int(flags)], ("seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"), 6 if self_dimer else 4,
+                     shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state, state, counters, best, L_const,
+                     subopt_e, oa=bool(self_dimer))
 
     def mc_run_cofold(self, prob, oligo_state, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state,
                       state, counters, best, L_const=504.12, subopt_e=None):
@@ -331,6 +343,17 @@ class Engine:
         self._mc_run("drna_mc_run_cofold", head, [], ("seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed", "oligo_fraction", "bonus"), 6,
                      shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state, state, counters, best, L_const,
                      subopt_e)
+
+    def self_dimer(self, seqs):
+        """Every sequence folded against a copy of itself (the reference's ``RNA.fold_compound(s + "&" + s).pf_dimer()`` of -o on,
+        utils/energy_scores.py:412-419): dict(FA, FcAA, FAA (kcal/mol, float64[R]; FAA is cofold_batch's FAB of s & s),
+        oligo_fraction (dimer_multichain_energy.oligo_fraction)).  The engine needs max_L >= len(s), not twice that; any
+        number of sequences."""
+        R, L = _equal_length(seqs)
+        F4 = np.zeros((R, 4), dtype=np.float64)
+        frac = np.zeros(R, dtype=np.float64)
+        self._check(self._L.drna_self_dimer_batch(self._h, R, L, "".join(seqs).encode("ascii"), F4.ctypes.data, frac.ctypes.data))
+        return {"FA": F4[:, 0], "FcAA": F4[:, 2], "FAA": F4[:, 3], "oligo_fraction": frac}
 
     def subopt_energy(self, seqs, want_both=False):
         """Energy (dcal/mol) of the second-best structure of each sequence as the reference's -nd on path takes it from

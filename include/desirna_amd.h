@@ -379,6 +379,37 @@ int drna_mc_run_cofold_nd(drna_engine *e, int R, int L, int cut, int n_iter, con
                           double *oligo_frac, double *bonus, int64_t *counters, char *best_seq, char *best_ss, double *best,
                           double *subopt_e);
 
+/*
+ * Avoid oligomerization (-oa on = the reference's -o on, oligo_state "avoid"; utils/energy_scores.py:118-119, :412-419).
+ *
+ * drna_self_dimer_batch: the partition function of every sequence folded against a copy of itself (s & s), replacing
+ * RNA.fold_compound(s + "&" + s).pf_dimer() and dimer_multichain_energy.oligo_fraction (:36-50).  seqs: R x L letters.
+ * F4[r] = {FA, FB (the same strand again), FcAA, FAA} in kcal/mol, in drna_cofold_batch's layout and with its values for
+ * (s + s, cut = L) -- the symmetry factor of two equal strands included; oligo_frac (R doubles, may be NULL) = the fraction of
+ * strands bound in the dimer at 1 mM.  L <= max_L: the engine is sized for L, not 2 L (fold_self_dimer.hpp stores ~1.5 L^2 cells,
+ * which fit the partition function's workspace slot of an L-nt sequence; nothing is allocated).  R is not limited by max_R: a
+ * larger batch goes through the workspace slots in chunks.  Sequences of at most "self_dimer_lds_max" nucleotides (read-only
+ * option, 62) keep every table in LDS; option "self_dimer_lds" (default 1) = 0 sends every length to the workspace kernel.
+ * Results are bit-identical either way.
+ *
+ * drna_mc_run_oa: drna_mc_run (subopt_e NULL) or drna_mc_run_nd (subopt_e given) with one more step: after the score batch of
+ * the R proposals has drained, all R proposals get their self-dimer partition function in one launch of R workgroups;
+ * oligo_fraction from it, and -kT ln(1 - oligo_fraction) is the LAST addition to the score, after the negative-design term
+ * (the reference's order, :104-119).  The random draws are those of drna_mc_run.
+ *   oligo_frac, bonus   R doubles, in/out: the values that belong to each replica's current state; travel with an accepted state
+ *   best                the two-strand layout: {1-MCC, score, Epf, Ed, oligo_fraction, bonus[, subopt_e]}
+ * New symbols: no existing signature changes, DRNA_ABI_VERSION stays 3.
+ */
+int drna_self_dimer_batch(drna_engine *e, int R, int L, const char *seqs, double *F4, double *oligo_frac);
+int drna_mc_run_oa(drna_engine *e, int R, int L, int n_iter, const char *target, const int32_t *partner,
+                   const unsigned char *allowed_mask, const int32_t *snake_of, int n_snakes, const int32_t *snake_off,
+                   const int32_t *snake_nodes, const int32_t *snake_nstates, const char *snake_states,
+                   const int32_t *shelf_index, int n_shelves, double tm_max, double tm_min, int targeted, const double *temps,
+                   double Lconst, int n_terms, const int32_t *term_id, const double *term_w, uint32_t flags,
+                   uint32_t *rng_state, char *seqs, char *mfe_ss, double *score, double *mcc1, double *Epf, double *Ed,
+                   int64_t *counters, char *best_seq, char *best_ss, double *best, double *subopt_e, double *oligo_frac,
+                   double *bonus);
+
 #ifdef __cplusplus
 }
 #endif
