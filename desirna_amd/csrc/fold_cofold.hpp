@@ -359,6 +359,20 @@ struct CoPfSmem : PfSmem {
   double qA3[MAXN + 3], qB5[MAXN + 3];
 };
 
+// what cofold_pf_body uses of its shared memory, for N nucleotides in all (both strands): the kernels whose tables live in LDS,
+// or whose 1-D arrays need not be PfSmem's
+template <int N>
+struct CoPfSmemCore {
+  double stack[64];
+  double mmH[128], mmI[128], mm1n[128], mm23[128], mmM[128], mmExt[128];
+  double int11[1024];
+  double d5[32], d3[32];
+  double q5[N + 2];
+  double qA3[N + 3], qB5[N + 3];
+  unsigned char S[N + 4];
+  int flag;
+};
+
 // Boltzmann factor of the interior loop (u1,u2) between a pair of type t and the inner pair given by its info byte,
 // scale[u1+u2+2] included
 template <class SM>
@@ -395,37 +409,167 @@ __device__ __forceinline__ double co_pf_endstem(const double* mm, const SM& sm, 
   return 1.0;
 }
 
-// partition function of pair r by the calling workgroup; QB, QM, QM1 (doubles) and INFO (bytes), diagonal-major with pitch
-// ld >= n + 2, live where the caller put them (workspace slot or LDS); sm holds the members of CoPfSmem
-template <int NT, class SM>
+// Where the cells of the QB / QM / QM1 / INFO tables live.  A layout carries the two lengths, maps the cell (p, p + d) to its
+// entry (at(d <= 0, .) reads 0: the empty segment), says how many cells diagonal d has, how many leading entries hold the
+// empty segment, how the letters get into sm.S, and whether the two strands are known to be equal.
+// Square: diagonal-major with pitch ld >= n + 2, n + 1 rows, row 0 = the empty segments (workspace slot or LDS).
+struct CoSquare {
+  int n, cut, ld;
+  static constexpr bool homodimer = false;
+  __device__ __forceinline__ int at(int d, int p) const { return d * ld + p; }
+  __device__ __forceinline__ int cells(int d) const { return n - d; }
+  __device__ __forceinline__ int zeros() const { return ld; }
+  template <int NT, class SM>
+  __device__ __forceinline__ void load(SM& sm, const char* seqs, int r, int tid) const {
+    load_sequence<NT>(sm, seqs + (long long)r * n, n, tid);
+  }
+};
+
+// two equal strands (n == 2 cut and the same letters): the homodimer, whose connected structures count half
+template <class SM>
+__device__ __forceinline__ bool co_homodimer(const SM& sm, int n, int cut) {
+  bool sym = n == 2 * cut;
+  for (int k = 1; sym && k <= cut; k++) sym = sm.S[k] == sm.S[cut + k];
+  return sym;
+}
+
+// ---- the 1-D columns.  One wave each, the lanes share the split points, one fixed-order wave sum per entry, every lane stores
+// the same value.  The inside sweep advances qA3 / qB5 one entry per diagonal; the outside kernel rebuilds all four from the
+// finished tables.  tAU = PfTables::TermAU, all these functions need of the energy tables.
+
+// qA3[x] of [x .. cut] from qA3[x + 1 ..]; in the sweep x = cut - d
+template <class SM, class LAY>
+__device__ __forceinline__ void co_qA3_step(SM& sm, const LAY& lay, const double* QB, const unsigned char* INFO,
+                                            int x, double tAU, double sc1, int lane) {
+  const int cut = lay.cut;
+  double s = 0.0;
+  for (int k = x + 1 + lane; k <= cut; k += WAVE) {
+    const int c = lay.at(k - x, x);
+    const int fi = INFO[c];
+    if (!fi) continue;
+    const int t = rtype_of(fi >> 4);
+    s += QB[c] * (t > 2 ? tAU : 1.0) * co_pf_endstem(sm.mmExt, sm, t, x > 1, sm.S[x - 1], k < cut, sm.S[k + 1]) * sm.qA3[k + 1];
+  }
+  s = wave_sum_f64(s);
+  sm.qA3[x] = sm.qA3[x + 1] * sc1 + s;
+}
+
+// qB5[y] of [cut + 1 .. y] from qB5[.. y - 1]; in the sweep y = cut + 1 + d
+template <class SM, class LAY>
+__device__ __forceinline__ void co_qB5_step(SM& sm, const LAY& lay, const double* QB, const unsigned char* INFO,
+                                            int y, double tAU, double sc1, int lane) {
+  const int n = lay.n, cut = lay.cut;
+  double s = 0.0;
+  for (int k = cut + 1 + lane; k < y; k += WAVE) {
+    const int c = lay.at(y - k, k);
+    const int fi = INFO[c];
+    if (!fi) continue;
+    const int t = rtype_of(fi >> 4);
+    s += sm.qB5[k - 1] * QB[c] * (t > 2 ? tAU : 1.0) * co_pf_endstem(sm.mmExt, sm, t, k > cut + 1, sm.S[k - 1], y < n, sm.S[y + 1]);
+  }
+  s = wave_sum_f64(s);
+  sm.qB5[y] = sm.qB5[y - 1] * sc1 + s;
+}
+
+// q5[0 .. n]: the exterior loop over the concatenation
+template <class SM, class LAY>
+__device__ __forceinline__ void co_q5_column(SM& sm, const LAY& lay, const double* QB, const unsigned char* INFO,
+                                             double tAU, double sc1, int lane) {
+  const int n = lay.n, cut = lay.cut;
+  sm.q5[0] = 1.0;
+  for (int j = 1; j <= n; j++) {
+    double s = 0.0;
+    for (int i = lane + 1; i < j; i += WAVE) {
+      const int c = lay.at(j - i, i);
+      const int fi = INFO[c];
+      if (!fi) continue;
+      const int t = rtype_of(fi >> 4);
+      const bool h5 = i > 1 && co_same(i - 1, i, cut), h3 = j < n && co_same(j, j + 1, cut);
+      s += sm.q5[i - 1] * QB[c] * (t > 2 ? tAU : 1.0) * co_pf_endstem(sm.mmExt, sm, t, h5, sm.S[i - 1], h3, sm.S[j + 1]);
+    }
+    s = wave_sum_f64(s);
+    sm.q5[j] = sm.q5[j - 1] * sc1 + s;
+  }
+}
+
+// q3[1 .. n + 1]: the suffix column of [i .. n], built the way q5 is (the outside kernel's exterior term)
+template <class SM, class LAY>
+__device__ __forceinline__ void co_q3_column(SM& sm, const LAY& lay, const double* QB, const unsigned char* INFO,
+                                             double tAU, double sc1, int lane) {
+  const int n = lay.n, cut = lay.cut;
+  sm.q3[n + 1] = 1.0;
+  for (int i = n; i >= 1; i--) {
+    double s = 0.0;
+    for (int j = i + 1 + lane; j <= n; j += WAVE) {
+      const int c = lay.at(j - i, i);
+      const int fi = INFO[c];
+      if (!fi) continue;
+      const int t = rtype_of(fi >> 4);
+      const bool h5 = i > 1 && co_same(i - 1, i, cut), h3 = j < n && co_same(j, j + 1, cut);
+      s += QB[c] * (t > 2 ? tAU : 1.0) * co_pf_endstem(sm.mmExt, sm, t, h5, sm.S[i - 1], h3, sm.S[j + 1]) * sm.q3[j + 1];
+    }
+    s = wave_sum_f64(s);
+    sm.q3[i] = sm.q3[i + 1] * sc1 + s;
+  }
+}
+
+// the four free energies of pair r from the finished columns (one lane): F4[r] = FA, FB, FcAB, FAB, and the status word
+template <class SM, class LAY>
+__device__ __forceinline__ void co_pf_finish(const SM& sm, const CoArgs& A, const LAY& lay, int r) {
+  const PfTables& T = *A.F;
+  const int n = lay.n, cut = lay.cut;
+  const double kT = T.kT / 1000.0, lsc = log(T.pf_scale);
+  const double Q0 = sm.q5[n];
+  double* out = A.F4 + (long long)r * 4;
+  if (!(Q0 > 0.0) || !(Q0 < 1.0e300)) {
+    A.status_pf[r] = ST_PF_RANGE;
+    for (int k = 0; k < 4; k++) out[k] = 0.0;
+  } else if (cut <= 0) {
+    A.status_pf[r] = ST_OK;
+    out[0] = out[3] = -kT * (log(Q0) + n * lsc); out[1] = 0.0; out[2] = 999.0;
+  } else {
+    // strand partition functions: scale^len when a strand cannot fold at all
+    const double QA = sm.qA3[1], QB_ = sm.qB5[n];
+    double QAB = (Q0 - QA * QB_) * A.eDuplexInit;
+    if (LAY::homodimer || co_homodimer(sm, n, cut)) QAB *= 0.5;      // rotational symmetry of a homodimer
+    A.status_pf[r] = ST_OK;
+    out[0] = -kT * (log(QA) + cut * lsc);
+    out[1] = -kT * (log(QB_) + (n - cut) * lsc);
+    out[2] = QAB > 1e-17 ? -kT * (log(QAB) + n * lsc) : 999.0;
+    out[3] = -kT * (log(QA * QB_ + QAB) + n * lsc);
+  }
+}
+
+// partition function of pair r by the calling workgroup; QB, QM, QM1 (doubles) and INFO (bytes) live where the caller put them
+// (workspace slot or LDS), their cells where the layout says; sm holds the members of CoPfSmemCore
+template <int NT, class SM, class LAY>
 __device__ __forceinline__ void cofold_pf_body(SM& sm, const CoArgs& A, int r, double* QB, double* QM, double* QM1, unsigned char* INFO,
-                                               int ld) {
+                                               const LAY lay) {
   const PfTables& T = *A.F;
   const Plan& P = *A.plan;
-  const int n = A.L, cut = A.cut;
+  const int n = lay.n, cut = lay.cut;
   const int tid = threadIdx.x, lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
-  int32_t* status = A.status_pf;
 
   stage_energy_tables<NT>(sm, T, tid);
-  for (int k = tid; k < ld; k += NT) { QM[k] = 0.0; QM1[k] = 0.0; QB[k] = 0.0; INFO[k] = 0; }   // row 0
+  for (int k = tid; k < lay.zeros(); k += NT) { QM[k] = 0.0; QM1[k] = 0.0; QB[k] = 0.0; INFO[k] = 0; }   // the empty segments
   // empty segments, and the one-nucleotide segments next to the nick (the sweep advances these arrays from diagonal 1 on)
   for (int k = tid; k <= n + 2; k += NT) {
     sm.qA3[k] = cut >= 1 && k == cut ? A.scale[1] : 1.0;
     sm.qB5[k] = cut >= 1 && k == cut + 1 && k <= n ? A.scale[1] : 1.0;
   }
-  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
+  lay.template load<NT>(sm, A.seqs, r, tid);
   if (sm.flag) {
-    if (tid == 0) { status[r] = ST_BAD_CHAR; for (int k = 0; k < 4; k++) A.F4[r * 4 + k] = 0.0; }
+    if (tid == 0) { A.status_pf[r] = ST_BAD_CHAR; for (int k = 0; k < 4; k++) A.F4[r * 4 + k] = 0.0; }
     return;
   }
   PfArgs H;                        // for pf_hairpin()
-  H.T = A.F; H.plan = A.plan; H.hp_w = A.hp_w; H.scale = A.scale; H.eMLb = A.eMLb; H.seqs = A.seqs; H.L = n; H.ld = ld;
+  H.T = A.F; H.plan = A.plan; H.hp_w = A.hp_w; H.scale = A.scale; H.eMLb = A.eMLb; H.seqs = A.seqs; H.L = n; H.ld = 0;
   H.ws = nullptr; H.ws_stride = 0; H.Epf = nullptr; H.status = nullptr;
   const double b1 = A.eMLb[1], sc1 = A.scale[1], sc2 = A.scale[2];
 
   for (int d = 1; d < n; d++) {
-    const int ncell = n - d;
+    const int ncell = lay.cells(d);
     // one wave per cell: the lanes share the interior-loop shapes and the split points; fixed-order wave sums
     for (int i = wave + 1; i <= ncell; i += NT / WAVE) {
       const int j = i + d;
@@ -446,15 +590,16 @@ __device__ __forceinline__ void cofold_pf_body(SM& sm, const CoArgs& A, int r, d
           if (dp < 1) continue;
           const int p = i + 1 + u1, q = j - 1 - u2;
           if (!co_same(i, p, cut) || !co_same(q, j, cut)) continue;
-          const int fi = INFO[dp * ld + p];
+          const int c = lay.at(dp, p);
+          const int fi = INFO[c];
           if (!fi) continue;
-          acc += QB[dp * ld + p] * co_pf_intloop(sm, T, A.scale, u1, u2, t, si1, sj1, fi);
+          acc += QB[c] * co_pf_intloop(sm, T, A.scale, u1, u2, t, si1, sj1, fi);
         }
         double tmp = 0.0;
         if (adj_i && adj_j) {
           for (int k = i + 3 + lane; k <= j - 2; k += WAVE) {
             if (k - 1 == cut) continue;                               // k-1, k must be neighbours
-            tmp += QM[(k - i - 2) * ld + i + 1] * QM1[(j - 1 - k) * ld + k];
+            tmp += QM[lay.at(k - i - 2, i + 1)] * QM1[lay.at(j - 1 - k, k)];
           }
         }
         acc = wave_sum_f64(acc);
@@ -463,89 +608,31 @@ __device__ __forceinline__ void cofold_pf_body(SM& sm, const CoArgs& A, int r, d
         info = (rtype_of(t) << 4) | (sm.S[j + 1] << 2) | sm.S[i - 1];
       }
       const bool h5 = i > 1 && co_same(i - 1, i, cut), h3 = j < n && co_same(j, j + 1, cut);
-      double m1 = adj_j ? QM1[(d - 1) * ld + i] * b1 : 0.0;
+      double m1 = adj_j ? QM1[lay.at(d - 1, i)] * b1 : 0.0;
       if (t) m1 += qb * T.MLintern * tau * co_pf_endstem(sm.mmM, sm, t, h5, sm.S[i - 1], h3, sm.S[j + 1]);
       double m = 0.0;
       for (int k = i + 1 + lane; k <= j - 1; k += WAVE) {
-        double left = (k - 1 != cut) ? QM[(k - 1 - i) * ld + i] : 0.0;
+        double left = (k - 1 != cut) ? QM[lay.at(k - 1 - i, i)] : 0.0;
         if (co_same(i, k, cut)) left += A.eMLb[k - i];
-        m += left * QM1[(j - k) * ld + k];
+        m += left * QM1[lay.at(j - k, k)];
       }
       m = m1 + wave_sum_f64(m);
       if (lane == 0) {
-        QB[d * ld + i] = qb;
-        INFO[d * ld + i] = (unsigned char)info;
-        QM1[d * ld + i] = m1;
-        QM[d * ld + i] = m;
+        const int c = lay.at(d, i);
+        QB[c] = qb;
+        INFO[c] = (unsigned char)info;
+        QM1[c] = m1;
+        QM[c] = m;
       }
     }
     __syncthreads();
-    if (wave == 0 && cut - d >= 1) {
-      const int x = cut - d;
-      double s = 0.0;
-      for (int k = x + 1 + lane; k <= cut; k += WAVE) {
-        const int fi = INFO[(k - x) * ld + x];
-        if (!fi) continue;
-        const int t = rtype_of(fi >> 4);
-        s += QB[(k - x) * ld + x] * (t > 2 ? T.TermAU : 1.0) *
-             co_pf_endstem(sm.mmExt, sm, t, x > 1, sm.S[x - 1], k < cut, sm.S[k + 1]) * sm.qA3[k + 1];
-      }
-      s = wave_sum_f64(s);
-      sm.qA3[x] = sm.qA3[x + 1] * sc1 + s;
-    }
-    if (wave == (NT > WAVE ? 1 : 0) && cut > 0 && cut + 1 + d <= n) {
-      const int y = cut + 1 + d;
-      double s = 0.0;
-      for (int k = cut + 1 + lane; k < y; k += WAVE) {
-        const int fi = INFO[(y - k) * ld + k];
-        if (!fi) continue;
-        const int t = rtype_of(fi >> 4);
-        s += sm.qB5[k - 1] * QB[(y - k) * ld + k] * (t > 2 ? T.TermAU : 1.0) *
-             co_pf_endstem(sm.mmExt, sm, t, k > cut + 1, sm.S[k - 1], y < n, sm.S[y + 1]);
-      }
-      s = wave_sum_f64(s);
-      sm.qB5[y] = sm.qB5[y - 1] * sc1 + s;
-    }
+    if (wave == 0 && cut - d >= 1) co_qA3_step(sm, lay, QB, INFO, cut - d, T.TermAU, sc1, lane);
+    if (wave == (NT > WAVE ? 1 : 0) && cut > 0 && cut + 1 + d <= n) co_qB5_step(sm, lay, QB, INFO, cut + 1 + d, T.TermAU, sc1, lane);
     __syncthreads();
   }
   if (wave != 0) return;
-  sm.q5[0] = 1.0;
-  for (int j = 1; j <= n; j++) {
-    double s = 0.0;
-    for (int i = lane + 1; i < j; i += WAVE) {
-      const int fi = INFO[(j - i) * ld + i];
-      if (!fi) continue;
-      const int t = rtype_of(fi >> 4);
-      const bool h5 = i > 1 && co_same(i - 1, i, cut), h3 = j < n && co_same(j, j + 1, cut);
-      s += sm.q5[i - 1] * QB[(j - i) * ld + i] * (t > 2 ? T.TermAU : 1.0) * co_pf_endstem(sm.mmExt, sm, t, h5, sm.S[i - 1], h3, sm.S[j + 1]);
-    }
-    s = wave_sum_f64(s);
-    sm.q5[j] = sm.q5[j - 1] * sc1 + s;
-  }
-  if (lane == 0) {
-    const double kT = T.kT / 1000.0, lsc = log(T.pf_scale);
-    const double Q0 = sm.q5[n];
-    double* out = A.F4 + (long long)r * 4;
-    if (!(Q0 > 0.0) || !(Q0 < 1.0e300)) {
-      status[r] = ST_PF_RANGE;
-      for (int k = 0; k < 4; k++) out[k] = 0.0;
-    } else if (cut <= 0) {
-      status[r] = ST_OK;
-      out[0] = out[3] = -kT * (log(Q0) + n * lsc); out[1] = 0.0; out[2] = 999.0;
-    } else {
-      // strand partition functions: scale^len when a strand cannot fold at all
-      const double QA = sm.qA3[1], QB_ = sm.qB5[n];
-      double QAB = (Q0 - QA * QB_) * A.eDuplexInit;
-      bool sym = n == 2 * cut;
-      for (int k = 1; sym && k <= cut; k++) sym = sm.S[k] == sm.S[cut + k];
-      if (sym) QAB *= 0.5;                                           // rotational symmetry of a homodimer
-      status[r] = ST_OK;
-      out[0] = -kT * (log(QA) + cut * lsc);
-      out[1] = -kT * (log(QB_) + (n - cut) * lsc);
-      out[2] = QAB > 1e-17 ? -kT * (log(QAB) + n * lsc) : 999.0;
-      out[3] = -kT * (log(QA * QB_ + QAB) + n * lsc);
-    }
-  }
+  co_q5_column(sm, lay, QB, INFO, T.TermAU, sc1, lane);
+  if (lane == 0) co_pf_finish(sm, A, lay, r);
 }
 
 template <int NT>
@@ -554,7 +641,8 @@ __global__ __launch_bounds__(NT) void cofold_pf_kernel(CoArgs A) {
   const int r = blockIdx.x;
   double* base = A.wsp + (long long)r * A.wsp_stride;
   const long long tab = (long long)A.ld * A.ld;
-  cofold_pf_body<NT>(sm, A, r, base, base + tab, base + 2 * tab, reinterpret_cast<unsigned char*>(base + 3 * tab), A.ld);
+  cofold_pf_body<NT>(sm, A, r, base, base + tab, base + 2 * tab, reinterpret_cast<unsigned char*>(base + 3 * tab),
+                     CoSquare{A.L, A.cut, A.ld});
 }
 
 }  // namespace drna

@@ -2,10 +2,10 @@
 // and partition function of fold_cofold.hpp with every 2-D table of the workgroup in LDS instead of HBM/L2.
 //
 // Design pairs are short (the reference's two-strand examples are 18 + 18 nt), so the general kernels spend their diagonals
-// waiting for L2: ~70 diagonals of a few cells each, every operand a global load behind a barrier.  Here the same cell bodies
-// (cofold_mfe_body / cofold_pf_body: same candidates, same order of minima and of summation) read and write LDS, so the results
-// are the general kernels' bit for bit; only the 1-D arrays and the staged energy tables get a layout of their own, because
-// MfeSmemCore<MAXN> / PfSmem size theirs for 2046 nt.
+// waiting for L2: ~70 diagonals of a few cells each, every operand a global load behind a barrier.  Here cofold_mfe_body and
+// cofold_pf_body are handed tables in LDS (the partition function in the square layout CoSquare with pitch n + 2), so the
+// results are the general kernels' bit for bit.  The 1-D arrays and the staged energy tables are sized for CO_LDS_MAX
+// (MfeSmemCore<CO_LDS_MAX>, CoPfSmemCore<CO_LDS_MAX>) instead of the 2046 nt of the general kernels' structs.
 //
 // LDS per workgroup at CO_LDS_MAX = 64 (pitch ld = n + 2 <= 66, n + 1 rows):
 //   MFE  3 int32 tables x 66 x 66 = 52,272 B + staged tables and 1-D arrays  9,5 KB  ->  ~61 KB
@@ -24,18 +24,9 @@ struct CoLdsMfeSmem : MfeSmemCore<CO_LDS_MAX> {
   int32_t Wc[CO_LDS_LD * CO_LDS_LD], FML[CO_LDS_LD * CO_LDS_LD], EXT[CO_LDS_LD * CO_LDS_LD];
 };
 
-// what cofold_pf_body uses of CoPfSmem, sized for CO_LDS_MAX
-struct CoLdsPfSmem {
-  double stack[64];
-  double mmH[128], mmI[128], mm1n[128], mm23[128], mmM[128], mmExt[128];
-  double int11[1024];
-  double d5[32], d3[32];
-  double q5[CO_LDS_MAX + 2];
-  double qA3[CO_LDS_MAX + 3], qB5[CO_LDS_MAX + 3];
+struct CoLdsPfSmem : CoPfSmemCore<CO_LDS_MAX> {
   double QB[CO_LDS_LD * CO_LDS_LD], QM[CO_LDS_LD * CO_LDS_LD], QM1[CO_LDS_LD * CO_LDS_LD];
   unsigned char INFO[CO_LDS_LD * CO_LDS_LD];
-  unsigned char S[CO_LDS_MAX + 4];
-  int flag;
 };
 
 // the host launches these for A.L <= CO_LDS_MAX only; a longer pair leaves at once with the status of an internal error
@@ -58,7 +49,7 @@ __global__ __launch_bounds__(NT) void cofold_pf_lds_kernel(CoArgs A) {
     if (threadIdx.x == 0) A.status_pf[r] = ST_TRACEBACK;
     return;
   }
-  cofold_pf_body<NT>(sm, A, r, sm.QB, sm.QM, sm.QM1, sm.INFO, A.L + 2);
+  cofold_pf_body<NT>(sm, A, r, sm.QB, sm.QM, sm.QM1, sm.INFO, CoSquare{A.L, A.cut, A.L + 2});
 }
 
 }  // namespace drna

@@ -5,8 +5,8 @@
 // strands (kappa = expDuplexInit, halved for two equal strands), so that the weights sum to exp(-FAB / kT).
 //
 // Runs after cofold_pf_kernel on the tables that kernel left in the workspace (QB, QM, QM1, INFO, diagonal-major); the 1-D
-// columns q5, qA3, qB5 are rebuilt here in that kernel's order of summation (four waves side by side, with the suffix column
-// q3), so cofold_pf_kernel stays as it is.  Like outside_kernel (fold_outside.hpp) the weights are GATHERED: diagonals
+// columns q5, qA3, qB5 are rebuilt here by that kernel's own column functions (four waves side by side, with the suffix column
+// q3), so cofold_pf_kernel need not keep them.  Like outside_kernel (fold_outside.hpp) the weights are GATHERED: diagonals
 // n-1 ... 1, a cell pulls from finished cells of larger span, every fp64 sum has one writer and a fixed order.  Like
 // cofold_pf_kernel one wave works one cell, the lanes share the 496 interior-loop shapes and the split points.
 //
@@ -107,66 +107,15 @@ __global__ __launch_bounds__(NT) void cofold_outside_kernel(CoOutArgs A) {
   }
   const double b1 = A.eMLb[1], sc1 = A.scale[1], sc2 = A.scale[2];
 
-  // ---- the 1-D columns, each by one wave in cofold_pf_kernel's order: qA3 of [x..cut], qB5 of [cut+1..y], q5 of [1..j], and
-  // the suffix column q3 of [i..n] built the way q5 is.  They read QB / INFO only, so the four run side by side.
-  if (wave == 0) {
-    for (int x = cut - 1; x >= 1; x--) {
-      double s = 0.0;
-      for (int k = x + 1 + lane; k <= cut; k += WAVE) {
-        const int fi = INFO[(k - x) * ld + x];
-        if (!fi) continue;
-        const int t = rtype_of(fi >> 4);
-        s += QB[(k - x) * ld + x] * (t > 2 ? T.TermAU : 1.0) *
-             co_pf_endstem(sm.mmExt, sm, t, x > 1, sm.S[x - 1], k < cut, sm.S[k + 1]) * sm.qA3[k + 1];
-      }
-      s = wave_sum_f64(s);
-      sm.qA3[x] = sm.qA3[x + 1] * sc1 + s;          // every lane stores the same value (here and below)
-    }
-  }
-  if (wave == 1 % NW) {
-    for (int y = cut + 2; y <= n; y++) {
-      double s = 0.0;
-      for (int k = cut + 1 + lane; k < y; k += WAVE) {
-        const int fi = INFO[(y - k) * ld + k];
-        if (!fi) continue;
-        const int t = rtype_of(fi >> 4);
-        s += sm.qB5[k - 1] * QB[(y - k) * ld + k] * (t > 2 ? T.TermAU : 1.0) *
-             co_pf_endstem(sm.mmExt, sm, t, k > cut + 1, sm.S[k - 1], y < n, sm.S[y + 1]);
-      }
-      s = wave_sum_f64(s);
-      sm.qB5[y] = sm.qB5[y - 1] * sc1 + s;
-    }
-  }
-  if (wave == 2 % NW) {
-    sm.q5[0] = 1.0;
-    for (int j = 1; j <= n; j++) {
-      double s = 0.0;
-      for (int i = lane + 1; i < j; i += WAVE) {
-        const int fi = INFO[(j - i) * ld + i];
-        if (!fi) continue;
-        const int t = rtype_of(fi >> 4);
-        const bool h5 = i > 1 && co_same(i - 1, i, cut), h3 = j < n && co_same(j, j + 1, cut);
-        s += sm.q5[i - 1] * QB[(j - i) * ld + i] * (t > 2 ? T.TermAU : 1.0) * co_pf_endstem(sm.mmExt, sm, t, h5, sm.S[i - 1], h3, sm.S[j + 1]);
-      }
-      s = wave_sum_f64(s);
-      sm.q5[j] = sm.q5[j - 1] * sc1 + s;
-    }
-  }
-  if (wave == 3 % NW) {
-    sm.q3[n + 1] = 1.0;
-    for (int i = n; i >= 1; i--) {
-      double s = 0.0;
-      for (int j = i + 1 + lane; j <= n; j += WAVE) {
-        const int fi = INFO[(j - i) * ld + i];
-        if (!fi) continue;
-        const int t = rtype_of(fi >> 4);
-        const bool h5 = i > 1 && co_same(i - 1, i, cut), h3 = j < n && co_same(j, j + 1, cut);
-        s += QB[(j - i) * ld + i] * (t > 2 ? T.TermAU : 1.0) * co_pf_endstem(sm.mmExt, sm, t, h5, sm.S[i - 1], h3, sm.S[j + 1]) * sm.q3[j + 1];
-      }
-      s = wave_sum_f64(s);
-      sm.q3[i] = sm.q3[i + 1] * sc1 + s;
-    }
-  }
+  // ---- the 1-D columns, each by one wave with the inside sweep's own steps (fold_cofold.hpp): qA3 of [x..cut], qB5 of
+  // [cut+1..y], q5 of [1..j] and the suffix column q3 of [i..n].  They read QB / INFO only, so the four run side by side.
+  const CoSquare lay{n, cut, ld};
+  if (wave == 0)
+    for (int x = cut - 1; x >= 1; x--) co_qA3_step(sm, lay, QB, INFO, x, T.TermAU, sc1, lane);
+  if (wave == 1 % NW)
+    for (int y = cut + 2; y <= n; y++) co_qB5_step(sm, lay, QB, INFO, y, T.TermAU, sc1, lane);
+  if (wave == 2 % NW) co_q5_column(sm, lay, QB, INFO, T.TermAU, sc1, lane);
+  if (wave == 3 % NW) co_q3_column(sm, lay, QB, INFO, T.TermAU, sc1, lane);
   __syncthreads();
   const double QAs = sm.qA3[1], QBs = sm.qB5[n];     // the strands' own partition functions
 
@@ -320,9 +269,7 @@ __global__ __launch_bounds__(NT) void cofold_outside_kernel(CoOutArgs A) {
   }
 
   // ---- probabilities (in place of OB), kappa on the connected part only
-  bool sym = n == 2 * cut;
-  for (int k = 1; sym && k <= cut; k++) sym = sm.S[k] == sm.S[cut + k];
-  const double kap = sym ? 0.5 * A.eDuplexInit : A.eDuplexInit;   // rotational symmetry of a homodimer
+  const double kap = co_homodimer(sm, n, cut) ? 0.5 * A.eDuplexInit : A.eDuplexInit;   // rotational symmetry of a homodimer
   const double Z = (sm.q5[n] - QAs * QBs) * kap + QAs * QBs;
   for (int d = 1; d < n; d++) {
     for (int i = tid + 1; i <= n - d; i += NT) {

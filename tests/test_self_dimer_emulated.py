@@ -16,6 +16,12 @@ def emu(blob):
     return emu_self_dimer.EmuSelfDimer(blob)
 
 
+@pytest.fixture(scope="module")
+def pair_emu(blob):
+    from tests.emu import emu_cofold_lds
+    return emu_cofold_lds.EmuCofoldLds(blob)
+
+
 def _rand(rng, n, alphabet="ACGU"):
     return "".join(rng.choice(list(alphabet), size=n))
 
@@ -69,6 +75,20 @@ def test_both_kernels_bit_identical(emu, oracle):
     b = _check(emu, oracle, seqs, 128, lds=False)
     c, _ = emu.fold(seqs, nt=64, lds=False)
     assert a.tobytes() == b.tobytes() == c.tobytes()
+
+
+@pytest.mark.parametrize("L,nt", [(2, 64), (5, 64), (13, 64), (14, 64), (25, 64), (32, 64), (14, 128)])
+def test_bit_identical_to_the_pair_kernel(emu, pair_emu, L, nt):
+    """one body, two layouts: both self-dimer kernels return the bytes of cofold_pf_lds_kernel on s & s, all four columns
+    (32 is the longest s whose doubled pair that kernel takes)"""
+    pair = pair_emu
+    assert 2 * L <= pair.max_len
+    s = _rand(np.random.default_rng(300 + L + nt), L, "GCGCAU")
+    want = pair.cofold([s + "&" + s], nt=nt)[2]
+    for lds in (True, False):
+        F4, st = emu.fold([s], nt=nt, lds=lds)
+        assert not st.any()
+        assert F4.tobytes() == want.tobytes(), (s, lds, F4, want)
 
 
 def test_special_sequences(emu, oracle):

@@ -72,6 +72,18 @@ def cofold_paths(eng, seqs):
     return out
 
 
+def self_dimer(eng, seqs):
+    """every sequence against a copy of itself (-oa on) with the tables in LDS (option self_dimer_lds = 1) and in the workspace
+    slots (0), same process and engine; a sequence beyond self_dimer_lds_max takes the workspace kernel either way"""
+    out = {}
+    for lds in (0, 1):
+        eng.set_option("self_dimer_lds", lds)
+        eng.self_dimer(seqs)
+        out["pf_ms_lds%d" % lds] = eng.last_timing()["pf"]
+    eng.set_option("self_dimer_lds", 1)
+    return out
+
+
 MC_TARGET = "((((((..((((......&......))))..))))))"       # 18 + 18 nt
 MC_RESTR = "N" * 18 + "&" + "N" * 18
 MC_ITERS = 200
@@ -127,6 +139,7 @@ def nd_loop(eng, seqs):
 PAIRS = ((64, 18, 18), (64, 50, 50), (64, 100, 100))
 SUB_MAX = 79          # SUB_LDS_MAX (fold_subopt_lds.hpp)
 CO_HALF = 32          # CO_LDS_MAX / 2 (fold_cofold_lds.hpp)
+SD_MAX = 62           # SD_LDS_MAX (fold_self_dimer.hpp)
 # one round of a section -> (shapes (R, strand lengths ...), seed, a fresh generator per shape, rounds, derived figure)
 SECTIONS = {
     edef: (((64, 200), (128, 400)), 20260101, True, 3,
@@ -140,6 +153,7 @@ SECTIONS = {
     subopt_structs: (((16, 100), (16, 200)), 5, False, 5, lambda R, v: ("ratio", v["kbest8_ms"] / v["kbest4_ms"])),
     cofold_paths: (((64, 18, 18), (64, CO_HALF, CO_HALF), (64, CO_HALF + 1, CO_HALF)), 5, False, 7,
                    lambda R, v: ("lds_over_general", (v["mfe_ms_lds1"] + v["pf_ms_lds1"]) / (v["mfe_ms_lds0"] + v["pf_ms_lds0"]))),
+    self_dimer: (((64, 36), (64, SD_MAX), (64, 100)), 5, False, 7, lambda R, v: ("lds_over_general", v["pf_ms_lds1"] / v["pf_ms_lds0"])),
     mc_cofold: (((64, 18, 18),), 5, False, 3,
                 lambda R, v: ("native_over_python", v["design_native_iter_per_s"] / v["design_python_iter_per_s"])),
 }
