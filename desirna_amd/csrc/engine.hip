@@ -44,6 +44,12 @@ static std::string g_create_error;
 #define DRNA_MFE_FARK_MIN_STRIPS 4
 #endif
 constexpr int MFE_FARK_MIN_STRIPS = DRNA_MFE_FARK_MIN_STRIPS;   // (measured against prebuilt variants)
+// hand-over flags hold (epoch << 12 | diagonal) for the strips and ((epoch * 8 + round) << 10 | diagonal) for the two-workgroup
+// kernel, compared wrap-safe: valid while live values are less than 2^31 apart, i.e. 2^19 (2^18) epochs.  Reset at a quarter of that.
+constexpr int STRIP_EPOCH_RESET = 1 << 17, DUAL_EPOCH_RESET = 1 << 16;
+// one set of hand-over flags of a multi-workgroup fold: ints flags on the device, zero when allocated; the epoch grows by one per
+// launch (strips) or call, and flags and epoch go back to zero at reset_at (flags_ready)
+struct EpochFlags { int* d = nullptr; size_t ints = 0; int epoch = 0; int reset_at = 0; };
 struct drna_engine {
   int device = 0, max_R = 0, max_L = 0, cus = 0;
   HostTables H;
@@ -63,7 +69,6 @@ struct drna_engine {
   int32_t* d_Emfe = nullptr;
   char* d_ss = nullptr;
   int32_t* d_Ed = nullptr;
-  size_t ed_cap = 0;
   // per-sequence status words, host-mapped so no copy is needed after the streams drain
   int32_t *h_status = nullptr, *d_status = nullptr;   // [0,R) mfe, [max_R, max_R+R) pf
   short* d_pt = nullptr;
@@ -106,12 +111,10 @@ struct drna_engine {
   bool dual = true;               // DRNA_DUAL=0 turns them off
   bool dual_force = false;        // option "dual" = 2: also beside a partition function (tests, diagnostics)
   int dual_cap = 0;               // sequences the exchange buffers hold
-  int dual_epoch = 0;             // grows by one per launch; flags and epoch go back to zero at DUAL_EPOCH_RESET (fold_common.hpp, DualLink)
-  int* d_dflags = nullptr;        // [2 kernels][dual_cap][64]
+  EpochFlags dflags{nullptr, 0, 0, DUAL_EPOCH_RESET};     // [2 kernels][R][64], grows with the batch (fold_common.hpp, DualLink)
   int32_t *d_xs = nullptr, *d_xa_mfe = nullptr, *d_xb_mfe = nullptr;
   // strip kernels (fold_pf_strip.hpp: 200 < n <= 2046, several workgroups per sequence): one flag line per (sequence, strip)
   int strips = 1;                 // 0 off (general kernel), 1 for n > 200, 2 also for 64 < n <= 200 (two strips; diagnostics)
-  int strip_epoch = 0;            // grows by one per launch; flags and epoch go back to zero at STRIP_EPOCH_RESET
   int flag_resets = 0;            // times the hand-over flags were zeroed because an epoch neared the compare range
   int strip_fault = 0;            // option "strip_fault": inject a lost strip (tests)
   bool cur_with_pf = false;       // the call being enqueued also folds the partition function
@@ -120,8 +123,7 @@ struct drna_engine {
   bool helper_fault = false;      // tests: the helper workgroups of the partition function leave at once (a lost partner)
   bool pf_helper = true;          // small batches: a helper workgroup per sequence computes the far multiloop split points of the
                                   // partition function (fold_pf_lds.hpp, pf_kfar_helper); option "pf_helper"
-  int* d_pflags = nullptr;        // its hand-over flags: per sequence two 128-byte lines
-  int pflags_cap = 0, pfh_epoch = 0;
+  EpochFlags pflags{nullptr, 0, 0, STRIP_EPOCH_RESET};    // its hand-over flags: per sequence two 128-byte lines, grows with the batch
   bool fused = true;              // small batches: both folds in ONE launch of 4 R workgroups (fold_fused.hpp); option "fused", DRNA_FUSED=0 turns it off.
                                   // On since the end of round 4: 0.413 against 0.420 ms of device time at R = 64 x L = 200 (the two launches' kernels
                                   // start and end a few us apart; the host pays the same 14 us either way)
@@ -137,7 +139,7 @@ struct drna_engine {
   // for the next SOLO_CALLS calls (option "solo_calls_left"); then one call probes again.  Any set_option of the paths resets it.
   int fallback_streak = 0, solo_left = 0;
   bool in_fallback = false;
-  int* d_sflags = nullptr;        // [2: partition function, MFE][max_R][STRIP_MAXS][32]
+  EpochFlags sflags{nullptr, 0, 0, STRIP_EPOCH_RESET};    // [2: partition function, MFE][max_R][STRIP_MAXS][32]; both halves share the epoch
   int32_t* d_srec = nullptr;      // MFE strips: exchange records and list counts, srec_stride int32 per sequence
   long long srec_stride = 0;
   long long* d_sclk = nullptr;    // DRNA_STRIP_DEBUG=1: start / end clocks of the MFE strip workgroups of the last launch
@@ -203,9 +205,6 @@ static CoArgs co_args(const drna_engine* e, const char* seqs, int L, int cut, in
   a.Emfe = e->d_Emfe; a.ss = e->d_ss; a.F4 = e->d_F4; a.status = e->d_status; a.status_pf = e->d_status + e->max_R;
   return a;
 }
-// hand-over flags hold (epoch << 12 | diagonal) for the strips and ((epoch * 8 + round) << 10 | diagonal) for the two-workgroup
-// kernel, compared wrap-safe: valid while live values are less than 2^31 apart, i.e. 2^19 (2^18) epochs.  Reset at a quarter of that.
-constexpr int STRIP_EPOCH_RESET = 1 << 17, DUAL_EPOCH_RESET = 1 << 16;
 #ifndef DRNA_PF_HELPER_NMIN
 #define DRNA_PF_HELPER_NMIN 95
 #endif
@@ -224,30 +223,36 @@ static int strips_for(const drna_engine* e, int n, int ld) {
   return S;
 }
 
-// flags (and, for the MFE fold, the record buffer) of the strip kernels: allocated (flags zeroed, once) on first use
+// The flags f, ints of them at least, ready for the next epoch: allocated and zeroed on first use or growth.  Flag compares are
+// wrap-safe over HALF the 32-bit range only (2^19 epochs of 4096 values): a slot that was never written, or not written for 2^19
+// launches (the MFE half of the strips after a long partition-function-only phase, a larger batch than seen before, more strips
+// than before), would then read as already published.  Every stream is idle here, so long before that point the flags go back to
+// zero and the epoch starts over.
+static int flags_ready(drna_engine* e, EpochFlags& f, size_t ints) {
+  if (f.ints < ints) {
+    if (f.d) (void)hipFree(f.d);
+    f.d = nullptr; f.ints = 0;
+    HIP_TRY(hipMalloc((void**)&f.d, ints * sizeof(int)));
+    f.ints = ints;
+  } else if (f.epoch >= f.reset_at) e->flag_resets++;
+  else return DRNA_OK;
+  HIP_TRY(hipMemset(f.d, 0, f.ints * sizeof(int)));
+  f.epoch = 0;
+  HIP_TRY(hipDeviceSynchronize());        // the memset runs on the null stream, the kernels on non-blocking streams of their own
+  return DRNA_OK;
+}
+static int flags_next(EpochFlags& f) { return f.epoch = (int)((unsigned)f.epoch + 1u); }   // reset by flags_ready() long before the half range
+static int epoch_base(int epoch) { return (int)((unsigned)epoch << 12); }       // of StripLink::base and PfArgs::hbase
+
+// flags (and, for the MFE fold, the record buffer) of the strip kernels, allocated on first use
 static int strip_flags(drna_engine* e, bool mfe) {
-  if (!e->d_sflags) {
-    const size_t b = (size_t)2 * e->max_R * STRIP_MAXS * 32 * sizeof(int);
-    HIP_TRY(hipMalloc((void**)&e->d_sflags, b));
-    HIP_TRY(hipMemset(e->d_sflags, 0, b));
-    HIP_TRY(hipDeviceSynchronize());      // the memset runs on the null stream, the kernels on non-blocking streams of their own
-    e->strip_epoch = 0;
-    if (getenv("DRNA_STRIP_DEBUG")) {
-      HIP_TRY(hipMalloc((void**)&e->d_sclk, (size_t)e->max_R * STRIP_MAXS * 2 * sizeof(long long)));
-      HIP_TRY(hipMalloc((void**)&e->d_sdbg, (size_t)2 * e->max_R * 8 * sizeof(int)));
-      HIP_TRY(hipMemset(e->d_sdbg, 0, (size_t)2 * e->max_R * 8 * sizeof(int)));
-      HIP_TRY(hipDeviceSynchronize());
-    }
-  }
-  // Flag compares are wrap-safe over HALF the 32-bit range only (2^19 epochs of 4096 values): a slot that was never written, or
-  // not written for 2^19 launches (the MFE half after a long partition-function-only phase, a larger batch than seen before,
-  // more strips than before), would then read as already published.  Every stream is idle here, so long before that point the
-  // flags go back to zero and the epochs start over.
-  if (e->strip_epoch >= STRIP_EPOCH_RESET) {
-    HIP_TRY(hipMemset(e->d_sflags, 0, (size_t)2 * e->max_R * STRIP_MAXS * 32 * sizeof(int)));
+  const bool first = !e->sflags.d;
+  { const int rc = flags_ready(e, e->sflags, (size_t)2 * e->max_R * STRIP_MAXS * 32); if (rc != DRNA_OK) return rc; }
+  if (first && getenv("DRNA_STRIP_DEBUG")) {
+    HIP_TRY(hipMalloc((void**)&e->d_sclk, (size_t)e->max_R * STRIP_MAXS * 2 * sizeof(long long)));
+    HIP_TRY(hipMalloc((void**)&e->d_sdbg, (size_t)2 * e->max_R * 8 * sizeof(int)));
+    HIP_TRY(hipMemset(e->d_sdbg, 0, (size_t)2 * e->max_R * 8 * sizeof(int)));
     HIP_TRY(hipDeviceSynchronize());
-    e->strip_epoch = 0;
-    e->flag_resets++;
   }
   if (mfe && !e->d_srec) {
     const int smax = std::min(STRIP_MAXS, strip_count(std::min(e->max_L, STRIP_NMAX), STRIP_WMAX) + 1);
@@ -256,24 +261,19 @@ static int strip_flags(drna_engine* e, bool mfe) {
   }
   return DRNA_OK;
 }
-static int next_strip_epoch(drna_engine* e) {
-  e->strip_epoch = (int)((unsigned)e->strip_epoch + 1u);          // reset by strip_flags() long before the compares' half range
-  return (int)((unsigned)e->strip_epoch << 12);
-}
 
 // nseq sequences (slots first_slot ...; idx = their sequence numbers or null) by S strips each
 constexpr int SOLO_CALLS = 1000;      // calls with one workgroup per fold after three lost calls in a row (see fallback_streak)
 static void launch_pf_strips(drna_engine* e, const PfArgs& a, int nseq, int S, int first_slot, const int* idx, hipStream_t st) {
   StripLink lk;
-  lk.flags = e->d_sflags + (size_t)first_slot * STRIP_MAXS * 32;
-  lk.base = next_strip_epoch(e);
+  lk.flags = e->sflags.d + (size_t)first_slot * STRIP_MAXS * 32;
+  lk.base = epoch_base(flags_next(e->sflags));
   lk.nseq = nseq; lk.S = S; lk.idx = idx; lk.pad = strip_pad(S); lk.fault = e->strip_fault;
   lk.dbg = e->d_sdbg ? e->d_sdbg + (size_t)first_slot * 8 : nullptr;
   const int groups = (nseq + 7) / 8;
   hipLaunchKernelGGL(pf_strip_kernel<1024>, dim3(groups * 8 * (S + strip_pad(S))), dim3(1024), 0, st, a, lk);
 }
 
-// MFE fold of nseq sequences by S strips each: per pseudoknot round one launch of the fill and one of the traceback
 // one pseudoknot round of nseq sequences (slots first_slot ...; idx = their sequence numbers, or null: sequences r0 ...)
 static void launch_mfe_strips_round(drna_engine* e, const MfeArgs& a, int nseq, int S, int first_slot, const int* idx, int r0,
                                     hipStream_t st, int round, hipEvent_t after_fill = nullptr) {
@@ -281,8 +281,8 @@ static void launch_mfe_strips_round(drna_engine* e, const MfeArgs& a, int nseq, 
   xr.rec = e->d_srec; xr.stride = e->srec_stride;
   const int groups = (nseq + 7) / 8;
   StripLink lk;
-  lk.flags = e->d_sflags + ((size_t)e->max_R + first_slot) * STRIP_MAXS * 32;
-  lk.base = next_strip_epoch(e);
+  lk.flags = e->sflags.d + ((size_t)e->max_R + first_slot) * STRIP_MAXS * 32;
+  lk.base = epoch_base(flags_next(e->sflags));
   lk.nseq = nseq; lk.S = S; lk.idx = idx; lk.r0 = r0; lk.pad = strip_pad(S); lk.fault = e->strip_fault;
   // blocked multiloop splits for the long folds (fold_mfe_strip.hpp, MKT_L).  Alone they win from four strips on (400 nt x 256:
   // 4.86 -> 4.48 ms); beside the partition function's strips only from five on (400 nt: both folds 9.31 -> 9.94 ms, 600 nt x 128:
@@ -387,7 +387,7 @@ extern "C" void drna_destroy(drna_engine* e) {
   void* bufs[] = {e->d_mfeT, e->d_pfT, e->d_plan, e->d_hp_len, e->d_bulge_len, e->d_int_len, e->d_hp_w, e->d_scale,
                   e->d_eMLb, e->d_ws_mfe, e->d_ws_pf, e->d_seqs, e->d_Epf, e->d_Emfe, e->d_ss, e->d_Ed, e->d_pt,
                   e->d_ws_out, e->d_edef, e->d_rg, e->d_rpt, e->d_rpt_off, e->d_F4, e->d_ws_kb, e->d_kbE, e->d_kbss,
-                  e->d_dflags, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->d_sflags, e->d_srec, e->d_sdbg, e->d_sclk, e->d_pflags};
+                  e->dflags.d, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->sflags.d, e->d_srec, e->d_sdbg, e->d_sclk, e->pflags.d};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_status) (void)hipHostFree(e->h_status);
@@ -421,7 +421,7 @@ extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!strcmp(name, "strip_fault")) { e->strip_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "mfe_fark_min_strips")) { e->mfe_fark_min_strips = value < 1 ? 1 : value; return DRNA_OK; }
   if (!strcmp(name, "mfe_split")) { e->mfe_split = value < 1 ? 1 : value > 8 ? 8 : value; return DRNA_OK; }
-  if (!strcmp(name, "debug_epoch")) { e->strip_epoch = value; e->dual_epoch = value; e->pfh_epoch = value; return DRNA_OK; }     // tests: jump near the reset point
+  if (!strcmp(name, "debug_epoch")) { e->sflags.epoch = e->dflags.epoch = e->pflags.epoch = value; return DRNA_OK; }     // tests: jump near the reset point
   e->err = std::string("drna_set_option: unknown option ") + name;
   return DRNA_ERR_ARG;
 }
@@ -456,7 +456,7 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "mc_threads_used")) { *value = 1; return DRNA_OK; }       // drna_mc_run's host work runs on the calling thread
   if (!strcmp(name, "workspace_slots")) { *value = e->ws_slots; return DRNA_OK; }
   if (!strcmp(name, "flag_resets")) { *value = e->flag_resets; return DRNA_OK; }
-  if (!strcmp(name, "debug_epoch")) { *value = std::max(e->pfh_epoch, std::max(e->strip_epoch, e->dual_epoch)); return DRNA_OK; }
+  if (!strcmp(name, "debug_epoch")) { *value = std::max(e->pflags.epoch, std::max(e->sflags.epoch, e->dflags.epoch)); return DRNA_OK; }
   return DRNA_ERR_ARG;
 }
 
@@ -569,15 +569,24 @@ static int redo_solo(drna_engine* e, F&& fold) {
   return rc;
 }
 
-// one batch that fits the workspaces; its sequences are the caller's r_base, r_base + 1, ...
-static int score_batch_impl(drna_engine* e, int R, int L, const char* d_seqs, uint32_t flags, double* d_Epf, int32_t* d_Emfe,
-                            char* d_mfe_ss, int32_t* d_Ed, int r_base) {
-  const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK),
-             want_pk = flags & DRNA_NEED_PK, want_ev = flags & DRNA_NEED_EVAL;
-  e->cur_with_pf = want_pf;
-  HIP_TRY(hipSetDevice(e->device));
-  const int ld = L + 2;
+static void reset_status(drna_engine* e) {
   for (int k = 0; k < 2 * e->max_R; k++) e->h_status[k] = ST_OK;
+}
+
+// Which kernels a uniform batch takes and how many workgroups each fold puts on the chip.  Decided once per call (a redone call
+// plans again, with the multi-workgroup paths off); the prepare, enqueue and drain steps and last_workgroups all read it.
+struct FoldPlan {
+  bool want_pf, want_mfe, want_pk, want_ev;
+  bool dual;                      // MFE fold by a main and a helper workgroup per sequence (fold_mfe_dual.hpp)
+  bool pf_help, ev_in_pf;         // partition function with a helper workgroup per sequence (pf_kfar_helper), which also evaluates E(targets)
+  bool fused;                     // both folds in ONE launch, 4 R workgroups resident side by side (fold_fused.hpp)
+  int pf_strips, mfe_strips;      // strips of columns per sequence, one workgroup each (fold_pf_strip.hpp); 0: not by strips
+  int mfe_wgs, pf_wgs;            // workgroups of each fold
+};
+static FoldPlan plan_uniform(drna_engine* e, int R, int L, uint32_t flags) {
+  FoldPlan p{};
+  p.want_pf = flags & DRNA_NEED_PF; p.want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK);
+  p.want_pk = flags & DRNA_NEED_PK; p.want_ev = flags & DRNA_NEED_EVAL;
   // small batches leave most CUs idle with one workgroup per fold (R = 64: 128 workgroups on 256 CUs): the MFE fold then
   // takes a main and a helper workgroup per sequence (fold_mfe_dual.hpp; the same split of the partition function did not
   // pay).  Needs 4 R <= CUs; larger batches keep the one-workgroup kernels, which saturate the chip by themselves
@@ -587,149 +596,159 @@ static int score_batch_impl(drna_engine* e, int R, int L, const char* d_seqs, ui
   // one XCD) at n = 120 without pseudoknot rounds (n = 130: 0.275 against 0.292 ms, n = 160: 0.336 against 0.383) and at n = 165
   // with them (their re-folds of masked sequences have little for the helper to do).
   const long long resident = (long long)e->cus * (e->dual || e->pf_helper ? pair_blocks_per_cu(e) : 1);   // workgroups the chip holds at once
-  const bool use_dual = e->dual && L <= MFE_FAST_NMAX && L > 2 * TURN + 2 && 4ll * R <= resident &&
-                        (L >= (want_pk ? 170 : 125) || e->dual_force);
-  if (use_dual) {
+  p.dual = e->dual && L <= MFE_FAST_NMAX && L > 2 * TURN + 2 && 4ll * R <= resident &&
+           (L >= (p.want_pk ? 170 : 125) || e->dual_force);
+  // longer sequences (and, as an option, short ones in small batches): the folds by strips of columns
+  p.pf_strips = p.want_pf ? strips_for(e, L, L + 2) : 0;
+  p.mfe_strips = p.want_mfe ? strips_for(e, L, L + 2) : 0;
+  p.mfe_wgs = p.want_mfe ? (p.dual ? 2 * R : p.mfe_strips ? R * p.mfe_strips : R) : 0;
+  // partition function of a small batch: a helper workgroup per sequence on a CU that would idle takes the far multiloop split
+  // points (the main workgroup's vector-memory path is what they saturate); needs room for 2 R workgroups beside the MFE fold's
+  p.pf_help = p.want_pf && e->pf_helper && !p.pf_strips && L <= PF_FAST_NMAX && L >= PF_HELPER_NMIN &&
+              2ll * R + p.mfe_wgs <= resident;
+  p.pf_wgs = p.want_pf ? (p.pf_strips ? R * p.pf_strips : p.pf_help ? 2 * R : R) : 0;
+  p.ev_in_pf = p.want_ev && p.pf_help;
+  p.fused = e->fused && p.dual && p.pf_help && p.want_mfe && p.want_pf && (!p.want_ev || p.ev_in_pf) && fused_grid_fits(e, R);
+  return p;
+}
+
+// what the planned kernels need before the first launch: their hand-over flags at a fresh epoch, the exchange rows of the
+// two-workgroup MFE fold (362 KB per sequence, so they grow with the batches seen and not to max_R) and the fused launch's clocks
+static int prepare_folds(drna_engine* e, const FoldPlan& p, int R) {
+  if (p.dual) {
+    { const int rc = flags_ready(e, e->dflags, (size_t)2 * R * 64); if (rc != DRNA_OK) return rc; }
     if (e->dual_cap < R) {
-      void* old[] = {e->d_dflags, e->d_xs, e->d_xa_mfe, e->d_xb_mfe};
-      for (void* b : old) if (b) (void)hipFree(b);
-      e->d_dflags = nullptr; e->d_xs = nullptr; e->d_xa_mfe = nullptr; e->d_xb_mfe = nullptr;
+      for (int32_t** b : {&e->d_xs, &e->d_xa_mfe, &e->d_xb_mfe}) { if (*b) (void)hipFree(*b); *b = nullptr; }
       e->dual_cap = 0;
       const size_t rows = (size_t)2 * (MFE_FAST_NMAX + 2) * XP;
-      HIP_TRY(hipMalloc((void**)&e->d_dflags, (size_t)2 * R * 64 * sizeof(int)));
-      HIP_TRY(hipMemset(e->d_dflags, 0, (size_t)2 * R * 64 * sizeof(int)));
-      HIP_TRY(hipDeviceSynchronize());    // the memset runs on the null stream, the kernels on non-blocking streams of their own
       HIP_TRY(hipMalloc((void**)&e->d_xs, (size_t)R * 256 * sizeof(int32_t)));
       HIP_TRY(hipMalloc((void**)&e->d_xa_mfe, (size_t)R * rows * sizeof(int32_t)));
       HIP_TRY(hipMalloc((void**)&e->d_xb_mfe, (size_t)R * rows * sizeof(int32_t)));
       e->dual_cap = R;
-      e->dual_epoch = 0;
     }
-    if (e->dual_epoch >= DUAL_EPOCH_RESET) {                       // same reasoning as in strip_flags(): 8192 flag values per epoch
-      HIP_TRY(hipMemset(e->d_dflags, 0, (size_t)2 * e->dual_cap * 64 * sizeof(int)));
-      HIP_TRY(hipDeviceSynchronize());
-      e->dual_epoch = 0;
-      e->flag_resets++;
-    }
-    e->dual_epoch = (int)((unsigned)e->dual_epoch + 1u);
+    flags_next(e->dflags);
   }
-  // longer sequences (and, as an option, short ones in small batches): the partition function by strips of columns, one
-  // workgroup each (fold_pf_strip.hpp)
-  const int pf_strips = want_pf ? strips_for(e, L, ld) : 0;
-  const int mfe_strips = want_mfe ? strips_for(e, L, ld) : 0;
-  e->last_wgs = 0;
-  // partition function of a small batch: a helper workgroup per sequence on a CU that would idle takes the far multiloop split
-  // points (the main workgroup's vector-memory path is what they saturate); needs room for 2 R workgroups beside the MFE fold's
-  const int mfe_wgs = want_mfe ? (use_dual ? 2 * R : mfe_strips ? R * mfe_strips : R) : 0;
-  const bool pf_help = want_pf && e->pf_helper && !pf_strips && L <= PF_FAST_NMAX && L >= PF_HELPER_NMIN &&
-                       2ll * R + mfe_wgs <= resident;
-  if (pf_help) {
-    if (e->pflags_cap < R) {
-      if (e->d_pflags) (void)hipFree(e->d_pflags);
-      e->d_pflags = nullptr; e->pflags_cap = 0;
-      HIP_TRY(hipMalloc((void**)&e->d_pflags, (size_t)R * 64 * sizeof(int)));
-      HIP_TRY(hipMemset(e->d_pflags, 0, (size_t)R * 64 * sizeof(int)));
-      HIP_TRY(hipDeviceSynchronize());
-      e->pflags_cap = R; e->pfh_epoch = 0;
-    }
-    if (e->pfh_epoch >= STRIP_EPOCH_RESET) {                       // see strip_flags(): 4096 flag values per epoch
-      HIP_TRY(hipMemset(e->d_pflags, 0, (size_t)e->pflags_cap * 64 * sizeof(int)));
-      HIP_TRY(hipDeviceSynchronize());
-      e->pfh_epoch = 0;
-      e->flag_resets++;
-    }
-    e->pfh_epoch++;
+  if (p.pf_help) {
+    { const int rc = flags_ready(e, e->pflags, (size_t)R * 64); if (rc != DRNA_OK) return rc; }
+    flags_next(e->pflags);
   }
-  if (pf_strips || mfe_strips) { const int rc = strip_flags(e, mfe_strips != 0); if (rc != DRNA_OK) return rc; }
-  // every stream of the engine is idle here (each call drains them before it returns), so nothing has to be fenced at the
-  // start; the two folds run side by side on disjoint CUs and a launch costs ~10 us, so the one that took longer in the
-  // previous call is enqueued first
-  // with a helper workgroup per sequence, E(targets) is evaluated by the helpers inside the partition-function launch
-  const bool ev_in_pf = want_ev && pf_help;
-  const EvalArgs ev = want_ev ? eval_args(e, d_seqs, L, d_Ed) : EvalArgs{};
-  MfeArgs ma = mfe_args(e, d_seqs, L, ld, want_pk ? 3 : 0, d_Emfe, d_mfe_ss);
-  PfArgs pa = pf_args(e, d_seqs, L, ld, d_Epf);
-  if (pf_help) { pa.helper = e->helper_fault ? 2 : 1; pa.hflags = e->d_pflags; pa.hbase = (int)((unsigned)e->pfh_epoch << 12); }
-  DualLink lk;
-  lk.flagA = e->d_dflags; lk.flagB = e->d_dflags;
-  lk.xs = e->d_xs; lk.xa = e->d_xa_mfe; lk.xb = e->d_xb_mfe; lk.epoch = e->dual_epoch;
+  if (p.pf_strips || p.mfe_strips) { const int rc = strip_flags(e, p.mfe_strips != 0); if (rc != DRNA_OK) return rc; }
+  if (p.fused && e->clk_cap < fused_grid(R)) {
+    if (e->h_clk) (void)hipHostFree(e->h_clk);
+    e->h_clk = nullptr; e->clk_cap = 0;
+    HIP_TRY(hipHostMalloc((void**)&e->h_clk, (size_t)2 * fused_grid(R) * sizeof(long long), hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer((void**)&e->d_clk, e->h_clk, 0));
+    e->clk_cap = fused_grid(R);
+  }
+  return DRNA_OK;
+}
+
+// one uniform batch on its way through the streams: plan, kernel arguments, and what the enqueue step leaves for the drain step
+struct FoldCall {
+  int R, L;
+  FoldPlan p;
+  MfeArgs ma; PfArgs pa; EvalArgs ev; DualLink lk;
+  bool mfe_first;                 // the MFE fold is enqueued before the partition function
+  hipStream_t s_ev;               // stream of the evaluation kernel
+  bool pf_gated;                  // the partition function's launch waits for ev_gate (enqueue_mfe decides, enqueue_pf obeys)
+};
+
+static int enqueue_pf(drna_engine* e, const FoldCall& c) {
+  const FoldPlan& p = c.p; const int R = c.R;
+  if (c.pf_gated) HIP_TRY(hipStreamWaitEvent(e->s_pf, e->ev_gate, 0));
+  HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
+  if (p.pf_strips) launch_pf_strips(e, c.pa, R, p.pf_strips, 0, nullptr, e->s_pf);
+  else if (p.pf_help)
+    hipLaunchKernelGGL((pf_lds_kernel<1024, false>), dim3(pair_grid(R)), dim3(1024), 0, e->s_pf, c.pa, p.ev_in_pf ? c.ev : EvalArgs{}, R);
+  else if (c.L <= PF_FAST_NMAX)
+    hipLaunchKernelGGL(pf_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, c.pa, EvalArgs{}, R);
+  else hipLaunchKernelGGL(pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, c.pa);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_p1, e->s_pf));
+  return DRNA_OK;
+}
+static int enqueue_mfe(drna_engine* e, FoldCall& c) {
+  const FoldPlan& p = c.p; const MfeArgs& ma = c.ma; const int R = c.R;
   // An MFE fold with pseudoknot rounds on the strip path is a chain of launches whose later links are sparse (only sequences that
   // found a pair fold again), the partition function is one dense launch.  On a chip the first fill already fills (R x strips >=
   // CUs) the partition function is therefore started when the last-but-one round has been queued: it runs beside the sparse rounds
   // instead of halving the CUs of the dense first ones (400 nt x 128: 10.6 -> 9.0 ms, x 256: 19.3 -> 16.5 ms; on a chip with idle CUs
   // it would only delay the partition function: 400 nt x 32 5.4 -> 5.7 ms).  DRNA_PF_GATE=-1 switches it off, k >= 0 forces round k.
   static const int pf_gate_env = getenv("DRNA_PF_GATE") ? atoi(getenv("DRNA_PF_GATE")) : -2;
-  int pf_gate_round = -1;
   static const int pf_gate_part = getenv("DRNA_PF_GATE_PART") ? atoi(getenv("DRNA_PF_GATE_PART")) : 0;
-  bool pf_gated = false;
-  auto enqueue_pf = [&]() -> int {
-    if (pf_gated) HIP_TRY(hipStreamWaitEvent(e->s_pf, e->ev_gate, 0));
-    HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
-    e->last_wgs += pf_strips ? R * pf_strips : pf_help ? 2 * R : R;
-    if (pf_strips) launch_pf_strips(e, pa, R, pf_strips, 0, nullptr, e->s_pf);
-    else if (pf_help)
-      hipLaunchKernelGGL((pf_lds_kernel<1024, false>), dim3(pair_grid(R)), dim3(1024), 0, e->s_pf, pa, ev_in_pf ? ev : EvalArgs{}, R);
-    else if (L <= PF_FAST_NMAX)
-      hipLaunchKernelGGL(pf_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, pa, EvalArgs{}, R);
-    else hipLaunchKernelGGL(pf_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, pa);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e->ev_p1, e->s_pf));
-    return DRNA_OK;
-  };
-  auto enqueue_mfe = [&]() -> int {
-    HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-    e->last_wgs += use_dual ? 2 * R : mfe_strips ? R * mfe_strips : R;
-    if (use_dual) hipLaunchKernelGGL(mfe_dual_kernel<1024>, dim3(pair_grid(R)), dim3(1024), 0, e->s_mfe, ma, lk, R);
-    else if (mfe_strips && ma.pk_rounds > 0 && R >= 16 * e->mfe_split && e->mfe_split > 1) {
-      // every round is a fill launch and a traceback launch (one wave per sequence, ~0.2 ms with the chip idle): the batch goes
-      // in parts on two streams, so that one part's traceback runs under another part's fill
-      const int np = e->mfe_split, per = ((R + np - 1) / np + 7) / 8 * 8;
-      pf_gate_round = pf_gate_env >= -1 ? pf_gate_env : (pf_strips && R * mfe_strips >= e->cus && ma.pk_rounds >= 2) ? ma.pk_rounds - 1 : -1;
-      for (int round = 0; round <= ma.pk_rounds; round++) {
-        for (int part = 0, r0 = 0; r0 < R; part++, r0 += per) {
-          const bool gate_here = round == pf_gate_round && want_pf && part == pf_gate_part;
-          launch_mfe_strips_round(e, ma, std::min(per, R - r0), mfe_strips, r0, nullptr, r0, (part & 1) ? e->s_eval : e->s_mfe, round,
-                                  gate_here ? e->ev_gate : nullptr);
-          if (gate_here) pf_gated = true;
-        }
+  HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
+  if (p.dual) hipLaunchKernelGGL(mfe_dual_kernel<1024>, dim3(pair_grid(R)), dim3(1024), 0, e->s_mfe, ma, c.lk, R);
+  else if (p.mfe_strips && ma.pk_rounds > 0 && R >= 16 * e->mfe_split && e->mfe_split > 1) {
+    // every round is a fill launch and a traceback launch (one wave per sequence, ~0.2 ms with the chip idle): the batch goes
+    // in parts on two streams, so that one part's traceback runs under another part's fill
+    const int np = e->mfe_split, per = ((R + np - 1) / np + 7) / 8 * 8;
+    const int pf_gate_round = pf_gate_env >= -1 ? pf_gate_env : (p.pf_strips && p.mfe_wgs >= e->cus && ma.pk_rounds >= 2) ? ma.pk_rounds - 1 : -1;
+    for (int round = 0; round <= ma.pk_rounds; round++) {
+      for (int part = 0, r0 = 0; r0 < R; part++, r0 += per) {
+        const bool gate_here = round == pf_gate_round && p.want_pf && part == pf_gate_part;
+        launch_mfe_strips_round(e, ma, std::min(per, R - r0), p.mfe_strips, r0, nullptr, r0, (part & 1) ? e->s_eval : e->s_mfe, round,
+                                gate_here ? e->ev_gate : nullptr);
+        if (gate_here) c.pf_gated = true;
       }
-      HIP_TRY(hipEventRecord(e->ev_mfe2, e->s_eval));
-      HIP_TRY(hipStreamWaitEvent(e->s_mfe, e->ev_mfe2, 0));
-    } else if (mfe_strips) launch_mfe_strips(e, ma, R, mfe_strips, 0, nullptr, e->s_mfe);
-    else if (L <= MFE_FAST_NMAX) hipLaunchKernelGGL(mfe_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, ma);
-    else hipLaunchKernelGGL(mfe_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, ma);
+    }
+    HIP_TRY(hipEventRecord(e->ev_mfe2, e->s_eval));
+    HIP_TRY(hipStreamWaitEvent(e->s_mfe, e->ev_mfe2, 0));
+  } else if (p.mfe_strips) launch_mfe_strips(e, ma, R, p.mfe_strips, 0, nullptr, e->s_mfe);
+  else if (c.L <= MFE_FAST_NMAX) hipLaunchKernelGGL(mfe_lds_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, ma);
+  else hipLaunchKernelGGL(mfe_kernel<1024>, dim3(R), dim3(1024), 0, e->s_mfe, ma);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
+  return DRNA_OK;
+}
+static int enqueue_eval(drna_engine* e, const FoldCall& c) {
+  if (c.p.ev_in_pf) return DRNA_OK;
+  HIP_TRY(hipEventRecord(e->ev_e0, c.s_ev));
+  hipLaunchKernelGGL(eval_kernel, dim3(c.R * e->n_targets), dim3(WAVE), 0, c.s_ev, c.ev);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_e1, c.s_ev));
+  return DRNA_OK;
+}
+// Every stream of the engine is idle here (each call drains them before it returns), so nothing has to be fenced at the start.
+// Small batches (the headline shape) take both folds in ONE launch; otherwise the two folds run side by side on disjoint CUs
+// and a launch costs ~10 us, so the one that took longer in the previous call is enqueued first
+static int enqueue_folds(drna_engine* e, FoldCall& c) {
+  const FoldPlan& p = c.p;
+  e->last_fused = p.fused;
+  e->last_wgs = p.mfe_wgs + p.pf_wgs;
+  if (p.fused) {
+    HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
+    hipLaunchKernelGGL(score_fused_kernel<1024>, dim3(fused_grid(c.R)), dim3(1024), 0, e->s_mfe, c.ma, c.lk, c.pa, c.ev, c.R, e->d_clk);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
     return DRNA_OK;
-  };
-  // ---- small batches (the headline shape): both folds in ONE launch, 4 R workgroups resident side by side (fold_fused.hpp)
-  e->last_fused = false;
-  const bool use_fused = e->fused && use_dual && pf_help && want_mfe && want_pf && (!want_ev || ev_in_pf) && fused_grid_fits(e, R);
-  if (use_fused) {
-    const int grid = fused_grid(R);
-    if (e->clk_cap < grid) {
-      if (e->h_clk) (void)hipHostFree(e->h_clk);
-      e->h_clk = nullptr; e->clk_cap = 0;
-      HIP_TRY(hipHostMalloc((void**)&e->h_clk, (size_t)2 * grid * sizeof(long long), hipHostMallocMapped));
-      HIP_TRY(hipHostGetDevicePointer((void**)&e->d_clk, e->h_clk, 0));
-      e->clk_cap = grid;
-    }
-    HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-    hipLaunchKernelGGL(score_fused_kernel<1024>, dim3(grid), dim3(1024), 0, e->s_mfe, ma, lk, pa, ev, R, e->d_clk);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
-    e->last_wgs = 4 * R;
-    e->last_fused = true;
+  }
+  c.mfe_first = p.want_mfe && (!p.want_pf || e->timing[0] > e->timing[1]);
+  // the evaluation kernel (~20 us) rides in FRONT of the shorter fold on that fold's stream: one stream less to drain at the end
+  c.s_ev = !(p.want_mfe && p.want_pf) ? e->s_eval : c.mfe_first ? e->s_pf : e->s_mfe;
+  if (c.mfe_first) { const int rc = enqueue_mfe(e, c); if (rc != DRNA_OK) return rc; }
+  if (p.want_ev && c.s_ev == e->s_pf) { const int rc = enqueue_eval(e, c); if (rc != DRNA_OK) return rc; }
+  if (p.want_pf) { const int rc = enqueue_pf(e, c); if (rc != DRNA_OK) return rc; }
+  if (p.want_ev && c.s_ev == e->s_mfe) { const int rc = enqueue_eval(e, c); if (rc != DRNA_OK) return rc; }
+  if (p.want_mfe && !c.mfe_first) { const int rc = enqueue_mfe(e, c); if (rc != DRNA_OK) return rc; }
+  if (p.want_ev && c.s_ev == e->s_eval) { const int rc = enqueue_eval(e, c); if (rc != DRNA_OK) return rc; }
+  return DRNA_OK;
+}
+
+// wait for the kernels of the call and fill e->timing (MFE, partition function, evaluation, total; ms)
+static int drain_folds(drna_engine* e, const FoldCall& c) {
+  const FoldPlan& p = c.p;
+  if (p.fused) {
     HIP_TRY(hipStreamSynchronize(e->s_mfe));
     float tot = 0.f;
     HIP_TRY(hipEventElapsedTime(&tot, e->ev_m0, e->ev_m1));
     // per-fold times from the blocks' own clocks (100 MHz): first start of any block to the last end of the fold's blocks
+    const int grid = fused_grid(c.R);
     long long t0 = 0, end_mfe = 0, end_pf = 0;
     bool first = true;
     for (int b = 0; b < grid; b++) {
       int r, role;
       fused_block_role(b, r, role, grid);
-      if (r >= R) continue;
+      if (r >= c.R) continue;
       const long long s0 = e->h_clk[2 * b], s1 = e->h_clk[2 * b + 1];
       if (first || s0 < t0) t0 = s0;
       first = false;
@@ -737,51 +756,54 @@ static int score_batch_impl(drna_engine* e, int R, int L, const char* d_seqs, ui
     }
     e->timing[0] = (float)((end_mfe - t0) * 1e-5); e->timing[1] = (float)((end_pf - t0) * 1e-5);
     e->timing[2] = 0.f; e->timing[3] = tot;
-  } else {
-    const bool mfe_first = want_mfe && (!want_pf || e->timing[0] > e->timing[1]);
-    // the evaluation kernel (~20 us) rides in FRONT of the shorter fold on that fold's stream: one stream less to drain at the end
-    hipStream_t s_ev = e->s_eval;
-    if (want_ev && want_mfe && want_pf) s_ev = mfe_first ? e->s_pf : e->s_mfe;
-    auto enqueue_eval = [&]() -> int {
-      if (ev_in_pf) return DRNA_OK;
-      HIP_TRY(hipEventRecord(e->ev_e0, s_ev));
-      hipLaunchKernelGGL(eval_kernel, dim3(R * e->n_targets), dim3(WAVE), 0, s_ev, ev);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(e->ev_e1, s_ev));
-      return DRNA_OK;
-    };
-    if (mfe_first) { const int rc = enqueue_mfe(); if (rc != DRNA_OK) return rc; }
-    if (want_ev && s_ev == e->s_pf) { const int rc = enqueue_eval(); if (rc != DRNA_OK) return rc; }
-    if (want_pf) { const int rc = enqueue_pf(); if (rc != DRNA_OK) return rc; }
-    if (want_ev && s_ev == e->s_mfe) { const int rc = enqueue_eval(); if (rc != DRNA_OK) return rc; }
-    if (want_mfe && !mfe_first) { const int rc = enqueue_mfe(); if (rc != DRNA_OK) return rc; }
-    if (want_ev && s_ev == e->s_eval) { const int rc = enqueue_eval(); if (rc != DRNA_OK) return rc; }
-    // join on the host: the streams are drained one after the other (a device-side join -- stream-wait-event packets
-    // plus an end marker -- costs ~15 us after the last kernel); "total" = first start event to the latest end event
-    if (want_ev && !ev_in_pf && s_ev == e->s_eval) HIP_TRY(hipStreamSynchronize(e->s_eval));
-    if (mfe_first && want_pf) HIP_TRY(hipStreamSynchronize(e->s_pf));
-    if (want_mfe) HIP_TRY(hipStreamSynchronize(e->s_mfe));
-    if (!mfe_first && want_pf) HIP_TRY(hipStreamSynchronize(e->s_pf));
-    e->timing[0] = e->timing[1] = e->timing[2] = 0.f;
-    if (want_mfe) HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
-    if (want_pf) HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
-    if (want_ev && !ev_in_pf) HIP_TRY(hipEventElapsedTime(&e->timing[2], e->ev_e0, e->ev_e1));
-    hipEvent_t first = mfe_first ? e->ev_m0 : want_pf ? e->ev_p0 : e->ev_e0;
-    float t = 0.f, tot = 0.f;
-    if (want_mfe) { HIP_TRY(hipEventElapsedTime(&t, first, e->ev_m1)); tot = t > tot ? t : tot; }
-    if (want_pf) { HIP_TRY(hipEventElapsedTime(&t, first, e->ev_p1)); tot = t > tot ? t : tot; }
-    if (want_ev && !ev_in_pf) { HIP_TRY(hipEventElapsedTime(&t, first, e->ev_e1)); tot = t > tot ? t : tot; }
-    e->timing[3] = tot;
+    return DRNA_OK;
   }
+  // join on the host: the streams are drained one after the other (a device-side join -- stream-wait-event packets
+  // plus an end marker -- costs ~15 us after the last kernel); "total" = first start event to the latest end event
+  const bool ev_own = p.want_ev && !p.ev_in_pf;          // the evaluation ran as a kernel of its own
+  if (ev_own && c.s_ev == e->s_eval) HIP_TRY(hipStreamSynchronize(e->s_eval));
+  if (c.mfe_first && p.want_pf) HIP_TRY(hipStreamSynchronize(e->s_pf));
+  if (p.want_mfe) HIP_TRY(hipStreamSynchronize(e->s_mfe));
+  if (!c.mfe_first && p.want_pf) HIP_TRY(hipStreamSynchronize(e->s_pf));
+  e->timing[0] = e->timing[1] = e->timing[2] = e->timing[3] = 0.f;
+  if (p.want_mfe) HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
+  if (p.want_pf) HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
+  if (ev_own) HIP_TRY(hipEventElapsedTime(&e->timing[2], e->ev_e0, e->ev_e1));
+  hipEvent_t first = c.mfe_first ? e->ev_m0 : p.want_pf ? e->ev_p0 : e->ev_e0;
+  float t = 0.f;
+  if (p.want_mfe) { HIP_TRY(hipEventElapsedTime(&t, first, e->ev_m1)); e->timing[3] = std::max(e->timing[3], t); }
+  if (p.want_pf) { HIP_TRY(hipEventElapsedTime(&t, first, e->ev_p1)); e->timing[3] = std::max(e->timing[3], t); }
+  if (ev_own) { HIP_TRY(hipEventElapsedTime(&t, first, e->ev_e1)); e->timing[3] = std::max(e->timing[3], t); }
+  return DRNA_OK;
+}
+
+// one batch that fits the workspaces; its sequences are the caller's r_base, r_base + 1, ...
+static int score_batch_impl(drna_engine* e, int R, int L, const char* d_seqs, uint32_t flags, double* d_Epf, int32_t* d_Emfe,
+                            char* d_mfe_ss, int32_t* d_Ed, int r_base) {
+  HIP_TRY(hipSetDevice(e->device));
+  // 1. plan (here, inside the call: fold_solo has switched the multi-workgroup paths off before a redone call gets here)
+  FoldCall c{R, L, plan_uniform(e, R, L, flags)};
+  const FoldPlan& p = c.p;
+  // 2. prepare
+  { const int rc = prepare_folds(e, p, R); if (rc != DRNA_OK) return rc; }
+  reset_status(e);
+  e->cur_with_pf = p.want_pf;
+  c.ev = p.want_ev ? eval_args(e, d_seqs, L, d_Ed) : EvalArgs{};
+  c.ma = mfe_args(e, d_seqs, L, L + 2, p.want_pk ? 3 : 0, d_Emfe, d_mfe_ss);
+  c.pa = pf_args(e, d_seqs, L, L + 2, d_Epf);
+  if (p.pf_help) { c.pa.helper = e->helper_fault ? 2 : 1; c.pa.hflags = e->pflags.d; c.pa.hbase = epoch_base(e->pflags.epoch); }
+  c.lk.flagA = e->dflags.d; c.lk.flagB = e->dflags.d;
+  c.lk.xs = e->d_xs; c.lk.xa = e->d_xa_mfe; c.lk.xb = e->d_xb_mfe; c.lk.epoch = e->dflags.epoch;
+  // 3. enqueue, 4. drain and time
+  { const int rc = enqueue_folds(e, c); if (rc != DRNA_OK) return rc; }
+  { const int rc = drain_folds(e, c); if (rc != DRNA_OK) return rc; }
+  // 5. status; a lost attempt (up to the wait budget) is not a kernel time and stays out of the sums
+  bool lost = false;
+  const int rc = fold_status(e, R, p.want_mfe, p.want_pf, nullptr, r_base, "traceback could not reproduce a table value", &lost);
+  if (lost && !e->in_fallback)
+    return redo_solo(e, [&] { return score_batch_impl(e, R, L, d_seqs, flags, d_Epf, d_Emfe, d_mfe_ss, d_Ed, r_base); });
   for (int k = 0; k < 4; k++) e->timing_sum[k] += e->timing[k];
   e->timing_sum[4] += 1.0;
-  bool lost = false;
-  const int rc = fold_status(e, R, want_mfe, want_pf, nullptr, r_base, "traceback could not reproduce a table value", &lost);
-  if (lost && !e->in_fallback) {
-    for (int k = 0; k < 4; k++) e->timing_sum[k] -= e->timing[k];        // the lost attempt (up to the wait budget) is not a kernel time
-    e->timing_sum[4] -= 1.0;
-    return redo_solo(e, [&] { return score_batch_impl(e, R, L, d_seqs, flags, d_Epf, d_Emfe, d_mfe_ss, d_Ed, r_base); });
-  }
   if (lost && e->d_sdbg) {
     std::vector<int> dbg((size_t)2 * e->max_R * 8);
     (void)hipMemcpy(dbg.data(), e->d_sdbg, dbg.size() * sizeof(int), hipMemcpyDeviceToHost);
@@ -793,16 +815,21 @@ static int score_batch_impl(drna_engine* e, int R, int L, const char* d_seqs, ui
   return rc;
 }
 
+// argument check of the two uniform entry points (host and device buffers)
+static int score_check(drna_engine* e, int R, int L, const char* seqs, uint32_t flags, const double* Epf, const int32_t* Emfe,
+                       const char* mfe_ss, const int32_t* Ed) {
+  const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK), want_ev = flags & DRNA_NEED_EVAL;
+  if (R >= 1 && R <= e->max_R && L >= 1 && L <= e->max_L && seqs && (!want_pf || Epf) && (!want_mfe || (Emfe && mfe_ss)) &&
+      (!want_ev || Ed)) return DRNA_OK;
+  e->err = "drna_score_batch: bad argument (R, L within the engine's limits; output pointers for every requested flag)";
+  return DRNA_ERR_ARG;
+}
+
 extern "C" int drna_score_batch_device(drna_engine* e, int R, int L, const char* d_seqs, uint32_t flags, double* d_Epf,
                                        int32_t* d_Emfe, char* d_mfe_ss, int32_t* d_Ed) {
   if (!e) return DRNA_ERR_ARG;
-  const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK), want_ev = flags & DRNA_NEED_EVAL;
-  if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || !d_seqs || (want_pf && !d_Epf) ||
-      (want_mfe && (!d_Emfe || !d_mfe_ss)) || (want_ev && !d_Ed)) {
-    e->err = "drna_score_batch: bad argument (R, L within the engine's limits; output pointers for every requested flag)";
-    return DRNA_ERR_ARG;
-  }
-  if (want_ev && (e->n_targets < 1 || e->L_targets != L)) {
+  { const int rc = score_check(e, R, L, d_seqs, flags, d_Epf, d_Emfe, d_mfe_ss, d_Ed); if (rc != DRNA_OK) return rc; }
+  if ((flags & DRNA_NEED_EVAL) && (e->n_targets < 1 || e->L_targets != L)) {
     e->err = "drna_score_batch: DRNA_NEED_EVAL needs drna_set_targets() with the same L";
     return DRNA_ERR_ARG;
   }
@@ -845,11 +872,7 @@ extern "C" int drna_score_batch(drna_engine* e, int R, int L, const char* seqs, 
   if (!e) return DRNA_ERR_ARG;
   const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK),
              want_ev = flags & DRNA_NEED_EVAL;
-  if (R < 1 || R > e->max_R || L < 1 || L > e->max_L || !seqs || (want_pf && !Epf) || (want_mfe && (!Emfe || !mfe_ss)) ||
-      (want_ev && !Ed)) {
-    e->err = "drna_score_batch: bad argument (R, L within the engine's limits; output pointers for every requested flag)";
-    return DRNA_ERR_ARG;
-  }
+  { const int rc = score_check(e, R, L, seqs, flags, Epf, Emfe, mfe_ss, Ed); if (rc != DRNA_OK) return rc; }
   HIP_TRY(hipSetDevice(e->device));
   const size_t ned = (size_t)R * (e->n_targets > 0 ? e->n_targets : 1);
   if (want_ev) { const int rc = mapped_Ed(e); if (rc != DRNA_OK) return rc; }
@@ -902,9 +925,6 @@ static int fits_workspace(drna_engine* e, const char* who, int R) {
   if (R <= e->ws_slots) return DRNA_OK;
   e->err = std::string(who) + ": batch larger than the workspace (raise DRNA_WS_GB or split the batch)";
   return DRNA_ERR_ARG;
-}
-static void reset_status(drna_engine* e) {
-  for (int k = 0; k < 2 * e->max_R; k++) e->h_status[k] = ST_OK;
 }
 
 // ---------------------------------------------------------------- ensemble defect (inside + outside recursion), one and two strands
@@ -1074,6 +1094,40 @@ extern "C" int drna_set_targets_ragged(drna_engine* e, int n_targets, const int3
   return DRNA_OK;
 }
 
+// One fold of a ragged batch of R sequences sorted longest first (lengths h[q]), in chunks of ws_slots consecutive positions q:
+// per chunk the strip kernels take idxC (one launch per number of strips, most strips first), the general kernel idxD, the LDS-
+// resident kernel idxA.  set_chunk(c0) points the fold's arguments at the chunk's workspace; a launch gets the number of its
+// sequences and their index list on the device (a strip launch also the number of strips and the first flag slot).
+template <class SetChunk, class Strips, class General, class Lds>
+static void ragged_fold(drna_engine* e, int R, const int* h, const int* idxA, int nA, const int* idxC, int nC, const int* idxD, int nD,
+                        SetChunk&& set_chunk, Strips&& launch_strips, General&& launch_general, Lds&& launch_lds) {
+  const int ld = e->max_L + 2;
+  // first entry of an index list (ascending q) that is not below q: the list's part in the chunk [c0, c1) is [lo(c0), lo(c1))
+  auto lo = [](const int* idx, int cnt, int q) { return (int)(std::lower_bound(idx, idx + cnt, q) - idx); };
+  for (int c0 = 0; c0 < R; c0 += e->ws_slots) {
+    const int c1 = std::min(R, c0 + e->ws_slots);
+    set_chunk(c0);
+    for (int k = lo(idxC, nC, c0), end = lo(idxC, nC, c1); k < end;) {
+      const int S = strips_for(e, h[idxC[k]], ld);
+      int k2 = k;
+      while (k2 < end && strips_for(e, h[idxC[k2]], ld) == S) k2++;
+      launch_strips(k2 - k, S, k, e->d_rg + (size_t)5 * R + k);
+      k = k2;
+    }
+    const int fD = lo(idxD, nD, c0), mD = lo(idxD, nD, c1) - fD, fA = lo(idxA, nA, c0), mA = lo(idxA, nA, c1) - fA;
+    if (mD) launch_general(mD, e->d_rg + (size_t)6 * R + fD);
+    if (mA) launch_lds(mA, e->d_rg + (size_t)3 * R + fA);
+  }
+}
+// R results of the sorted order back from the device into the caller's order
+template <class T>
+static int scatter_back(drna_engine* e, const T* d_src, const std::vector<int>& order, T* out) {
+  std::vector<T> t(order.size());
+  HIP_TRY(hipMemcpy(t.data(), d_src, t.size() * sizeof(T), hipMemcpyDeviceToHost));
+  for (size_t q = 0; q < t.size(); q++) out[order[q]] = t[q];
+  return DRNA_OK;
+}
+
 extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, const char* seqs, const int32_t* target_of,
                                  uint32_t flags, double* Epf, int32_t* Emfe, char* mfe_ss, int32_t* Ed) {
   if (!e) return DRNA_ERR_ARG;
@@ -1142,19 +1196,11 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
   if (!e->d_rg) HIP_TRY(hipMalloc((void**)&e->d_rg, (size_t)7 * e->max_R * sizeof(int)));
   HIP_TRY(hipMemcpy(e->d_rg, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->d_seqs, sorted_seqs.data(), total, hipMemcpyHostToDevice));
-  if (want_ev && R > 0) {
-    if (!e->d_Ed) HIP_TRY(hipMalloc((void**)&e->d_Ed, (size_t)e->max_R * std::max(1, e->n_targets) * sizeof(int32_t)));
-  }
-  for (int k = 0; k < 2 * e->max_R; k++) e->h_status[k] = ST_OK;
+  if (want_ev && !e->d_Ed) HIP_TRY(hipMalloc((void**)&e->d_Ed, (size_t)e->max_R * std::max(1, e->n_targets) * sizeof(int32_t)));
+  reset_status(e);
   if ((want_pf || want_mfe) && nC) { const int rc = strip_flags(e, want_mfe); if (rc != DRNA_OK) return rc; }
   Ragged rg;
   rg.len = e->d_rg; rg.off = e->d_rg + R;
-  // the part of an index list (ascending q) that falls into the chunk [c0, c1)
-  auto part = [&](const int* idx, int cnt, int c0, int c1, int& first, int& num) {
-    first = (int)(std::lower_bound(idx, idx + cnt, c0) - idx);
-    num = (int)(std::lower_bound(idx, idx + cnt, c1) - idx) - first;
-  };
-  const int slots = e->ws_slots;
   HIP_TRY(hipEventRecord(e->ev_start, e->s_mfe));
   HIP_TRY(hipStreamWaitEvent(e->s_pf, e->ev_start, 0));
   HIP_TRY(hipStreamWaitEvent(e->s_eval, e->ev_start, 0));
@@ -1162,30 +1208,11 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
     MfeArgs a = mfe_args(e, e->d_seqs, 0, ld, want_pk ? 3 : 0, e->d_Emfe, e->d_ss);
     a.rg = rg;
     HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-    for (int c0 = 0; c0 < R; c0 += slots) {
-      const int c1 = std::min(R, c0 + slots);
-      a.ws = e->d_ws_mfe - (long long)c0 * a.ws_stride;           // slot of sequence q: q - c0
-      int f, m;
-      part(idxC, nC, c0, c1, f, m);
-      a.rg.idx = nullptr;
-      for (int k = f; k < f + m;) {                 // the long sequences first: strip kernels, one launch per number of strips
-        const int S = strips_for(e, h[idxC[k]], ld);
-        int k2 = k;
-        while (k2 < f + m && strips_for(e, h[idxC[k2]], ld) == S) k2++;
-        launch_mfe_strips(e, a, k2 - k, S, k, e->d_rg + (size_t)5 * R + k, e->s_mfe);
-        k = k2;
-      }
-      part(idxD, nD, c0, c1, f, m);
-      if (m) {
-        a.rg.idx = e->d_rg + (size_t)6 * R + f;
-        hipLaunchKernelGGL(mfe_kernel<1024>, dim3(m), dim3(1024), 0, e->s_mfe, a);
-      }
-      part(idxA, nA, c0, c1, f, m);
-      if (m) {
-        a.rg.idx = e->d_rg + (size_t)3 * R + f;
-        hipLaunchKernelGGL(mfe_lds_kernel<1024>, dim3(m), dim3(1024), 0, e->s_mfe, a);
-      }
-    }
+    ragged_fold(e, R, h.data(), idxA, nA, idxC, nC, idxD, nD,
+                [&](int c0) { a.ws = e->d_ws_mfe - (long long)c0 * a.ws_stride; a.rg.idx = nullptr; },
+                [&](int n, int S, int k, const int* idx) { launch_mfe_strips(e, a, n, S, k, idx, e->s_mfe); },
+                [&](int n, const int* idx) { a.rg.idx = idx; hipLaunchKernelGGL(mfe_kernel<1024>, dim3(n), dim3(1024), 0, e->s_mfe, a); },
+                [&](int n, const int* idx) { a.rg.idx = idx; hipLaunchKernelGGL(mfe_lds_kernel<1024>, dim3(n), dim3(1024), 0, e->s_mfe, a); });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
   }
@@ -1193,30 +1220,11 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
     PfArgs a = pf_args(e, e->d_seqs, 0, ld, e->d_Epf);
     a.rg = rg;
     HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
-    for (int c0 = 0; c0 < R; c0 += slots) {
-      const int c1 = std::min(R, c0 + slots);
-      a.ws = e->d_ws_pf - (long long)c0 * a.ws_stride;
-      int f, m;
-      part(idxC, nC, c0, c1, f, m);
-      a.rg.idx = nullptr;
-      for (int k = f; k < f + m;) {                 // the strip kernel: one launch per number of strips, most strips first
-        const int S = strips_for(e, h[idxC[k]], ld);
-        int k2 = k;
-        while (k2 < f + m && strips_for(e, h[idxC[k2]], ld) == S) k2++;
-        launch_pf_strips(e, a, k2 - k, S, k, e->d_rg + (size_t)5 * R + k, e->s_pf);
-        k = k2;
-      }
-      part(idxD, nD, c0, c1, f, m);
-      if (m) {
-        a.rg.idx = e->d_rg + (size_t)6 * R + f;
-        hipLaunchKernelGGL(pf_kernel<1024>, dim3(m), dim3(1024), 0, e->s_pf, a);
-      }
-      part(idxA, nA, c0, c1, f, m);
-      if (m) {
-        a.rg.idx = e->d_rg + (size_t)3 * R + f;
-        hipLaunchKernelGGL(pf_lds_kernel<1024>, dim3(m), dim3(1024), 0, e->s_pf, a, EvalArgs{}, m);
-      }
-    }
+    ragged_fold(e, R, h.data(), idxA, nA, idxC, nC, idxD, nD,
+                [&](int c0) { a.ws = e->d_ws_pf - (long long)c0 * a.ws_stride; a.rg.idx = nullptr; },
+                [&](int n, int S, int k, const int* idx) { launch_pf_strips(e, a, n, S, k, idx, e->s_pf); },
+                [&](int n, const int* idx) { a.rg.idx = idx; hipLaunchKernelGGL(pf_kernel<1024>, dim3(n), dim3(1024), 0, e->s_pf, a); },
+                [&](int n, const int* idx) { a.rg.idx = idx; hipLaunchKernelGGL(pf_lds_kernel<1024>, dim3(n), dim3(1024), 0, e->s_pf, a, EvalArgs{}, n); });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_p1, e->s_pf));
     HIP_TRY(hipStreamWaitEvent(e->s_mfe, e->ev_p1, 0));
@@ -1238,31 +1246,19 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
   if (want_pf) HIP_TRY(hipEventElapsedTime(&e->timing[1], e->ev_p0, e->ev_p1));
   if (want_ev) HIP_TRY(hipEventElapsedTime(&e->timing[2], e->ev_e0, e->ev_e1));
   HIP_TRY(hipEventElapsedTime(&e->timing[3], e->ev_start, e->ev_end));
-  {
-    bool lost = false;
-    const int rc = fold_status(e, R, want_mfe, want_pf, order.data(), 0, "traceback could not reproduce a table value", &lost);
-    if (lost && !e->in_fallback) return redo_solo(e, again);      // (see score_batch_impl)
-    if (rc != DRNA_OK) return rc;
-  }
+  bool lost = false;
+  const int rc = fold_status(e, R, want_mfe, want_pf, order.data(), 0, "traceback could not reproduce a table value", &lost);
+  if (lost && !e->in_fallback) return redo_solo(e, again);      // (see score_batch_impl)
+  if (rc != DRNA_OK) return rc;
   if (!e->in_fallback) e->fallback_streak = 0;
   // results back in the caller's order
-  if (want_pf) {
-    std::vector<double> t(R);
-    HIP_TRY(hipMemcpy(t.data(), e->d_Epf, (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
-    for (int q = 0; q < R; q++) Epf[order[q]] = t[q];
-  }
+  if (want_pf) { const int rc = scatter_back(e, e->d_Epf, order, Epf); if (rc != DRNA_OK) return rc; }
   if (want_mfe) {
-    std::vector<int32_t> t(R);
-    HIP_TRY(hipMemcpy(t.data(), e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int q = 0; q < R; q++) Emfe[order[q]] = t[q];
+    { const int rc = scatter_back(e, e->d_Emfe, order, Emfe); if (rc != DRNA_OK) return rc; }
     HIP_TRY(hipMemcpy(sorted_seqs.data(), e->d_ss, total, hipMemcpyDeviceToHost));
     for (int q = 0; q < R; q++) memcpy(mfe_ss + src_off[order[q]], sorted_seqs.data() + off[q], (size_t)h[q]);
   }
-  if (want_ev) {
-    std::vector<int32_t> t(R);
-    HIP_TRY(hipMemcpy(t.data(), e->d_Ed, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int q = 0; q < R; q++) Ed[order[q]] = t[q];
-  }
+  if (want_ev) { const int rc = scatter_back(e, e->d_Ed, order, Ed); if (rc != DRNA_OK) return rc; }
   return DRNA_OK;
 }
 

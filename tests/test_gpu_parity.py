@@ -1035,3 +1035,33 @@ def test_one_launch_form_equals_the_two_launches(eng400, oracle, eterna_targets)
         assert 0 < tm["mfe"] <= tm["total"] * 1.05 and 0 < tm["pf"] <= tm["total"] * 1.05
         ss, e = oracle.mfe(seqs[0])
         assert (a["mfe_ss"][0] == (oracle.pk_struct(seqs[0], ss) if pk else ss)) and int(a["Emfe"][0]) == e
+
+
+def test_per_call_flag_sets_and_exchange_rows_grow_with_the_batch():
+    """The hand-over flags of the two-workgroup MFE fold and of the partition function's helpers, and the exchange rows, are sized
+    by the largest batch an engine has seen (not by max_R).  A fresh engine at the shortest length where the two-workgroup kernel,
+    the helpers and the one launch all engage unforced (130 nt) sees R = 2, 8, 2: first allocation, growth, a smaller batch in
+    the grown buffers.  Growth is no epoch reset, nothing is lost, and the results are those of one workgroup per fold."""
+    from desirna_amd import engine as E
+    rng = np.random.default_rng(130828)
+    L = 130
+    batches = [[_rand(rng, L) for _ in range(R)] for R in (2, 8, 2)]
+    flags = E.NEED_PF | E.NEED_MFE | E.NEED_EVAL
+    eng = E.Engine(max_R=8, max_L=L, device=0)
+    try:
+        eng.set_targets(["(((....)))" + "." * (L - 10)])
+        resets = eng.get_option("flag_resets")
+        got = []
+        for seqs in batches:
+            got.append(eng.score_batch(seqs, flags))
+            assert eng.get_option("last_fused") == 1 and eng.get_option("last_workgroups") == 4 * len(seqs)
+            assert eng.get_option("sync_fallbacks") == 0 and eng.get_option("flag_resets") == resets
+        for name in ("fused", "dual", "pf_helper"):
+            eng.set_option(name, 0)
+        for seqs, x in zip(batches, got):
+            a = eng.score_batch(seqs, flags)
+            assert eng.get_option("last_fused") == 0 and eng.get_option("last_workgroups") == 2 * len(seqs)
+            assert (x["Epf"].view(np.int64) == a["Epf"].view(np.int64)).all()
+            assert x["mfe_ss"] == a["mfe_ss"] and (x["Emfe"] == a["Emfe"]).all() and (x["Ed"] == a["Ed"]).all()
+    finally:
+        eng.close()
