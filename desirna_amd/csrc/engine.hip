@@ -33,6 +33,7 @@
 #include "fold_cofold_subopt.hpp"
 #include "fold_subopt_lds.hpp"
 #include "fold_cofold_outside.hpp"
+#include "fold_edef_lds.hpp"
 #include "host_driver.hpp"
 #include "tables.hpp"
 
@@ -95,6 +96,8 @@ struct drna_engine {
   double *hm_F4 = nullptr, *dm_F4 = nullptr;   // ... of drna_cofold_batch and drna_mc_run_cofold: host-mapped like hm_Epf, allocated on first use
   bool cofold_lds = true;   // option "cofold_lds": pairs of at most CO_LDS_MAX nt fold with their tables in LDS (fold_cofold_lds.hpp)
   bool self_dimer_lds = true;   // option "self_dimer_lds": self-dimers of at most SD_LDS_MAX nt keep their tables in LDS (fold_self_dimer.hpp)
+  bool edef_lds = true;     // option "edef_lds": ensemble defects of at most EDEF_LDS_HOST_MAX nt (pairs: CO_EDEF_LDS_MAX) in one launch, tables in LDS (fold_edef_lds.hpp)
+  int edef_lds_calls = 0;   // launches of that kernel (read-only option "edef_lds_calls")
   bool subopt_lds = true;   // option "subopt_lds": second-best folds of at most SUB_LDS_MAX nt keep their tables in LDS (fold_subopt_lds.hpp)
   // K-best structures: workspace for kb_chunk sequences, allocated on first use
   int32_t* d_ws_kb = nullptr;
@@ -416,6 +419,7 @@ extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!strcmp(name, "pf_helper")) { e->pf_helper = value != 0; return DRNA_OK; }
   if (!strcmp(name, "cofold_lds")) { e->cofold_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds")) { e->subopt_lds = value != 0; return DRNA_OK; }
+  if (!strcmp(name, "edef_lds")) { e->edef_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "self_dimer_lds")) { e->self_dimer_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "helper_fault")) { e->helper_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "strip_fault")) { e->strip_fault = value != 0; return DRNA_OK; }
@@ -443,6 +447,10 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "fused")) { *value = e->fused ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "cofold_lds")) { *value = e->cofold_lds ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "cofold_lds_max")) { *value = CO_LDS_MAX; return DRNA_OK; }
+  if (!strcmp(name, "edef_lds")) { *value = e->edef_lds ? 1 : 0; return DRNA_OK; }
+  if (!strcmp(name, "edef_lds_max")) { *value = EDEF_LDS_HOST_MAX; return DRNA_OK; }     // what the host sends there; the kernel holds EDEF_LDS_MAX
+  if (!strcmp(name, "cofold_edef_lds_max")) { *value = CO_EDEF_LDS_MAX; return DRNA_OK; }
+  if (!strcmp(name, "edef_lds_calls")) { *value = e->edef_lds_calls; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds")) { *value = e->subopt_lds ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds_max")) { *value = SUB_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "self_dimer_lds")) { *value = e->self_dimer_lds ? 1 : 0; return DRNA_OK; }
@@ -990,35 +998,58 @@ static int cofold_edef_impl(drna_engine* e, int R, int L, int cut, const char* d
                         [&] { hipLaunchKernelGGL(cofold_outside_kernel<1024>, dim3(R), dim3(1024), 0, e->s_pf, o); });
 }
 
-// R sequences in device memory (cut = 0: one strand).  More of them than the workspaces hold (DRNA_WS_GB): one sub-batch of
-// ws_slots after the other; last_edef_timing = their sums
-static int edef_batch_device(drna_engine* e, int R, int L, int cut, const char* d_seqs, double* d_edef, double* d_bpp) {
+// short designs: inside and outside sweep in one launch on tables in LDS (fold_edef_lds.hpp), no workspace slot; cut = 0: one
+// strand, the instance with an empty second strand.  timing_edef[0] is the launch, [1] stays ~0
+static int edef_lds_impl(drna_engine* e, int R, int L, int cut, const char* d_seqs, double* d_edef, double* d_bpp, int r_base) {
+  EdefLdsArgs a;
+  a.in = co_args(e, d_seqs, L, cut ? cut : L, 0);
+  a.out.F = e->d_pfT; a.out.plan = e->d_plan; a.out.scale = e->d_scale; a.out.eMLb = e->d_eMLb;
+  a.out.seqs = d_seqs; a.out.L = L; a.out.cut = a.in.cut; a.out.eDuplexInit = a.in.eDuplexInit;
+  a.out.pt = e->d_pt; a.out.edef = d_edef; a.out.bpp = d_bpp; a.out.status_pf = a.in.status_pf;
+  e->edef_lds_calls++;
+  return inside_outside(e, R, r_base, "unexpected status of the ensemble-defect kernel",
+                        [&] {
+                          if (cut) hipLaunchKernelGGL((edef_lds_kernel<1024, false>), dim3(R), dim3(1024), 0, e->s_pf, a);
+                          else hipLaunchKernelGGL((edef_lds_kernel<1024, true>), dim3(R), dim3(1024), 0, e->s_pf, a);
+                        },
+                        [] {});
+}
+
+// R sequences in device memory (cut = 0: one strand), the caller's r_base, r_base + 1, ...  Short ones take the fused LDS kernel
+// (option "edef_lds"), in chunks of max_R (the status words); the others one sub-batch of ws_slots after the other (the
+// workspaces, DRNA_WS_GB).  last_edef_timing = the chunks' sums, added to *tsum when given
+static int edef_batch_device(drna_engine* e, int R, int L, int cut, const char* d_seqs, double* d_edef, double* d_bpp, int r_base = 0,
+                             float* tsum = nullptr) {
   static_assert(sizeof(double) == 8, "workspace strides are counted in doubles");
-  if (cut && (cofold_outside_ws_stride(L + 2) > (long long)pf_ws_stride(L + 2) || 4ll * (L + 2) * (L + 2) > outside_ws_stride(L + 2))) {
+  const bool lds = e->edef_lds && L <= (cut ? CO_EDEF_LDS_MAX : EDEF_LDS_HOST_MAX);
+  if (!lds && cut && (cofold_outside_ws_stride(L + 2) > (long long)pf_ws_stride(L + 2) || 4ll * (L + 2) * (L + 2) > outside_ws_stride(L + 2))) {
     e->err = "drna_cofold_ensemble_defect_batch: workspace slot too small for the outside tables";
     return DRNA_ERR_INTERNAL;
   }
   HIP_TRY(hipSetDevice(e->device));
-  { const int rc = outside_workspace(e); if (rc != DRNA_OK) return rc; }
-  if (cut && !e->d_F4) HIP_TRY(hipMalloc((void**)&e->d_F4, (size_t)4 * e->max_R * sizeof(double)));
+  if (!lds) { const int rc = outside_workspace(e); if (rc != DRNA_OK) return rc; }
+  if ((cut || lds) && !e->d_F4) HIP_TRY(hipMalloc((void**)&e->d_F4, (size_t)4 * e->max_R * sizeof(double)));
   float sum[2] = {0, 0};
-  for (int r0 = 0; r0 < R; r0 += e->ws_slots) {
-    const int m = std::min(e->ws_slots, R - r0);
+  const int step = lds ? e->max_R : e->ws_slots;
+  for (int r0 = 0; r0 < R; r0 += step) {
+    const int m = std::min(step, R - r0);
     const char* s = d_seqs + (size_t)r0 * L;
     double* b = d_bpp ? d_bpp + (size_t)r0 * (L + 1) * (L + 1) : nullptr;
-    const int rc = cut ? cofold_edef_impl(e, m, L, cut, s, d_edef + r0, b, r0) : ensemble_defect_impl(e, m, L, s, d_edef + r0, b, r0);
+    const int rc = lds   ? edef_lds_impl(e, m, L, cut, s, d_edef + r0, b, r_base + r0)
+                   : cut ? cofold_edef_impl(e, m, L, cut, s, d_edef + r0, b, r_base + r0)
+                         : ensemble_defect_impl(e, m, L, s, d_edef + r0, b, r_base + r0);
     if (rc != DRNA_OK) return rc;
     sum[0] += e->timing_edef[0]; sum[1] += e->timing_edef[1];
   }
   e->timing_edef[0] = sum[0]; e->timing_edef[1] = sum[1];
+  if (tsum) { tsum[0] += sum[0]; tsum[1] += sum[1]; }
   return DRNA_OK;
 }
 
-// the same from and to host memory; bpp optional
+// the same from and to host memory; bpp optional.  R is not limited by max_R: the staging buffers take max_R sequences at a time
 static int edef_batch_host(drna_engine* e, int R, int L, int cut, const char* seqs, double* edef, double* bpp) {
   HIP_TRY(hipSetDevice(e->device));
   if (!e->d_edef) HIP_TRY(hipMalloc((void**)&e->d_edef, (size_t)e->max_R * sizeof(double)));
-  HIP_TRY(hipMemcpy(e->d_seqs, seqs, (size_t)R * L, hipMemcpyHostToDevice));
   double* d_bpp = nullptr;
   const size_t nb = (size_t)R * (L + 1) * (L + 1) * sizeof(double);
   if (bpp) {
@@ -1027,18 +1058,23 @@ static int edef_batch_host(drna_engine* e, int R, int L, int cut, const char* se
     if (z == hipSuccess) z = hipDeviceSynchronize();     // the memset runs on the null stream, the kernels on a non-blocking stream
     if (z != hipSuccess) { (void)hipFree(d_bpp); e->err = "hipMemset(bpp)"; return DRNA_ERR_DEVICE; }
   }
-  int rc = edef_batch_device(e, R, L, cut, e->d_seqs, e->d_edef, d_bpp);
-  if (rc == DRNA_OK) {
-    hipError_t c1 = hipMemcpy(edef, e->d_edef, (size_t)R * sizeof(double), hipMemcpyDeviceToHost);
-    hipError_t c2 = bpp ? hipMemcpy(bpp, d_bpp, nb, hipMemcpyDeviceToHost) : hipSuccess;
-    if (c1 != hipSuccess || c2 != hipSuccess) { e->err = "hipMemcpy(edef/bpp)"; rc = DRNA_ERR_DEVICE; }
+  int rc = DRNA_OK;
+  float sum[2] = {0, 0};
+  for (int r0 = 0; r0 < R && rc == DRNA_OK; r0 += e->max_R) {
+    const int m = std::min(e->max_R, R - r0);
+    if (hipMemcpy(e->d_seqs, seqs + (size_t)r0 * L, (size_t)m * L, hipMemcpyHostToDevice) != hipSuccess) { e->err = "hipMemcpy(seqs)"; rc = DRNA_ERR_DEVICE; break; }
+    rc = edef_batch_device(e, m, L, cut, e->d_seqs, e->d_edef, d_bpp ? d_bpp + (size_t)r0 * (L + 1) * (L + 1) : nullptr, r0, sum);
+    if (rc == DRNA_OK && hipMemcpy(edef + r0, e->d_edef, (size_t)m * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { e->err = "hipMemcpy(edef)"; rc = DRNA_ERR_DEVICE; }
   }
+  e->timing_edef[0] = sum[0]; e->timing_edef[1] = sum[1];
+  if (rc == DRNA_OK && bpp && hipMemcpy(bpp, d_bpp, nb, hipMemcpyDeviceToHost) != hipSuccess) { e->err = "hipMemcpy(bpp)"; rc = DRNA_ERR_DEVICE; }
   if (d_bpp) (void)hipFree(d_bpp);
   return rc;
 }
 
+// (R >= 1 is all that is asked of R: a batch beyond max_R goes through the staging buffers and status words in chunks)
 static int edef_check(drna_engine* e, const char* who, int R, int L, const int* cut, bool ok) {
-  const int rc = aux_check(e, who, R, L, cut, ok, "seqs and edef required");
+  const int rc = aux_check(e, who, std::min(R, e->max_R), L, cut, ok, "seqs and edef required");
   return rc != DRNA_OK ? rc : need_targets(e, who, L);
 }
 

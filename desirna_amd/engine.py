@@ -408,7 +408,9 @@ class Engine:
     def ensemble_defect_arrays(self, seqs_u8, want_bpp=False):
         """Ensemble defect of each sequence ((R, L) uint8 ASCII letters) against targets[0] (reference
         ScoreSeq.get_ensemble_defect, utils/energy_scores.py:362-374).  Returns float64[R]; with want_bpp also the
-        (R, L+1, L+1) base-pair probability matrices (1-based, upper triangle)."""
+        (R, L+1, L+1) base-pair probability matrices (1-based, upper triangle).  R is not limited by max_R.  Sequences of at
+        most ``get_option("edef_lds_max")`` nucleotides (pairs: ``"cofold_edef_lds_max"``) take one fused launch with every table
+        in LDS (option ``"edef_lds"``, default 1; the counter ``"edef_lds_calls"`` counts those launches)."""
         seqs_u8 = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
         R, L = seqs_u8.shape
         ed = np.zeros(R, dtype=np.float64)

@@ -160,6 +160,8 @@ int drna_cofold_subopt_energy_batch(drna_engine *e, int R, int L, int cut, const
  * drna_set_targets (same L, '&' removed, '(' ')' pairs only).
  *   edef  R doubles
  *   bpp   R*(L+1)*(L+1) doubles, may be NULL: P(i,j) at [i*(L+1)+j], 1 <= i < j <= L, every other entry 0
+ * R is not limited by max_R (chunks of max_R).  Pairs of at most "cofold_edef_lds_max" nucleotides take one fused launch with
+ * every table in LDS (option "edef_lds", see drna_set_option); the values do not depend on it.
  * A new symbol: no existing buffer changes, DRNA_ABI_VERSION stays 3.
  */
 int drna_cofold_ensemble_defect_batch(drna_engine *e, int R, int L, int cut, const char *seqs, double *edef, double *bpp);
@@ -186,6 +188,8 @@ int drna_subopt_structs_batch(drna_engine *e, int R, int L, const char *seqs, in
  * cancels in every probability.
  *   edef  R doubles in [0,1]                                     out
  *   bpp   R*(L+1)*(L+1) doubles, P(i,j) at [r][i][j], 1 <= i < j <= L  out, may be NULL
+ * R is not limited by max_R (chunks of max_R).  Sequences of at most "edef_lds_max" nucleotides take one fused launch with
+ * every table in LDS (option "edef_lds", see drna_set_option).
  */
 int drna_ensemble_defect_batch(drna_engine *e, int R, int L, const char *seqs, double *edef, double *bpp);
 
@@ -197,7 +201,8 @@ int drna_ensemble_defect_batch_device(drna_engine *e, int R, int L, const char *
  * of calls; out may be NULL (reset only).  Lets a caller time a loop of calls without a query per call. */
 int drna_timing_sums(drna_engine *e, double out[5], int reset);
 
-/* device ms of the last drna_ensemble_defect_batch*: out[0] = inside kernel, out[1] = outside kernel */
+/* device ms of the last drna_ensemble_defect_batch*: out[0] = inside kernel, out[1] = outside kernel; on the fused LDS path
+ * out[0] = the one launch, out[1] ~ 0 */
 int drna_last_edef_timing(const drna_engine *e, float out[2]);
 
 /*
@@ -222,6 +227,13 @@ int drna_last_edef_timing(const drna_engine *e, float out[2]);
  * drna_mc_run_nd / drna_mc_run_cofold_nd fold sequences (pairs: both strands together) of at most "subopt_lds_max" nucleotides
  * (read-only, 79) with their three two-best tables in LDS (fold_subopt_lds.hpp); 0 = the general kernels.  E2 and E12 are
  * bit-identical either way.
+ * "edef_lds" (default 1): drna_ensemble_defect_batch[_device], drna_cofold_ensemble_defect_batch and the Edef step of every
+ * drna_mc_run* take ONE launch for sequences of at most "edef_lds_max" nucleotides (read-only, 40: up to there the fused kernel is the faster one; its LDS would hold 71) and pairs of at most
+ * "cofold_edef_lds_max" nucleotides in all (read-only, 57): inside and outside sweep on tables in LDS (fold_edef_lds.hpp), no
+ * workspace slot; 0 = the two launches of the general kernels, which longer inputs take either way.  Two strands: edef and bpp are
+ * bit-identical either way.  One strand: the fused kernel sums in another order than outside_kernel, so edef and bpp move in
+ * the last bits with the option (about 1e-15; both within 1e-10 of the reference), as Epf does with "strips".  The read-only
+ * counter "edef_lds_calls" counts the launches of the fused kernel.
  */
 int drna_set_option(drna_engine *e, const char *name, int value);
 

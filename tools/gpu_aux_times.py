@@ -28,7 +28,8 @@ def cofold_subopt(eng, seqs):
 
 
 def cofold_edef(eng, seqs):
-    """two-strand outside kernel (-sf Edef) next to the co-fold partition function it runs after"""
+    """two-strand outside kernel (-sf Edef) next to the co-fold partition function it runs after (a pair within
+    cofold_edef_lds_max takes the fused launch: its time is the inside figure, the outside figure ~0)"""
     eng.cofold_batch(seqs, E.NEED_PF)
     p = eng.last_timing()["pf"]
     eng.cofold_ensemble_defect(seqs)
@@ -136,10 +137,41 @@ def nd_loop(eng, seqs):
     return out
 
 
+def edef_paths(eng, seqs):
+    """ensemble defect (-sf Edef) through the fused LDS kernel (option edef_lds = 1: one launch) and through the general inside +
+    outside kernels (0), same process and engine; at the reference's design sizes (36 nt, 18 + 18 nt) also the wall time per
+    iteration of the native Monte-Carlo loop with -sf Edef:1.0 (2 exchange steps of 20 iterations, same seed) either way"""
+    from desirna_amd import design
+    two = "&" in seqs[0]
+    R, L = len(seqs), len(seqs[0].replace("&", ""))
+    fn = eng.cofold_ensemble_defect if two else eng.ensemble_defect
+    loop = L == 36
+    inp = SimpleNamespace(name="edef", sec_struct=MC_TARGET if two else ND_TARGET, seq_restr=MC_RESTR if two else "N" * 36,
+                          seed_seq=None, alt_sec_struct=None, alt_sec_structs=None)
+    out = {}
+    for lds in (0, 1):
+        eng.set_option("edef_lds", lds)
+        eng.set_targets(["." * L])
+        c0 = eng.get_option("edef_lds_calls")
+        fn(seqs)
+        t = eng.last_edef_timing()
+        out["edef_ms_lds%d" % lds] = t["inside"] + t["outside"]
+        out["fused_launches_lds%d" % lds] = eng.get_option("edef_lds_calls") - c0
+        if loop:
+            t0 = time.perf_counter()
+            res = design.run_design_fast(inp, engine=eng, replicas=R, exchange=20, steps=2, seed=3, timelimit=600, scoring_f="Edef:1.0",
+                                         keep_records=False)
+            out["mc_iter_wall_ms_lds%d" % lds] = (time.perf_counter() - t0) * 1e3 / (res["steps"] * 20)
+    eng.set_option("edef_lds", 1)
+    return out
+
+
 PAIRS = ((64, 18, 18), (64, 50, 50), (64, 100, 100))
 SUB_MAX = 79          # SUB_LDS_MAX (fold_subopt_lds.hpp)
 CO_HALF = 32          # CO_LDS_MAX / 2 (fold_cofold_lds.hpp)
 SD_MAX = 62           # SD_LDS_MAX (fold_self_dimer.hpp)
+EDEF_MAX = 40         # EDEF_LDS_HOST_MAX (fold_edef_lds.hpp)
+CO_EDEF_MAX = 57      # CO_EDEF_LDS_MAX
 # one round of a section -> (shapes (R, strand lengths ...), seed, a fresh generator per shape, rounds, derived figure)
 SECTIONS = {
     edef: (((64, 200), (128, 400)), 20260101, True, 3,
@@ -154,6 +186,8 @@ SECTIONS = {
     cofold_paths: (((64, 18, 18), (64, CO_HALF, CO_HALF), (64, CO_HALF + 1, CO_HALF)), 5, False, 7,
                    lambda R, v: ("lds_over_general", (v["mfe_ms_lds1"] + v["pf_ms_lds1"]) / (v["mfe_ms_lds0"] + v["pf_ms_lds0"]))),
     self_dimer: (((64, 36), (64, SD_MAX), (64, 100)), 5, False, 7, lambda R, v: ("lds_over_general", v["pf_ms_lds1"] / v["pf_ms_lds0"])),
+    edef_paths: (((64, 36), (64, 18, 18), (64, EDEF_MAX), (64, CO_EDEF_MAX // 2, CO_EDEF_MAX - CO_EDEF_MAX // 2)), 5, False, 5,
+                 lambda R, v: ("lds_over_general", v["edef_ms_lds1"] / v["edef_ms_lds0"])),
     mc_cofold: (((64, 18, 18),), 5, False, 3,
                 lambda R, v: ("native_over_python", v["design_native_iter_per_s"] / v["design_python_iter_per_s"])),
 }
