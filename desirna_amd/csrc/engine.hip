@@ -1380,15 +1380,13 @@ static int second_best_mapped(drna_engine* e, int H, int L, int cut) {
   return fold_status(e, H, true, false, nullptr, 0, cut ? "unexpected status of the second-best co-fold" : "unexpected status of the second-best fold");
 }
 
-extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const char* seqs, int K, int32_t* E, char* ss) {
-  if (!e) return DRNA_ERR_ARG;
-  // (no upper limit on R here: the batch goes through the K-best workspace in chunks of kb_chunk)
-  { const int rc = aux_check(e, "drna_subopt_structs_batch", std::min(R, e->max_R), L, nullptr, K >= 1 && K <= 8 && seqs && E && ss,
-                             "1 <= K <= 8; seqs, E and ss required"); if (rc != DRNA_OK) return rc; }
+// the ranked structures of R sequences (cut > 0: pairs) through the K-best workspace in chunks of kb_chunk.  One slot size serves
+// both kernels (the two-strand one keeps its 1-D lists and stacks behind the three tables), whichever call comes first
+static int ranked_structs_batch(drna_engine* e, int R, int L, int cut, const char* seqs, int K, int32_t* E, char* ss) {
   HIP_TRY(hipSetDevice(e->device));
   const int KT = K <= 4 ? 4 : 8;                      // kernel instantiations
   const int ldmax = e->max_L + 2;
-  const size_t stride_max = (size_t)3 * 8 * ldmax * ldmax;
+  const size_t stride_max = (size_t)3 * 8 * ldmax * ldmax + (size_t)cofold_kbest_ws_extra(8, ldmax);
   if (!e->d_ws_kb) {
     e->kb_chunk = e->max_R < 16 ? e->max_R : 16;
     HIP_TRY(hipMalloc((void**)&e->d_ws_kb, stride_max * sizeof(int32_t) * e->kb_chunk));
@@ -1403,10 +1401,16 @@ extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const cha
     const int rc = R - r0 < e->kb_chunk ? R - r0 : e->kb_chunk;
     HIP_TRY(hipMemcpy(e->d_seqs, seqs + (size_t)r0 * L, (size_t)rc * L, hipMemcpyHostToDevice));
     for (int k = 0; k < rc; k++) e->h_status[k] = ST_OK;
-    const SuboptArgs a = subopt_args(e, L, 0, KT);
+    SuboptArgs a = subopt_args(e, L, cut, KT);
+    if (cut) a.ws_stride += cofold_kbest_ws_extra(KT, a.ld);
     HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-    if (KT == 4) hipLaunchKernelGGL((kbest_kernel<1024, 4>), dim3(rc), dim3(1024), 0, e->s_mfe, a);
-    else hipLaunchKernelGGL((kbest_kernel<1024, 8>), dim3(rc), dim3(1024), 0, e->s_mfe, a);
+    if (cut) {
+      if (KT == 4) hipLaunchKernelGGL((cofold_kbest_kernel<1024, 4>), dim3(rc), dim3(1024), 0, e->s_mfe, a);
+      else hipLaunchKernelGGL((cofold_kbest_kernel<1024, 8>), dim3(rc), dim3(1024), 0, e->s_mfe, a);
+    } else {
+      if (KT == 4) hipLaunchKernelGGL((kbest_kernel<1024, 4>), dim3(rc), dim3(1024), 0, e->s_mfe, a);
+      else hipLaunchKernelGGL((kbest_kernel<1024, 8>), dim3(rc), dim3(1024), 0, e->s_mfe, a);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
     HIP_TRY(hipStreamSynchronize(e->s_mfe));
@@ -1424,6 +1428,21 @@ extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const cha
   }
   e->timing[0] = ms_total; e->timing[1] = e->timing[2] = 0.f; e->timing[3] = ms_total;
   return DRNA_OK;
+}
+
+extern "C" int drna_subopt_structs_batch(drna_engine* e, int R, int L, const char* seqs, int K, int32_t* E, char* ss) {
+  if (!e) return DRNA_ERR_ARG;
+  // (no upper limit on R here: the batch goes through the K-best workspace in chunks of kb_chunk)
+  { const int rc = aux_check(e, "drna_subopt_structs_batch", std::min(R, e->max_R), L, nullptr, K >= 1 && K <= 8 && seqs && E && ss,
+                             "1 <= K <= 8; seqs, E and ss required"); if (rc != DRNA_OK) return rc; }
+  return ranked_structs_batch(e, R, L, 0, seqs, K, E, ss);
+}
+
+extern "C" int drna_cofold_subopt_structs_batch(drna_engine* e, int R, int L, int cut, const char* seqs, int K, int32_t* E, char* ss) {
+  if (!e) return DRNA_ERR_ARG;
+  { const int rc = aux_check(e, "drna_cofold_subopt_structs_batch", std::min(R, e->max_R), L, &cut, K >= 1 && K <= 8 && seqs && E && ss,
+                             "1 <= K <= 8; seqs, E and ss required"); if (rc != DRNA_OK) return rc; }
+  return ranked_structs_batch(e, R, L, cut, seqs, K, E, ss);
 }
 
 // ---------------------------------------------------------------- two strands (co-fold)

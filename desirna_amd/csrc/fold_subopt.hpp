@@ -1,5 +1,5 @@
 // fold_subopt.hpp -- the lowest-energy structures next to the ground state, one sequence (or sequence pair) per workgroup on
-// gfx950.  Three kernels over one table fill (kbest_fill) and one exterior level (kbest_exterior):
+// gfx950.  Four kernels over one table fill (kbest_fill) and one exterior level (kbest_exterior):
 //
 //   subopt_kernel         energy of the second-best structure of one strand.  Replaces
 //       get_first_suboptimal_structure_and_energy(seq, fc, 1)[1] of the reference's negative-design option (-nd on;
@@ -8,6 +8,8 @@
 //       used by the caller: the lowest energy over all structures other than one ground-state structure (0 if none lies
 //       within 49 kcal/mol of the MFE).
 //   cofold_subopt_kernel  the same for two strands: fold_cofold_subopt.hpp, over the CO = true instance of the fill below.
+//   cofold_kbest_kernel   kbest_kernel (below) for two strands: fold_cofold_subopt.hpp, over the CO = true instances of the fill and
+//       of the traceback's enumerator kb_enum.
 //   kbest_kernel          K lowest-energy structures (energies AND dot-bracket strings) of one strand.  Replaces
 //       get_first_suboptimal_structure_and_energy(seq, fc, k)[0] for k = 1 .. #alt structures, the call behind get_alt_mcc()
 //       in the reference's final ranking of alternative-structure designs (utils/sequence_utils.py:766-793,
@@ -336,11 +338,20 @@ struct KbSmem : MfeSmemCore<MAXN> {
   char db[K][MAXN + 2];
 };
 
-enum { KB_F = 1, KB_C = 2, KB_M = 3, KB_M2 = 4 };
+// kinds of a traceback item.  KB_F is the exterior level (two strands: Fu, the unconnected half); the last three exist for two
+// strands only: Fc[j], fcA[x] and fcB[y] (x, y travel in the item's i).  Seven kinds: the packed word has three bits for them
+enum { KB_F = 1, KB_C = 2, KB_M = 3, KB_M2 = 4, KB_FC = 5, KB_FA = 6, KB_FB = 7 };
 __device__ __forceinline__ int kb_pack(int kind, int i, int j, int r) { return i | (j << 12) | (kind << 24) | (r << 27); }
 
+template <int K, bool CO>
+struct KbNick {};
 template <int K>
-struct KbCtx {
+struct KbNick<K, true> {           // two strands (F is Fu there)
+  const TopK<K>*Fc, *fcA, *fcB;
+  int cut;
+};
+template <int K, bool CO>
+struct KbCtx : KbNick<K, CO> {
   const KbSmem<K>* sm;
   const MfeTables* T;
   const Plan* P;
@@ -350,43 +361,70 @@ struct KbCtx {
 };
 
 // candidates of element e of a table entry whose value is v; returns how many of them reproduce v and, when sel >= 0,
-// leaves the children of the sel-th such candidate in (ca, cb) (0 = no child)
-template <int K>
-__device__ int kb_enum(const KbCtx<K>& X, int kind, int i, int j, int v, int e, int sel, int& ca, int& cb) {
+// leaves the children of the sel-th such candidate in (ca, cb) (0 = no child).  The candidates are the terms of kbest_fill /
+// kbest_exterior, with the same conditions; CO adds the nick rules and the levels next to the nick
+template <int K, bool CO>
+__device__ int kb_enum(const KbCtx<K, CO>& X, int kind, int i, int j, int v, int e, int sel, int& ca, int& cb) {
   const KbSmem<K>& sm = *X.sm;
   const MfeTables& T = *X.T;
   const int ld = X.ld, n = X.n, HALF = INF_DEV / 2;
+  int cut = 0;
+  if constexpr (CO) cut = X.cut;
+  constexpr int D0 = CO ? 1 : TURN + 1;
   int cnt = 0;
 #define KB_HIT(A_, B_) do { if (cnt == sel) { ca = (A_); cb = (B_); } cnt++; } while (0)
-  if (kind == KB_F) {
+  if (kind == KB_F || (CO && kind == KB_FC)) {
+    const bool conn = CO && kind == KB_FC;
+    const TopK<K>* own = X.F;
+    if constexpr (CO) { if (conn) own = X.Fc; }
+    const int ok = conn ? KB_FC : KB_F;
     if (e == 0) {
-      const TopK<K> f = X.F[j - 1];
-      for (int a = 0; a < K; a++) if (f.v[a] < HALF && f.v[a] == v) KB_HIT(kb_pack(KB_F, 0, j - 1, a), 0);
+      const TopK<K> f = own[j - 1];
+      for (int a = 0; a < K; a++) if (f.v[a] < HALF && f.v[a] == v) KB_HIT(kb_pack(ok, 0, j - 1, a), 0);
     } else {
       const int p = e;
-      const int t = pair_type(sm.S[p], sm.S[j]);
-      if (t) {
-        const TopK<K> c = X.C[(j - p) * ld + p], f = X.F[p - 1];
-        const int x = (t > 2 ? T.TermAU : 0) + mfe_extstem(sm, t, p, j, n);
+      const bool same = !CO || co_same(p, j, cut);
+      const int t = (!CO || j - p > TURN || !same) ? pair_type(sm.S[p], sm.S[j]) : 0;
+      if (t && (same || conn)) {
+        // (two strands) the one exterior-level pair that joins the strands leads from Fc to Fu
+        const TopK<K> c = X.C[(j - p) * ld + p], f = (same ? own : X.F)[p - 1];
+        const int fk = same ? ok : KB_F;
+        int x = t > 2 ? T.TermAU : 0;
+        if constexpr (CO) x += co_endstem(sm.mmExt, sm, t, p > 1 && co_same(p - 1, p, cut), sm.S[p - 1], j < n && co_same(j, j + 1, cut), sm.S[j + 1]);
+        else x += mfe_extstem(sm, t, p, j, n);
         for (int a = 0; a < K; a++)
           for (int b = 0; b < K; b++)
-            if (f.v[a] < HALF && c.v[b] < HALF && f.v[a] + c.v[b] + x == v) KB_HIT(kb_pack(KB_F, 0, p - 1, a), kb_pack(KB_C, p, j, b));
+            if (f.v[a] < HALF && c.v[b] < HALF && f.v[a] + c.v[b] + x == v) KB_HIT(kb_pack(fk, 0, p - 1, a), kb_pack(KB_C, p, j, b));
       }
     }
   } else if (kind == KB_C) {
     const int d = j - i;
-    const int t = pair_type(sm.S[i], sm.S[j]);
+    const bool same = !CO || co_same(i, j, cut);
+    const int t = (!CO || d > TURN || !same) ? pair_type(sm.S[i], sm.S[j]) : 0;
     const int si1 = sm.S[i + 1], sj1 = sm.S[j - 1];
+    const int tau = t > 2 ? T.TermAU : 0;
+    if (CO && !t) return 0;
     if (e == 0) {
-      if (mfe_hairpin_e(sm, T, X.hp_len[d - 1], i, j, t) == v) KB_HIT(0, 0);
-      const TopK<K> m2 = X.M2[(d - 2) * ld + i + 1];
-      const int x = T.MLclosing + T.MLintern + (t > 2 ? T.TermAU : 0) + sm.mmM[rtype_of(t) * 16 + sj1 * 4 + si1];
-      for (int a = 0; a < K; a++) if (m2.v[a] < HALF && m2.v[a] + x == v) KB_HIT(kb_pack(KB_M2, i + 1, j - 1, a), 0);
+      if (same && mfe_hairpin_e(sm, T, X.hp_len[d - 1], i, j, t) == v) KB_HIT(0, 0);
+      const bool adj_i = !CO || co_same(i, i + 1, cut), adj_j = !CO || co_same(j - 1, j, cut);
+      if constexpr (CO)
+        if (!same) {
+          const TopK<K> fa = X.fcA[i + 1], fb = X.fcB[j - 1];
+          const int x = tau + co_endstem(sm.mmExt, sm, rtype_of(t), adj_j, sj1, adj_i, si1);
+          for (int a = 0; a < K; a++)
+            for (int b = 0; b < K; b++)
+              if (fa.v[a] < HALF && fb.v[b] < HALF && fa.v[a] + fb.v[b] + x == v) KB_HIT(kb_pack(KB_FA, i + 1, 0, a), kb_pack(KB_FB, j - 1, 0, b));
+        }
+      if (adj_i && adj_j && (!CO || d >= 2)) {
+        const TopK<K> m2 = X.M2[(d - 2) * ld + i + 1];
+        const int x = T.MLclosing + T.MLintern + tau + sm.mmM[rtype_of(t) * 16 + sj1 * 4 + si1];
+        for (int a = 0; a < K; a++) if (m2.v[a] < HALF && m2.v[a] + x == v) KB_HIT(kb_pack(KB_M2, i + 1, j - 1, a), 0);
+      }
     } else {
       const int u1 = X.P->u1[e - 1], u2 = X.P->u2[e - 1];
       const int dp = d - 2 - u1 - u2;
-      if (dp > TURN) {
-        const int p = i + 1 + u1, q = j - 1 - u2;
+      const int p = i + 1 + u1, q = j - 1 - u2;
+      if (dp >= D0 && (!CO || (co_same(i, p, cut) && co_same(q, j, cut)))) {
         const int t2 = pair_type(sm.S[p], sm.S[q]);
         if (t2) {
           const TopK<K> c = X.C[dp * ld + p];
@@ -396,25 +434,65 @@ __device__ int kb_enum(const KbCtx<K>& X, int kind, int i, int j, int v, int e, 
         }
       }
     }
-  } else {
+  } else if (!CO || kind == KB_M || kind == KB_M2) {
     const int d = j - i;
     const TopK<K>* own = kind == KB_M ? X.M : X.M2;
     if (e == 0) {
-      const TopK<K> m = own[(d - 1) * ld + i];
-      for (int a = 0; a < K; a++) if (m.v[a] < HALF && m.v[a] + T.MLbase == v) KB_HIT(kb_pack(kind, i, j - 1, a), 0);
+      if (!CO || co_same(j - 1, j, cut)) {
+        const TopK<K> m = own[(d - 1) * ld + i];
+        for (int a = 0; a < K; a++) if (m.v[a] < HALF && m.v[a] + T.MLbase == v) KB_HIT(kb_pack(kind, i, j - 1, a), 0);
+      }
     } else {
       const int k = i + e - 1;
-      const int tk = pair_type(sm.S[k], sm.S[j]);
+      const int tk = (!CO || j - k > TURN || !co_same(k, j, cut)) ? pair_type(sm.S[k], sm.S[j]) : 0;
       if (tk) {
         const TopK<K> c = X.C[(j - k) * ld + k];
-        const int st = T.MLintern + (tk > 2 ? T.TermAU : 0) + sm.mmM[tk * 16 + sm.S[k - 1] * 4 + sm.S[j + 1]];
-        if (kind == KB_M)
+        int st = T.MLintern + (tk > 2 ? T.TermAU : 0);
+        if constexpr (CO) st += co_endstem(sm.mmM, sm, tk, k > 1 && co_same(k - 1, k, cut), sm.S[k - 1], j < n && co_same(j, j + 1, cut), sm.S[j + 1]);
+        else st += sm.mmM[tk * 16 + sm.S[k - 1] * 4 + sm.S[j + 1]];
+        if (kind == KB_M && (!CO || co_same(i, k, cut)))
           for (int a = 0; a < K; a++) if (c.v[a] < HALF && c.v[a] + (k - i) * T.MLbase + st == v) KB_HIT(kb_pack(KB_C, k, j, a), 0);
-        if (k > i) {
+        if (k > i && (!CO || k - 1 != cut)) {
           const TopK<K> m = X.M[(k - 1 - i) * ld + i];
           for (int a = 0; a < K; a++)
             for (int b = 0; b < K; b++)
               if (m.v[a] < HALF && c.v[b] < HALF && m.v[a] + c.v[b] + st == v) KB_HIT(kb_pack(KB_M, i, k - 1, a), kb_pack(KB_C, k, j, b));
+        }
+      }
+    }
+  } else if constexpr (CO) {
+    if (kind == KB_FA) {
+      // fcA[x] of [x .. cut]: x unpaired, or x pairs with k <= cut and fcA[k + 1] follows
+      const int x = i;
+      if (e == 0) {
+        const TopK<K> f = X.fcA[x + 1];
+        for (int a = 0; a < K; a++) if (f.v[a] < HALF && f.v[a] == v) KB_HIT(kb_pack(KB_FA, x + 1, 0, a), 0);
+      } else {
+        const int k = x + e;
+        const int t = pair_type(sm.S[x], sm.S[k]);
+        if (t) {
+          const TopK<K> c = X.C[(k - x) * ld + x], f = X.fcA[k + 1];
+          const int ext = (t > 2 ? T.TermAU : 0) + co_endstem(sm.mmExt, sm, t, x > 1, sm.S[x - 1], k < cut, sm.S[k + 1]);
+          for (int a = 0; a < K; a++)
+            for (int b = 0; b < K; b++)
+              if (c.v[a] < HALF && f.v[b] < HALF && c.v[a] + f.v[b] + ext == v) KB_HIT(kb_pack(KB_C, x, k, a), kb_pack(KB_FA, k + 1, 0, b));
+        }
+      }
+    } else {
+      // fcB[y] of [cut + 1 .. y]: y unpaired, or y pairs with k > cut and fcB[k - 1] precedes
+      const int y = i;
+      if (e == 0) {
+        const TopK<K> f = X.fcB[y - 1];
+        for (int a = 0; a < K; a++) if (f.v[a] < HALF && f.v[a] == v) KB_HIT(kb_pack(KB_FB, y - 1, 0, a), 0);
+      } else {
+        const int k = cut + e;
+        const int t = pair_type(sm.S[k], sm.S[y]);
+        if (t) {
+          const TopK<K> f = X.fcB[k - 1], c = X.C[(y - k) * ld + k];
+          const int ext = (t > 2 ? T.TermAU : 0) + co_endstem(sm.mmExt, sm, t, k > cut + 1, sm.S[k - 1], y < n, sm.S[y + 1]);
+          for (int a = 0; a < K; a++)
+            for (int b = 0; b < K; b++)
+              if (f.v[a] < HALF && c.v[b] < HALF && f.v[a] + c.v[b] + ext == v) KB_HIT(kb_pack(KB_FB, k - 1, 0, a), kb_pack(KB_C, k, y, b));
         }
       }
     }
@@ -472,7 +550,7 @@ __global__ __launch_bounds__(NT) void kbest_kernel(SuboptArgs A) {
   __syncthreads();
 
   // ---- one traceback per rank; a wave works on one rank at a time, every lane holds the same state
-  KbCtx<K> X;
+  KbCtx<K, false> X;
   X.sm = &sm; X.T = &T; X.P = &P; X.hp_len = A.hp_len; X.C = C; X.M = M; X.M2 = M2; X.F = F; X.n = n; X.ld = ld;
   for (int rank = wave; rank < K; rank += NT / WAVE) {
     if (F[n].v[rank] >= HALF) continue;
@@ -498,7 +576,7 @@ __global__ __launch_bounds__(NT) void kbest_kernel(SuboptArgs A) {
       for (int b0 = 0; b0 < nel && !found; b0 += WAVE) {
         const int e = b0 + lane;
         int da = 0, dbb = 0;
-        const int cnt = e < nel ? kb_enum<K>(X, kind, i, j, v, e, -1, da, dbb) : 0;
+        const int cnt = e < nel ? kb_enum<K, false>(X, kind, i, j, v, e, -1, da, dbb) : 0;
         int pre = cnt;                               // inclusive prefix over the lanes (= over the elements, in order)
         for (int o = 1; o < WAVE; o <<= 1) {
           const int x = __shfl(pre, lane >= o ? lane - o : lane);
@@ -509,7 +587,7 @@ __global__ __launch_bounds__(NT) void kbest_kernel(SuboptArgs A) {
           const unsigned long long mask = __ballot(pre > m);
           const int win = __ffsll((long long)mask) - 1;
           const int sel = m - (__shfl(pre, win) - __shfl(cnt, win));
-          if (lane == win) kb_enum<K>(X, kind, i, j, v, e, sel, da, dbb);
+          if (lane == win) kb_enum<K, false>(X, kind, i, j, v, e, sel, da, dbb);
           ca = __shfl(da, win); cb = __shfl(dbb, win);
           found = true;
         } else m -= total;

@@ -49,6 +49,7 @@ _SIGNATURES = {
     "drna_cofold_subopt_energy_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _vp, _vp]),
     "drna_cofold_ensemble_defect_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _vp, _vp]),
     "drna_subopt_structs_batch": (_ci, [_vp, _ci, _ci, _str, _ci, _vp, _vp]),
+    "drna_cofold_subopt_structs_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _ci, _vp, _vp]),
     "drna_simscore_batch": (_ci, [_ci, _ci, _str, _vp, _vp, _vp, _vp]),
     "drna_propose_batch": (_ci, [_ci, _ci, _str, _vp, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci, _vp, _vp]),
     "drna_propose_batch_alt": (_ci, [_ci, _ci, _str, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci,
@@ -388,6 +389,20 @@ class Engine:
                                                       ss.ctypes.data))
         raw = ss.tobytes().decode("ascii")
         return E, [[raw[(r * K + k) * L:(r * K + k + 1) * L] for k in range(K)] for r in range(R)]
+
+    def cofold_subopt_structs(self, seqs, K):
+        """Two strands: the K (<= 8) lowest-energy co-fold structures of each 'AAAA&BBBB' pair (equal cut): (R, K) int32 energies
+        in dcal/mol (ascending; 10000000 where a pair has fewer structures) and a list of R lists of K dot-bracket strings
+        with the '&' put back at the cut.  Rank k is what get_first_suboptimal_structure_and_energy(seq, fc, k) takes from the
+        dimer fold compound; the structures and energies are those of :meth:`cofold_batch`'s MFE, the order among structures
+        of equal energy is the engine's own."""
+        flat, R, L, cut = _split_pairs(seqs)
+        E = np.zeros((R, K), dtype=np.int32)
+        ss = np.zeros((R, K, L), dtype=np.uint8)
+        self._check(self._L.drna_cofold_subopt_structs_batch(self._h, R, L, cut, flat, int(K), E.ctypes.data, ss.ctypes.data))
+        raw = ss.tobytes().decode("ascii")
+        rows = [[raw[(r * K + k) * L:(r * K + k + 1) * L] for k in range(K)] for r in range(R)]
+        return E, [[x[:cut] + "&" + x[cut:] for x in row] for row in rows]
 
     def ensemble_defect(self, seqs, want_bpp=False):
         """String form of :meth:`ensemble_defect_arrays` (seqs: list of equal-length strings)."""

@@ -80,25 +80,32 @@ def get_alt_mcc(simulation_data, alt_sec_structs, engine):
     the records as ``mcc_k`` / ``alt_struct_k`` -- reference ``get_alt_mcc`` (``utils/sequence_utils.py:766-793``) on top of
     ``get_first_suboptimal_structure_and_energy`` (``utils/energy_scores.py:453-488``: entry k of the energy-sorted subopt list
     found within at most 49 kcal/mol of the ground state, else all dots).  The ranked structures of all records come from
-    one ``engine.subopt_structs`` call per sequence length (GPU; no CPU fallback)."""
+    one ``engine.subopt_structs`` call per sequence length, for two-strand records (an ``&`` in the sequence: the reference
+    ranks the dimer fold compound's structures) from one ``engine.cofold_subopt_structs`` call per (length, cut) (GPU; no
+    CPU fallback).  The fallback string is ``"." * len(sequence)``, dots over the ``&`` column too, as the reference writes it;
+    its 1-MCC is that of the all-unpaired structure with the ``&`` in place (the reference's own comparison ends in a KeyError
+    there: its query is one position shorter than the ``Ee``-marked target)."""
     from .sim_score import SimScore
     n_alt = len(alt_sec_structs)
     if not simulation_data or not n_alt:
         return simulation_data
     if n_alt > 7:
         raise ValueError("at most 7 alternative structures (the engine ranks up to 8 structures per sequence)")
-    by_len = {}
+    two = ["&" in d["sequence"] for d in simulation_data]
+    if any(two) and not all(two):
+        raise ValueError("one-strand and two-strand records in one call")
+    groups = {}
     for i, d in enumerate(simulation_data):
-        if "&" in d["sequence"]:
-            raise ValueError("ranked sub-optimal structures are single-strand only")
-        by_len.setdefault(len(d["sequence"]), []).append(i)
-    for L, idx in by_len.items():
-        E, ss = engine.subopt_structs([simulation_data[i]["sequence"] for i in idx], n_alt + 1)
+        groups.setdefault((len(d["sequence"]), d["sequence"].find("&")), []).append(i)
+    ranked = engine.cofold_subopt_structs if two[0] else engine.subopt_structs
+    for (L, cut), idx in groups.items():
+        E, ss = ranked([simulation_data[i]["sequence"] for i in idx], n_alt + 1)
         for row, i in enumerate(idx):
             for k in range(1, n_alt + 1):
                 ok = E[row, k] < 10000000 and int(E[row, k]) - int(E[row, 0]) <= 4900
                 sub = ss[row][k] if ok else "." * L
-                sc = SimScore(alt_sec_structs[k - 1].replace("&", "Ee"), sub.replace("&", "Ee"))
+                query = sub if ok or cut < 0 else "." * cut + "&" + "." * (L - cut - 1)
+                sc = SimScore(alt_sec_structs[k - 1].replace("&", "Ee"), query.replace("&", "Ee"))
                 sc.find_basepairs()
                 sc.cofusion_matrix()
                 simulation_data[i]["mcc_" + str(k)] = 1 - sc.mcc()

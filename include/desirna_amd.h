@@ -180,6 +180,23 @@ int drna_cofold_ensemble_defect_batch(drna_engine *e, int R, int L, int cut, con
 int drna_subopt_structs_batch(drna_engine *e, int R, int L, const char *seqs, int K, int32_t *E, char *ss);
 
 /*
+ * The K lowest-energy CO-FOLD structures of R sequence pairs, energies and dot-bracket strings: the final ranking of a
+ * two-strand design with alternative structures.  Replaces get_first_suboptimal_structure_and_energy(seq, fc, k)[0] on the
+ * dimer fold compound, the call behind get_alt_mcc() (utils/sequence_utils.py:766-793, utils/energy_scores.py:453-488) when
+ * the sequence holds an '&'.  Pairs as for drna_cofold_batch: total length L, both strands concatenated WITHOUT the '&', the
+ * first strand `cut` nucleotides long (1 <= cut < L).  The structures and energies are those of drna_cofold_batch's MFE and
+ * of drna_cofold_subopt_energy_batch (DuplexInit iff a pair joins the strands; two equal strands are not reduced by symmetry:
+ * a structure and its rotation are two structures), so E[0] is the co-fold MFE and E[0 .. 1] the E12 of that call.  The
+ * reference pins no two-strand subopt output; structures of equal energy come in this engine's own fixed order.  R is not
+ * limited by max_R (the batch is worked off in chunks).
+ *   K    1 .. 8
+ *   E    R*K int32, dcal/mol, ascending per pair; 10000000 where the pair has fewer than rank+1 structures
+ *   ss   R*K*L chars (no terminator, no '&'); all dots where E = 10000000
+ * A new symbol: no existing signature or buffer changes, DRNA_ABI_VERSION stays 3.
+ */
+int drna_cofold_subopt_structs_batch(drna_engine *e, int R, int L, int cut, const char *seqs, int K, int32_t *E, char *ss);
+
+/*
  * Ensemble defect of R sequences against targets[0] (needs drna_set_targets with the same L): inside fill,
  * outside recursion, base-pair probabilities, then (1/L) * [ sum_{i unpaired in target} sum_j P(i,j)
  * + sum_{i paired with m in target} (1 - P(i,m)) ], '(' ')' pairs only.

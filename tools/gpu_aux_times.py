@@ -60,6 +60,19 @@ def subopt_structs(eng, seqs):
     return out
 
 
+def cofold_kbest(eng, seqs):
+    """K lowest-energy co-fold structures with their strings (get_alt_mcc of a two-strand design), both kernel instantiations,
+    next to the one-strand kernel on the same letters read as single strands of the total length"""
+    flat = [s.replace("&", "") for s in seqs]
+    out = {}
+    for K in (4, 8):
+        eng.cofold_subopt_structs(seqs, K)
+        out["cofold_kbest%d_ms" % K] = eng.last_timing()["mfe"]
+        eng.subopt_structs(flat, K)
+        out["kbest%d_ms" % K] = eng.last_timing()["mfe"]
+    return out
+
+
 def cofold_paths(eng, seqs):
     """both co-fold folds with the tables in LDS (option cofold_lds = 1) and on the general kernels (0), same process and engine;
     a pair beyond the bound takes the general kernels either way"""
@@ -183,6 +196,8 @@ SECTIONS = {
     nd_loop: (((64, 36),), 5, False, 3,
               lambda R, v: ("native_over_per_iteration", v["nd_native_scored_per_s"] / v["nd_per_iteration_scored_per_s"])),
     subopt_structs: (((16, 100), (16, 200)), 5, False, 5, lambda R, v: ("ratio", v["kbest8_ms"] / v["kbest4_ms"])),
+    cofold_kbest: (((16, 18, 18), (16, 50, 50)), 5, False, 5,
+                   lambda R, v: ("ratio_k8", v["cofold_kbest8_ms"] / v["kbest8_ms"])),
     cofold_paths: (((64, 18, 18), (64, CO_HALF, CO_HALF), (64, CO_HALF + 1, CO_HALF)), 5, False, 7,
                    lambda R, v: ("lds_over_general", (v["mfe_ms_lds1"] + v["pf_ms_lds1"]) / (v["mfe_ms_lds0"] + v["pf_ms_lds0"]))),
     self_dimer: (((64, 36), (64, SD_MAX), (64, 100)), 5, False, 7, lambda R, v: ("lds_over_general", v["pf_ms_lds1"] / v["pf_ms_lds0"])),
