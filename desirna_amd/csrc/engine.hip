@@ -1164,35 +1164,47 @@ static int scatter_back(drna_engine* e, const T* d_src, const std::vector<int>& 
   return DRNA_OK;
 }
 
-extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, const char* seqs, const int32_t* target_of,
-                                 uint32_t flags, double* Epf, int32_t* Emfe, char* mfe_ss, int32_t* Ed) {
-  if (!e) return DRNA_ERR_ARG;
-  const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK),
-             want_pk = flags & DRNA_NEED_PK, want_ev = flags & DRNA_NEED_EVAL;
-  if (R < 1 || R > e->max_R || !lens || !seqs || (want_pf && !Epf) || (want_mfe && (!Emfe || !mfe_ss)) ||
-      (want_ev && (!Ed || !target_of))) {
-    e->err = "drna_score_ragged: bad argument (R within the engine's limit; output pointers for every requested flag)";
-    return DRNA_ERR_ARG;
-  }
-  e->cur_with_pf = want_pf;
-  auto again = [&] { return drna_score_ragged(e, R, lens, seqs, target_of, flags, Epf, Emfe, mfe_ss, Ed); };
-  if (!e->in_fallback && e->solo_left > 0) {             // (see drna_score_batch_device)
-    const int rc = fold_solo(e, again);
-    e->solo_left--;
-    return rc;
-  }
-  // The batch is folded in SORTED order, longest first: position q on the device is sequence order[q] of the caller.  Then
-  // (a) the three classes -- strips (n > 200), general kernels, LDS-resident kernels (n <= 200) -- are ranges of q, and (b) a
-  // batch larger than the workspaces (ws_slots sequences, DRNA_WS_GB) goes through them in CHUNKS of consecutive q: chunk c
-  // uses slot q - c0, i.e. a workspace pointer moved back by c0 slots, its launches queue behind the previous chunk's on the
-  // same streams (the MFE stream owns the MFE workspace, the partition-function stream the other), and nothing waits in between.
-  // descriptors: len | off | target_of | index lists (q values) of the LDS-resident kernels | - | strip kernels | general kernels
-  std::vector<int> order(R);
-  std::iota(order.begin(), order.end(), 0);
+// What a ragged batch keeps from call to call while its lengths stay: drna_score_ragged plans and runs once, drna_mc_run_ragged
+// plans once and runs every iteration.
+// The batch is folded in SORTED order, longest first: position q on the device is sequence order[q] of the caller.  Then
+// (a) the three classes -- strips (n > 200), general kernels, LDS-resident kernels (n <= 200) -- are ranges of q, and (b) a
+// batch larger than the workspaces (ws_slots sequences, DRNA_WS_GB) goes through them in CHUNKS of consecutive q: chunk c
+// uses slot q - c0, i.e. a workspace pointer moved back by c0 slots, its launches queue behind the previous chunk's on the
+// same streams (the MFE stream owns the MFE workspace, the partition-function stream the other), and nothing waits in between.
+// descriptors h: len | off | target_of | index lists (q values) of the LDS-resident kernels | - | strip kernels | general kernels
+struct RaggedPlan {
+  int R = 0, nA = 0, nC = 0, nD = 0, strips = 0;   // strips: the option "strips" the index lists were made under (fold_solo turns it off)
+  uint32_t flags = 0;
   size_t total = 0;
+  std::vector<int> order, h;
+  std::vector<size_t> src_off;                     // of the caller's sequence r
+  std::vector<char> sorted;                        // the sequences going up / the structures coming back, in sorted order
+};
+// the three kernel classes of the plan's lengths under the engine's strip option, and the descriptor block on the device
+static int ragged_classes(drna_engine* e, RaggedPlan& p) {
+  const int R = p.R, ld = e->max_L + 2;
+  int *idxA = p.h.data() + (size_t)3 * R, *idxC = p.h.data() + (size_t)5 * R, *idxD = p.h.data() + (size_t)6 * R;
+  p.nA = p.nC = p.nD = 0;
+  for (int q = 0; q < R; q++) {
+    const int len = p.h[q];
+    if (len <= MFE_FAST_NMAX && len <= PF_FAST_NMAX) idxA[p.nA++] = q;
+    else if (strips_for(e, len, ld) && len > PF_FAST_NMAX) idxC[p.nC++] = q;
+    else idxD[p.nD++] = q;
+  }
+  p.strips = e->strips;
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->d_rg) HIP_TRY(hipMalloc((void**)&e->d_rg, (size_t)7 * e->max_R * sizeof(int)));
+  HIP_TRY(hipMemcpy(e->d_rg, p.h.data(), p.h.size() * sizeof(int), hipMemcpyHostToDevice));
+  return DRNA_OK;
+}
+static int ragged_plan(drna_engine* e, int R, const int32_t* lens, const int32_t* target_of, uint32_t flags, RaggedPlan& p) {
+  const bool want_ev = flags & DRNA_NEED_EVAL;
+  p.R = R; p.flags = flags; p.total = 0;
+  p.order.resize(R);
+  std::iota(p.order.begin(), p.order.end(), 0);
   for (int r = 0; r < R; r++) {
     if (lens[r] < 1 || lens[r] > e->max_L) { e->err = "drna_score_ragged: sequence length outside [1, max_L]"; return DRNA_ERR_ARG; }
-    total += (size_t)lens[r];
+    p.total += (size_t)lens[r];
     if (want_ev) {
       const int t = target_of[r];
       if (t < 0 || t >= (int)e->rt_len.size() || e->rt_len[t] != lens[r]) {
@@ -1201,38 +1213,46 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
       }
     }
   }
-  if (total > (size_t)e->max_R * e->max_L) { e->err = "drna_score_ragged: more nucleotides than max_R * max_L"; return DRNA_ERR_ARG; }
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });   // longest first
-  std::vector<size_t> src_off(R);
-  { size_t o = 0; for (int r = 0; r < R; r++) { src_off[r] = o; o += (size_t)lens[r]; } }
-  std::vector<int> h((size_t)7 * R);
-  std::vector<char> sorted_seqs(total);
-  int* off = h.data() + R;
-  {
-    size_t o = 0;
-    for (int q = 0; q < R; q++) {
-      const int r = order[q];
-      h[q] = lens[r];
-      off[q] = (int)o;
-      memcpy(sorted_seqs.data() + o, seqs + src_off[r], (size_t)lens[r]);
-      o += (size_t)lens[r];
-      if (want_ev) h[(size_t)2 * R + q] = target_of[r];
-    }
-  }
-  int nA = 0, nC = 0, nD = 0;
-  int *idxA = h.data() + (size_t)3 * R, *idxC = h.data() + (size_t)5 * R, *idxD = h.data() + (size_t)6 * R;
-  const int ld = e->max_L + 2;
+  if (p.total > (size_t)e->max_R * e->max_L) { e->err = "drna_score_ragged: more nucleotides than max_R * max_L"; return DRNA_ERR_ARG; }
+  std::stable_sort(p.order.begin(), p.order.end(), [&](int a, int b) { return lens[a] > lens[b]; });   // longest first
+  p.src_off.resize(R);
+  { size_t o = 0; for (int r = 0; r < R; r++) { p.src_off[r] = o; o += (size_t)lens[r]; } }
+  p.h.assign((size_t)7 * R, 0);
+  p.sorted.resize(p.total);
+  size_t o = 0;
   for (int q = 0; q < R; q++) {
-    const int len = h[q];
-    if (len <= MFE_FAST_NMAX && len <= PF_FAST_NMAX) idxA[nA++] = q;
-    else if (strips_for(e, len, ld) && len > PF_FAST_NMAX) idxC[nC++] = q;
-    else idxD[nD++] = q;
+    const int r = p.order[q];
+    p.h[q] = lens[r];
+    p.h[(size_t)R + q] = (int)o;
+    o += (size_t)lens[r];
+    if (want_ev) p.h[(size_t)2 * R + q] = target_of[r];
   }
-  HIP_TRY(hipSetDevice(e->device));
-  if (!e->d_rg) HIP_TRY(hipMalloc((void**)&e->d_rg, (size_t)7 * e->max_R * sizeof(int)));
-  HIP_TRY(hipMemcpy(e->d_rg, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_seqs, sorted_seqs.data(), total, hipMemcpyHostToDevice));
+  { const int rc = ragged_classes(e, p); if (rc != DRNA_OK) return rc; }
   if (want_ev && !e->d_Ed) HIP_TRY(hipMalloc((void**)&e->d_Ed, (size_t)e->max_R * std::max(1, e->n_targets) * sizeof(int32_t)));
+  return DRNA_OK;
+}
+
+// One scoring of the plan's batch: the sequences up, the launches, the status words, the results back in the caller's order
+static int ragged_run(drna_engine* e, RaggedPlan& p, const char* seqs, double* Epf, int32_t* Emfe, char* mfe_ss, int32_t* Ed) {
+  const uint32_t flags = p.flags;
+  const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK),
+             want_pk = flags & DRNA_NEED_PK, want_ev = flags & DRNA_NEED_EVAL;
+  const int R = p.R;
+  e->cur_with_pf = want_pf;
+  auto again = [&] { return ragged_run(e, p, seqs, Epf, Emfe, mfe_ss, Ed); };
+  if (!e->in_fallback && e->solo_left > 0) {             // (see drna_score_batch_device)
+    const int rc = fold_solo(e, again);
+    e->solo_left--;
+    return rc;
+  }
+  if (p.strips != e->strips) { const int rc = ragged_classes(e, p); if (rc != DRNA_OK) return rc; }   // (a redone call, or the first after one)
+  const int *h = p.h.data(), *off = h + R;
+  const int *idxA = h + (size_t)3 * R, *idxC = h + (size_t)5 * R, *idxD = h + (size_t)6 * R;
+  const int nA = p.nA, nC = p.nC, nD = p.nD;
+  const int ld = e->max_L + 2;
+  for (int q = 0; q < R; q++) memcpy(p.sorted.data() + off[q], seqs + p.src_off[p.order[q]], (size_t)h[q]);
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipMemcpy(e->d_seqs, p.sorted.data(), p.total, hipMemcpyHostToDevice));
   reset_status(e);
   if ((want_pf || want_mfe) && nC) { const int rc = strip_flags(e, want_mfe); if (rc != DRNA_OK) return rc; }
   Ragged rg;
@@ -1244,7 +1264,7 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
     MfeArgs a = mfe_args(e, e->d_seqs, 0, ld, want_pk ? 3 : 0, e->d_Emfe, e->d_ss);
     a.rg = rg;
     HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-    ragged_fold(e, R, h.data(), idxA, nA, idxC, nC, idxD, nD,
+    ragged_fold(e, R, h, idxA, nA, idxC, nC, idxD, nD,
                 [&](int c0) { a.ws = e->d_ws_mfe - (long long)c0 * a.ws_stride; a.rg.idx = nullptr; },
                 [&](int n, int S, int k, const int* idx) { launch_mfe_strips(e, a, n, S, k, idx, e->s_mfe); },
                 [&](int n, const int* idx) { a.rg.idx = idx; hipLaunchKernelGGL(mfe_kernel<1024>, dim3(n), dim3(1024), 0, e->s_mfe, a); },
@@ -1256,7 +1276,7 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
     PfArgs a = pf_args(e, e->d_seqs, 0, ld, e->d_Epf);
     a.rg = rg;
     HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
-    ragged_fold(e, R, h.data(), idxA, nA, idxC, nC, idxD, nD,
+    ragged_fold(e, R, h, idxA, nA, idxC, nC, idxD, nD,
                 [&](int c0) { a.ws = e->d_ws_pf - (long long)c0 * a.ws_stride; a.rg.idx = nullptr; },
                 [&](int n, int S, int k, const int* idx) { launch_pf_strips(e, a, n, S, k, idx, e->s_pf); },
                 [&](int n, const int* idx) { a.rg.idx = idx; hipLaunchKernelGGL(pf_kernel<1024>, dim3(n), dim3(1024), 0, e->s_pf, a); },
@@ -1283,19 +1303,33 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
   if (want_ev) HIP_TRY(hipEventElapsedTime(&e->timing[2], e->ev_e0, e->ev_e1));
   HIP_TRY(hipEventElapsedTime(&e->timing[3], e->ev_start, e->ev_end));
   bool lost = false;
-  const int rc = fold_status(e, R, want_mfe, want_pf, order.data(), 0, "traceback could not reproduce a table value", &lost);
+  const int rc = fold_status(e, R, want_mfe, want_pf, p.order.data(), 0, "traceback could not reproduce a table value", &lost);
   if (lost && !e->in_fallback) return redo_solo(e, again);      // (see score_batch_impl)
   if (rc != DRNA_OK) return rc;
   if (!e->in_fallback) e->fallback_streak = 0;
   // results back in the caller's order
-  if (want_pf) { const int rc = scatter_back(e, e->d_Epf, order, Epf); if (rc != DRNA_OK) return rc; }
+  if (want_pf) { const int rc = scatter_back(e, e->d_Epf, p.order, Epf); if (rc != DRNA_OK) return rc; }
   if (want_mfe) {
-    { const int rc = scatter_back(e, e->d_Emfe, order, Emfe); if (rc != DRNA_OK) return rc; }
-    HIP_TRY(hipMemcpy(sorted_seqs.data(), e->d_ss, total, hipMemcpyDeviceToHost));
-    for (int q = 0; q < R; q++) memcpy(mfe_ss + src_off[order[q]], sorted_seqs.data() + off[q], (size_t)h[q]);
+    { const int rc = scatter_back(e, e->d_Emfe, p.order, Emfe); if (rc != DRNA_OK) return rc; }
+    HIP_TRY(hipMemcpy(p.sorted.data(), e->d_ss, p.total, hipMemcpyDeviceToHost));
+    for (int q = 0; q < R; q++) memcpy(mfe_ss + p.src_off[p.order[q]], p.sorted.data() + off[q], (size_t)h[q]);
   }
-  if (want_ev) { const int rc = scatter_back(e, e->d_Ed, order, Ed); if (rc != DRNA_OK) return rc; }
+  if (want_ev) { const int rc = scatter_back(e, e->d_Ed, p.order, Ed); if (rc != DRNA_OK) return rc; }
   return DRNA_OK;
+}
+
+extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, const char* seqs, const int32_t* target_of,
+                                 uint32_t flags, double* Epf, int32_t* Emfe, char* mfe_ss, int32_t* Ed) {
+  if (!e) return DRNA_ERR_ARG;
+  const bool want_pf = flags & DRNA_NEED_PF, want_mfe = flags & (DRNA_NEED_MFE | DRNA_NEED_PK), want_ev = flags & DRNA_NEED_EVAL;
+  if (R < 1 || R > e->max_R || !lens || !seqs || (want_pf && !Epf) || (want_mfe && (!Emfe || !mfe_ss)) ||
+      (want_ev && (!Ed || !target_of))) {
+    e->err = "drna_score_ragged: bad argument (R within the engine's limit; output pointers for every requested flag)";
+    return DRNA_ERR_ARG;
+  }
+  RaggedPlan p;
+  const int rc = ragged_plan(e, R, lens, target_of, flags, p);
+  return rc != DRNA_OK ? rc : ragged_run(e, p, seqs, Epf, Emfe, mfe_ss, Ed);
 }
 
 // ---------------------------------------------------------------- second-best structure energy (-nd on), one and two strands
@@ -1836,7 +1870,7 @@ extern "C" int drna_metropolis_batch(int R, const double* score_o, const double*
 
 // What one scoring pass over the R proposals of an iteration leaves per replica (filled by the entry point's score step)
 struct McScored {
-  std::vector<char> ss;                          // R x L MFE structures, in the layout of the state strings
+  std::vector<char> ss;                          // the chains' MFE structures, in the layout of the state strings
   std::vector<double> Epf, ed, Emfe, edef;       // kcal/mol: ensemble free energy, E(targets[0]), MFE energy; ensemble defect
   std::vector<double> add;                       // added to the -sf sum: the alternative-structure term
   std::vector<double> x0, x1;                    // two strands: oligo_fraction and the bonus, kept with an accepted state; the bonus is
@@ -1844,47 +1878,68 @@ struct McScored {
   bool has_add = false;
 };
 
-// The loop both drna_mc_run and drna_mc_run_cofold run: proposals from the replicas' own streams, the entry point's scoring of
-// all R proposals (score_all(prop) fills S), SimScore (metrics(ss, pq): pair table of the L-char structure for the targeted
-// moves, and the three rounded metrics against the target), the -sf sum, Metropolis, state update, counters and best state.
-// L is the length of the state strings (two strands: with the '&'); xs0 / xs1: per-replica state beside the usual arrays or null.
+// The chains of a loop: chain r belongs to design problem of[r] and keeps its state strings (seqs, mfe_ss: len[r] chars) at off[r].
+// Problem p keeps its best strings at poff[p], its best values at best + p * best_vals and three counters.  One problem of R
+// replicas (every entry point but drna_mc_run_ragged) is mc_uniform: off[r] = r * L.
+struct McChains {
+  int P = 1, best_vals = 0, max_len = 0;
+  std::vector<int> of, len;
+  std::vector<size_t> off, poff;
+  size_t total = 0;
+  int R() const { return (int)of.size(); }
+};
+static McChains mc_uniform(int R, int L) {
+  McChains c;
+  c.max_len = L; c.total = (size_t)R * L;
+  c.of.assign(R, 0); c.len.assign(R, L); c.off.resize(R); c.poff.assign(1, 0);
+  for (int r = 0; r < R; r++) c.off[r] = (size_t)r * L;
+  return c;
+}
+
+// The loop every drna_mc_run* entry point runs: proposals from the chains' own streams, the entry point's scoring of all
+// proposals (score_all(prop) fills S), SimScore (metrics(r, ss, pq, m): pair table of chain r's structure for the targeted
+// moves, and the three rounded metrics against its target), the -sf sum, Metropolis, state update, counters and best state of
+// the chain's problem (ctx[p], p < ch.P).  A chain's strings have ch.len[r] chars (two strands: with the '&'); xs0 / xs1:
+// per-replica state beside the usual arrays or null.
 // Negative design (sub given: the _nd entry points; utils/energy_scores.py:104-108): between scoring and Metropolis the proposals
 // whose 1 - MCC is exactly 0 get their second-best fold in ONE launch (second_best(prop, hits, H) leaves E2 of hit h in
 // e->hm_Emfe[h]) and lose E2 / 100 - Epf; sub[r] is the second-best energy of replica r's current state (0 where it is unsolved)
-// and best[4] (two strands: best[6]) that of the best state.  So an iteration is two passes over the replicas: scores of all R
-// proposals first, then the Metropolis draws in replica order, each from its replica's own stream as before
+// and best[4] (two strands: best[6]) that of the best state.  So an iteration is two passes over the chains: scores of all
+// proposals first, then the Metropolis draws in chain order, each from its chain's own stream as before
 template <class ScoreAll, class Metrics, class SecondBest>
-static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, ProposeCtx& ctx, const int32_t* shelf_index, int targeted,
-                   const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w, uint32_t* rng_state,
-                   char* seqs, char* mfe_ss, double* score, double* mcc1, double* Epf, double* Ed, double* xs0, double* xs1, double* sub,
-                   int64_t* counters, char* best_seq, char* best_ss, double* best, McScored& S, ScoreAll&& score_all,
-                   Metrics&& metrics, SecondBest&& second_best) {
+static int mc_loop(drna_engine* e, const char* who, const McChains& ch, int n_iter, const ProposeCtx* ctx, const int32_t* shelf_index,
+                   int targeted, const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w,
+                   uint32_t* rng_state, char* seqs, char* mfe_ss, double* score, double* mcc1, double* Epf, double* Ed, double* xs0,
+                   double* xs1, double* sub, int64_t* counters, char* best_seq, char* best_ss, double* best, McScored& S,
+                   ScoreAll&& score_all, Metrics&& metrics, SecondBest&& second_best) {
   using namespace drna_host;
-  std::vector<char> prop((size_t)R * L);
+  const int R = ch.R();
+  const size_t* off = ch.off.data();
+  std::vector<char> prop(ch.total);
   std::vector<double> pscore(R), pmcc(R), p_shelf(R, 0.0), psub(sub ? R : 0);
   std::vector<unsigned char> acc(R), better(R), same(R), bad(R);
   std::vector<SimMetrics> pm(R);
   std::vector<int> hits;
-  // Per replica, of its CURRENT structure: the pair table, its SimScore against the target and the targeted-move pool (what the
+  // Per chain, of its CURRENT structure: the pair table, its SimScore against the target and the targeted-move pool (what the
   // proposal compares with the target).  Parsed once here and replaced when a proposal is accepted; a proposal whose MFE
   // structure equals the current one (most single mutations of a converged replica) reuses all three
-  std::vector<int> cur_pq((size_t)R * L), prop_pq((size_t)R * L), cur_pool((size_t)R * L), cur_np(R, -1);
+  std::vector<int> cur_pq(ch.total), prop_pq(ch.total), cur_pool(ch.total), cur_np(R, -1);
   std::vector<SimMetrics> cur_m(R);
-  std::vector<char> mark(L);
-  int fail = DRNA_OK;              // the last failure; the other replicas go on, as without it
+  std::vector<char> mark(ch.max_len);
+  int fail = DRNA_OK;              // the last failure; the other chains go on, as without it
   auto refresh_pool = [&](int r) {
-    if (targeted) cur_np[r] = targeted_pool(ctx, cur_pq.data() + (size_t)r * L, mark.data(), cur_pool.data() + (size_t)r * L);
+    if (targeted) cur_np[r] = targeted_pool(ctx[ch.of[r]], cur_pq.data() + off[r], mark.data(), cur_pool.data() + off[r]);
   };
-  auto propose_all = [&] {         // the next proposal of every replica, each from its own random stream
+  auto propose_all = [&] {         // the next proposal of every chain, each from its own random stream
     for (int r = 0; r < R; r++) {
-      const int rc = propose_one(ctx, seqs + (size_t)r * L, cur_pool.data() + (size_t)r * L, cur_np[r], p_shelf[r],
-                                 Mt{rng_state + (size_t)r * RNG_WORDS}, prop.data() + (size_t)r * L);
+      const int rc = propose_one(ctx[ch.of[r]], seqs + off[r], cur_pool.data() + off[r], cur_np[r], p_shelf[r],
+                                 Mt{rng_state + (size_t)r * RNG_WORDS}, prop.data() + off[r]);
       if (rc != DRNA_OK) fail = rc;
     }
   };
   for (int r = 0; r < R; r++) {
-    if (targeted) p_shelf[r] = shelf_probability(ctx, shelf_index[r]);
-    if (!metrics(mfe_ss + (size_t)r * L, cur_pq.data() + (size_t)r * L, cur_m[r])) { fail = DRNA_ERR_STRUCTURE; continue; }
+    if (targeted) p_shelf[r] = shelf_probability(ctx[ch.of[r]], shelf_index[r]);
+    if (!metrics(r, mfe_ss + off[r], cur_pq.data() + off[r], cur_m[r])) { fail = DRNA_ERR_STRUCTURE; continue; }
     refresh_pool(r);
   }
   if (n_iter > 0 && fail == DRNA_OK) propose_all();
@@ -1900,10 +1955,11 @@ static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, Pr
     hits.clear();
     for (int r = 0; r < R; r++) {
       // SimScore of the proposal's structure against the target (utils/sim_score.py:62-147)
-      same[r] = std::memcmp(S.ss.data() + (size_t)r * L, mfe_ss + (size_t)r * L, (size_t)L) == 0;
+      const int L = ch.len[r];
+      same[r] = std::memcmp(S.ss.data() + off[r], mfe_ss + off[r], (size_t)L) == 0;
       SimMetrics& m = pm[r];
       m = cur_m[r];
-      bad[r] = !same[r] && !metrics(S.ss.data() + (size_t)r * L, prop_pq.data() + (size_t)r * L, m);
+      bad[r] = !same[r] && !metrics(r, S.ss.data() + off[r], prop_pq.data() + off[r], m);
       if (bad[r]) { fail = DRNA_ERR_STRUCTURE; continue; }
       const double ed = S.ed[r];
       // -sf terms (utils/energy_scores.py:376-398): 0 Ed-Epf, 1 1-MCC, 2 sln_Epf, 3 Ed-MFE, 4 1-precision, 5 1-recall, 6 Edef
@@ -1940,18 +1996,19 @@ static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, Pr
     for (int r = 0; r < R; r++) {
       if (bad[r]) continue;
       if (xs0) pscore[r] += S.x1[r];                          // oligomer / monomer-fraction bonus: the last addition
+      const int L = ch.len[r];
       const bool same_ss = same[r];
       const SimMetrics& m = pm[r];
-      int* ppq = prop_pq.data() + (size_t)r * L;
+      int* ppq = prop_pq.data() + off[r];
       const double ed = S.ed[r];
-      // Metropolis (utils/replica_exchange_monte_carlo.py:26-57): one draw from the replica's stream, only when the mutant is worse
+      // Metropolis (utils/replica_exchange_monte_carlo.py:26-57): one draw from the chain's stream, only when the mutant is worse
       (void)drna_metropolis_batch(1, score + r, pscore.data() + r, temps + r, Lconst, rng_state + (size_t)r * RNG_WORDS, acc.data() + r,
                                   better.data() + r);
       if (acc[r]) {
-        std::memcpy(seqs + (size_t)r * L, prop.data() + (size_t)r * L, (size_t)L);
+        std::memcpy(seqs + off[r], prop.data() + off[r], (size_t)L);
         if (!same_ss) {
-          std::memcpy(mfe_ss + (size_t)r * L, S.ss.data() + (size_t)r * L, (size_t)L);
-          std::memcpy(cur_pq.data() + (size_t)r * L, ppq, (size_t)L * sizeof(int));
+          std::memcpy(mfe_ss + off[r], S.ss.data() + off[r], (size_t)L);
+          std::memcpy(cur_pq.data() + off[r], ppq, (size_t)L * sizeof(int));
           cur_m[r] = m;
           refresh_pool(r);
         }
@@ -1963,19 +2020,22 @@ static int mc_loop(drna_engine* e, const char* who, int R, int L, int n_iter, Pr
     if (it + 1 < n_iter && fail == DRNA_OK) propose_all();          // the next iteration's proposals (same streams, after the Metropolis draw)
     if (fail != DRNA_OK) { e->err = std::string(who) + ": unbalanced MFE structure from the engine, or a failed proposal"; return fail; }
     const double tp2 = mc_profile ? now_us() : 0.0;
-    // counters and the best state, replica by replica in replica order (first strictly better wins)
+    // counters and the best state of every problem, chain by chain in chain order (first strictly better wins)
     for (int r = 0; r < R; r++) {
+      const int p = ch.of[r];
+      int64_t* cnt = counters + (size_t)3 * p;
+      double* bst = best + (size_t)p * ch.best_vals;
       if (acc[r]) {
-        counters[0]++;
-        if (better[r]) counters[1]++;
-        if (mcc1[r] < best[0] || (mcc1[r] == best[0] && score[r] < best[1])) {
-          best[0] = mcc1[r]; best[1] = score[r]; best[2] = Epf[r]; best[3] = Ed[r];
-          if (xs0) { best[4] = xs0[r]; best[5] = xs1[r]; }
-          if (sub) best[xs0 ? 6 : 4] = sub[r];
-          std::memcpy(best_seq, seqs + (size_t)r * L, (size_t)L);
-          std::memcpy(best_ss, mfe_ss + (size_t)r * L, (size_t)L);
+        cnt[0]++;
+        if (better[r]) cnt[1]++;
+        if (mcc1[r] < bst[0] || (mcc1[r] == bst[0] && score[r] < bst[1])) {
+          bst[0] = mcc1[r]; bst[1] = score[r]; bst[2] = Epf[r]; bst[3] = Ed[r];
+          if (xs0) { bst[4] = xs0[r]; bst[5] = xs1[r]; }
+          if (sub) bst[xs0 ? 6 : 4] = sub[r];
+          std::memcpy(best_seq + ch.poff[p], seqs + off[r], (size_t)ch.len[r]);
+          std::memcpy(best_ss + ch.poff[p], mfe_ss + off[r], (size_t)ch.len[r]);
         }
-      } else counters[2]++;
+      } else cnt[2]++;
     }
     if (mc_profile) { prof[0] += tp1 - tp0 - e->timing[3] * 1e3; prof[1] += tp2 - tp1; prof[2] += now_us() - tp2; }
   }
@@ -2060,7 +2120,7 @@ static int mc_run_impl(drna_engine* e, const char* who, int R, int L, int n_iter
     }
     return DRNA_OK;
   };
-  auto metrics = [&](const char* ss, int* pq, SimMetrics& m) {
+  auto metrics = [&](int, const char* ss, int* pq, SimMetrics& m) {
     if (!pair_table(ss, L, pq)) return false;
     m = sim_metrics(pr, pq, L);
     return true;
@@ -2069,7 +2129,7 @@ static int mc_run_impl(drna_engine* e, const char* who, int R, int L, int n_iter
     for (int h = 0; h < H; h++) std::memcpy(e->hm_seqs + (size_t)h * L, prop + (size_t)hits[h] * L, (size_t)L);
     return second_best_mapped(e, H, L, 0);
   };
-  return mc_loop(e, who, R, L, n_iter, ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs,
+  return mc_loop(e, who, mc_uniform(R, L), n_iter, &ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs,
                  mfe_ss, score, mcc1, Epf, Ed, oligo_frac, bonus, subopt_e, counters, best_seq, best_ss, best, S, score_all, metrics,
                  second_best);
 }
@@ -2159,7 +2219,7 @@ static int mc_run_cofold_impl(const char* who, MC_RUN_CO_PARAMS, double* subopt_
   };
   expand(target);
   if (!pair_table(xs.data(), Ls + 1, xr.data())) { e->err = std::string(who) + ": unbalanced target structure"; return DRNA_ERR_STRUCTURE; }
-  auto metrics = [&](const char* ss, int* pq, SimMetrics& m) {
+  auto metrics = [&](int, const char* ss, int* pq, SimMetrics& m) {
     if (ss[cut] != '&' || !pair_table(ss, Ls, pq)) return false;
     expand(ss);
     if (!pair_table(xs.data(), Ls + 1, xq.data())) return false;
@@ -2200,7 +2260,7 @@ static int mc_run_cofold_impl(const char* who, MC_RUN_CO_PARAMS, double* subopt_
     }
     return second_best_mapped(e, H, L, cut);
   };
-  return mc_loop(e, who, R, Ls, n_iter, ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs, mfe_ss,
+  return mc_loop(e, who, mc_uniform(R, Ls), n_iter, &ctx, shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs, mfe_ss,
                  score, mcc1, Epf, Ed, oligo_frac, bonus, subopt_e, counters, best_seq, best_ss, best, S, score_all, metrics, second_best);
 }
 
@@ -2213,4 +2273,100 @@ extern "C" int drna_mc_run_cofold_nd(MC_RUN_CO_PARAMS, double* subopt_e) {
   if (!e) return DRNA_ERR_ARG;
   if (!subopt_e) { e->err = "drna_mc_run_cofold_nd: bad argument (subopt_e required)"; return DRNA_ERR_ARG; }
   return mc_run_cofold_impl("drna_mc_run_cofold_nd", e, MC_RUN_CO_ARGS, subopt_e);
+}
+
+// ---------------------------------------------------------------- a set of design problems in lock-step
+
+// drna_mc_run for P problems of different lengths: the chains of all problems make one ragged batch per iteration.  The plan of
+// that batch (lengths do not change inside a call) is made once; an iteration uploads the proposals, launches, and scatters back.
+extern "C" int drna_mc_run_ragged(drna_engine* e, int P, const int32_t* R_of, const int32_t* L_of, int n_iter, const char* targets,
+                                  const unsigned char* allowed_mask, const int32_t* shelf_index, const int32_t* n_shelves,
+                                  double tm_max, double tm_min, int targeted, const double* temps, double Lconst, int n_terms,
+                                  const int32_t* term_id, const double* term_w, uint32_t flags, uint32_t* rng_state, char* seqs,
+                                  char* mfe_ss, double* score, double* mcc1, double* Epf, double* Ed, int64_t* counters,
+                                  char* best_seq, char* best_ss, double* best) {
+  using namespace drna_host;
+  const char* who = "drna_mc_run_ragged";
+  if (!e) return DRNA_ERR_ARG;
+  if (P < 1 || !R_of || !L_of || n_iter < 0 || !targets || !allowed_mask || !shelf_index || !n_shelves || !temps || n_terms < 1 ||
+      !term_id || !term_w || !rng_state || !seqs || !mfe_ss || !score || !mcc1 || !Epf || !Ed || !counters || !best_seq || !best_ss ||
+      !best) {
+    e->err = std::string(who) + ": bad argument (P >= 1; every per-puzzle and per-chain array given)";
+    return DRNA_ERR_ARG;
+  }
+  bool want_edef = false;
+  { const int rc = mc_terms(e, who, n_terms, term_id, &want_edef); if (rc != DRNA_OK) return rc; }
+  if (want_edef) { e->err = std::string(who) + ": scoring term 6 (Edef) is not available for a set of puzzles"; return DRNA_ERR_ARG; }
+  McChains ch;
+  ch.P = P; ch.best_vals = 4; ch.poff.resize(P);
+  size_t chars = 0, n_chains = 0;
+  for (int p = 0; p < P; p++) {
+    if (R_of[p] < 1 || L_of[p] < 1) { e->err = std::string(who) + ": puzzle " + std::to_string(p) + ": R_of < 1 or L_of < 1"; return DRNA_ERR_ARG; }
+    ch.poff[p] = chars;
+    chars += (size_t)L_of[p];
+    n_chains += (size_t)R_of[p];
+    ch.total += (size_t)R_of[p] * L_of[p];
+    ch.max_len = std::max(ch.max_len, (int)L_of[p]);
+  }
+  if (n_chains > (size_t)e->max_R) {
+    e->err = std::string(who) + ": " + std::to_string(n_chains) + " chains, more than max_R = " + std::to_string(e->max_R);
+    return DRNA_ERR_ARG;
+  }
+  if (ch.total > (size_t)e->max_R * e->max_L) {
+    e->err = std::string(who) + ": " + std::to_string(ch.total) + " nucleotides in all chains, more than max_R * max_L = " +
+             std::to_string((size_t)e->max_R * e->max_L);
+    return DRNA_ERR_ARG;
+  }
+  for (int p = 0; p < P; p++) {
+    if (L_of[p] > e->max_L) { e->err = std::string(who) + ": puzzle " + std::to_string(p) + ": L_of above max_L"; return DRNA_ERR_ARG; }
+    for (int i = 0; i < L_of[p]; i++) {
+      const char c = targets[ch.poff[p] + i];
+      if (c != '(' && c != ')' && c != '.') {
+        e->err = std::string(who) + ": puzzle " + std::to_string(p) + ": target holds '" + c + "' (one strand and the plain brackets ( ) . only)";
+        return DRNA_ERR_ARG;
+      }
+    }
+  }
+  const int C = (int)n_chains;
+  std::vector<ProposeCtx> ctx(P);
+  std::vector<int32_t> lens(C);
+  ch.of.resize(C); ch.len.resize(C); ch.off.resize(C);
+  {
+    size_t o = 0;
+    int r = 0;
+    for (int p = 0; p < P; p++) {
+      const int rc = propose_ctx_init(ctx[p], L_of[p], targets + ch.poff[p], nullptr, allowed_mask + ch.poff[p], nullptr, nullptr,
+                                      nullptr, nullptr, nullptr, n_shelves[p], tm_max, tm_min, targeted);
+      if (rc != DRNA_OK) {
+        e->err = std::string(who) + ": puzzle " + std::to_string(p) + (rc == DRNA_ERR_STRUCTURE ? ": unbalanced target structure" : ": proposal failed");
+        return rc;
+      }
+      for (int k = 0; k < R_of[p]; k++, r++) {
+        ch.of[r] = p; ch.len[r] = lens[r] = L_of[p]; ch.off[r] = o;
+        o += (size_t)L_of[p];
+      }
+    }
+  }
+  // the call's own targets: a set left from an earlier call (more puzzles, other structures) must not be evaluated against
+  { const int rc = drna_set_targets_ragged(e, P, L_of, targets); if (rc != DRNA_OK) return rc; }
+  RaggedPlan plan;
+  { const int rc = ragged_plan(e, C, lens.data(), ch.of.data(), flags | DRNA_NEED_PF | DRNA_NEED_MFE | DRNA_NEED_EVAL, plan); if (rc != DRNA_OK) return rc; }
+  McScored S;
+  S.ss.resize(ch.total); S.Epf.resize(C); S.ed.resize(C); S.Emfe.resize(C);
+  std::vector<int32_t> pEmfe(C), pEd(C);
+  auto score_all = [&](const char* prop) -> int {
+    const int rc = ragged_run(e, plan, prop, S.Epf.data(), pEmfe.data(), S.ss.data(), pEd.data());
+    if (rc != DRNA_OK) return rc;
+    for (int r = 0; r < C; r++) { S.ed[r] = pEd[r] / 100.0; S.Emfe[r] = pEmfe[r] / 100.0; }
+    return DRNA_OK;
+  };
+  auto metrics = [&](int r, const char* ss, int* pq, SimMetrics& m) {
+    if (!pair_table(ss, ch.len[r], pq)) return false;
+    m = sim_metrics(ctx[ch.of[r]].pt.data(), pq, ch.len[r]);
+    return true;
+  };
+  auto second_best = [](const char*, const int*, int) -> int { return DRNA_OK; };   // (no negative design here)
+  return mc_loop(e, who, ch, n_iter, ctx.data(), shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs,
+                 mfe_ss, score, mcc1, Epf, Ed, nullptr, nullptr, nullptr, counters, best_seq, best_ss, best, S, score_all, metrics,
+                 second_best);
 }

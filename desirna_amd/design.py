@@ -33,6 +33,11 @@ candidate folded against a copy of itself, ``Engine.self_dimer`` per iteration o
 
 Two strands (hetero-dimer, ``-d on`` homodimer) run through both drivers; together with alternative structures through
 ``run_design`` only.
+
+A set of puzzles (``--set a.txt b.txt ...``, ``run_puzzle_set(batched=True)``): the one-strand puzzles with plain brackets and
+no alternative structures advance in lock-step in ``run_puzzle_batch`` -- the per-puzzle state code of ``run_design_fast``
+(``_array_state`` and what follows it), one ragged scoring call per iteration for all of them (``Engine.mc_run_ragged``) --,
+the others one after the other.
 """
 import argparse
 import random
@@ -433,6 +438,96 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
             "simulation_data": run.simulation_data, "engine": getattr(scorer, "engine", None)}
 
 
+# ---- what run_design_fast and run_puzzle_batch share: one puzzle's replica state in arrays, and what an inner iteration or a
+# native call does to it.
+
+def _array_state(run, b, exchange, two=False, oa=False, nd=False):
+    """The replica state of one run: the arrays of the scored batch `b` (``energy_scores.score_arrays`` of the initial
+    sequence) that ``Engine.mc_run*`` holds, under its names; the best state; the records.  Calls ``_start``."""
+    Rl, local = len(run.local), np.array(run.local, dtype=np.int64)
+    keys = ["seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"] + ["oligo_fraction", "bonus"] * (two or oa) + ["subopt_e"] * nd
+    cur = SimpleNamespace(**{k: np.array(getattr(b, k), dtype=np.uint8 if k in keys[:2] else np.float64) for k in keys})
+    bonus_name = "monomer_bonus" if oa else "oligomer_bonus"
+    if oa:
+        cur.bonus_field = bonus_name                      # (energy_scores.record names the bonus of its records by it)
+    # fields of `best`; after the strings, in the order of mc_run's best["vals"] (esubopt_minus_Epf follows from them)
+    fields = (["sequence", "mfe_ss", "mcc", "scoring_function", "Epf", "edesired"] + ["oligo_fraction", bonus_name] * (two or oa)
+              + ["subopt_e", "esubopt_minus_Epf"] * nd)
+    st = SimpleNamespace(keys=keys, cur=cur, nd=nd, Rl=Rl, local=local, vals=[f for f in fields[2:] if f != "esubopt_minus_Epf"])
+
+    def best_of(k):
+        sc = es.record(cur, k)
+        return SimpleNamespace(**{f: getattr(sc, f) if f in fields[:2] else float(getattr(sc, f)) for f in fields})
+
+    def records():
+        out = []
+        for k in range(Rl):
+            sc = es.record(cur, k)
+            sc.get_replica_num(int(local[k]) + 1)
+            sc.get_temp_shelf(float(run.temps[local[k]]))
+            sc.get_sim_step(run.step * exchange)          # reference: stats.step = global_step * RE_attempt
+            out.append(dict(vars(sc)))
+        return out
+
+    st.best_of, st.records = best_of, records
+    st.best = best_of(int(np.lexsort((cur.score, cur.mcc1))[0]))
+    _start(run, cur.score[:Rl], st.best.mcc == 0.0, records)
+    return st
+
+
+def _step_ladder(run, st, hk, rng_state, shelves):
+    """Start of an exchange step: random.seed(replica index) for every local replica (App. C2) into `rng_state`; returns the
+    replicas' temperatures and shelf indices"""
+    hk.rng_seed(st.local if st.Rl else [0], out=rng_state)
+    tl = np.array(run.temps, dtype=np.float64)[st.local if st.Rl else [0]]
+    return tl, np.searchsorted(shelves, tl).astype(np.int32)
+
+
+def _native_best(st):
+    """`best` of ``Engine.mc_run*``: the best state going into a native call"""
+    return dict(seq=np.frombuffer(st.best.sequence.encode(), dtype=np.uint8).copy(),
+                ss=np.frombuffer(st.best.mfe_ss.encode(), dtype=np.uint8).copy(),
+                vals=np.array([getattr(st.best, f) for f in st.vals], dtype=np.float64))
+
+
+def _native_done(run, st, seq, ss, vals, counters, n_iter):
+    """... and what comes back from it: the best state, the three counters"""
+    st.best = SimpleNamespace(sequence=seq.tobytes().decode(), mfe_ss=ss.tobytes().decode(),
+                              **{f: float(v) for f, v in zip(st.vals, vals)})
+    if st.nd:
+        st.best.esubopt_minus_Epf = st.best.subopt_e - st.best.Epf if st.best.mcc == 0 else 0.0
+    stats = run.stats
+    stats["acc_mc"] += int(counters[0]); stats["acc_mc_better"] += int(counters[1]); stats["rej_mc"] += int(counters[2])
+    stats["scored"] += st.Rl * n_iter
+
+
+def _host_accept(run, st, p, acc, better):
+    """One iteration's Metropolis outcome on the state: the accepted candidates of the scored batch `p` replace their replicas"""
+    cur, stats = st.cur, run.stats
+    for k in st.keys:
+        getattr(cur, k)[acc] = getattr(p, k)[acc]
+    na = int(acc.sum())
+    stats["acc_mc"] += na
+    stats["acc_mc_better"] += int((acc & better).sum())
+    stats["rej_mc"] += st.Rl - na
+    stats["scored"] += st.Rl
+    # the best state is tracked replica by replica in replica order, like the native loop (first strictly better wins)
+    for kb in np.nonzero(acc)[0]:
+        if (cur.mcc1[kb], cur.score[kb]) < (st.best.mcc, st.best.scoring_function):
+            st.best = st.best_of(kb)
+
+
+def _array_exchange(run, st):
+    _exchange_step(run, st.cur.score[:st.Rl], bool(st.Rl) and bool((st.cur.mcc1[:st.Rl] == 0.0).any()), st.records)
+
+
+def _array_result(run, st, eng, native_loop):
+    best = _finish(run, st.best if st.Rl else None)
+    return {"best": best, "solved": run.solved, "stats": run.stats, "steps": run.step, "simulation_data": run.simulation_data,
+            "engine": eng, "temps": [float(t) for t in run.temps], "local": [int(r) for r in st.local],
+            "used_native_loop": bool(native_loop)}
+
+
 def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                     scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
                     device=0, engine=None, keep_records=True, native_loop=None, shards=None, num_results=None, dimer="off",
@@ -475,41 +570,13 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                  shards, dimer, oligo, keep_records=keep_records)
     prob, sf, oligo_state, nd = run.prob, run.opts.scoring_f, run.opts.oligo_state, negative_design == "on"
     oa = oligo_state == "avoid"
-    local = np.array(run.local, dtype=np.int64)
     R, L, Rl = replicas, prob.n, len(run.local)
     eng = engine or _engine.Engine(max_R=max(1, Rl), max_L=L - 1 if two else L, device=device)      # L counts the '&'
     hk = _engine.HostKernels()
     eng.set_targets([input_file.sec_struct.replace("&", "")] + list(input_file.alt_sec_structs or []))
     score = lambda seqs_u8: es.score_arrays(eng, hk, input_file.sec_struct, sf, seqs_u8, oligo_state, run.opts.pks, nd, self_dimer=oa)
-    # the replica state: the arrays of the scored batch that Engine.mc_run[_cofold] holds, under its names
-    b = score(np.tile(np.frombuffer(run.init.encode(), dtype=np.uint8), (max(1, Rl), 1)))
-    keys = ["seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"] + ["oligo_fraction", "bonus"] * (two or oa) + ["subopt_e"] * nd
-    cur = SimpleNamespace(**{k: np.array(getattr(b, k), dtype=np.uint8 if k in keys[:2] else np.float64) for k in keys})
-    bonus_name = "monomer_bonus" if oa else "oligomer_bonus"
-    if oa:
-        cur.bonus_field = bonus_name                      # (energy_scores.record names the bonus of its records by it)
-    # fields of `best`; after the strings, in the order of mc_run's best["vals"] (esubopt_minus_Epf follows from them)
-    fields = (["sequence", "mfe_ss", "mcc", "scoring_function", "Epf", "edesired"] + ["oligo_fraction", bonus_name] * (two or oa)
-              + ["subopt_e", "esubopt_minus_Epf"] * nd)
-    vals = [f for f in fields[2:] if f != "esubopt_minus_Epf"]
-
-    def best_of(k):
-        sc = es.record(cur, k)
-        return SimpleNamespace(**{f: getattr(sc, f) if f in fields[:2] else float(getattr(sc, f)) for f in fields})
-
-    def records():
-        out = []
-        for k in range(Rl):
-            sc = es.record(cur, k)
-            sc.get_replica_num(int(local[k]) + 1)
-            sc.get_temp_shelf(float(run.temps[local[k]]))
-            sc.get_sim_step(run.step * exchange)          # reference: stats.step = global_step * RE_attempt
-            out.append(dict(vars(sc)))
-        return out
-
-    best = best_of(int(np.lexsort((cur.score, cur.mcc1))[0]))
-    _start(run, cur.score[:Rl], best.mcc == 0.0, records)
-    stats = run.stats
+    st = _array_state(run, score(np.tile(np.frombuffer(run.init.encode(), dtype=np.uint8), (max(1, Rl), 1))), exchange, two, oa, nd)
+    cur = st.cur
     if native_loop is None:
         native_loop = True
     native_loop = native_loop and all(name in eng.TERM_IDS for name, _ in sf)   # (every -sf term, Edef included, has a native id)
@@ -518,28 +585,19 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
     shelves = np.array(run.shelves)
     targeted = point_mutations == "on"
     while _next_step(run):
-        hk.rng_seed(local if Rl else [0], out=rng_state)        # random.seed(replica index) at every exchange step (App. C2)
-        tl = np.array(run.temps, dtype=np.float64)[local if Rl else [0]]
-        shelf_idx = np.searchsorted(shelves, tl).astype(np.int32)
+        tl, shelf_idx = _step_ladder(run, st, hk, rng_state, shelves)
         if native_loop and Rl:
             # the whole inner loop of the exchange step in native code (drna_mc_run[_cofold]): one call, no per-iteration Python
             counters = np.zeros(3, dtype=np.int64)
             nd_kw = dict(subopt_e=cur.subopt_e) if nd else {}
-            bst = dict(seq=np.frombuffer(best.sequence.encode(), dtype=np.uint8).copy(),
-                       ss=np.frombuffer(best.mfe_ss.encode(), dtype=np.uint8).copy(),
-                       vals=np.array([getattr(best, f) for f in vals], dtype=np.float64))
+            bst = _native_best(st)
             if two:
                 eng.mc_run_cofold(prob, oligo_state, exchange, shelf_idx, R, tm_max, tm_min, targeted, tl, sf, rng_state, vars(cur),
                                   counters, bst, **nd_kw)
             else:
                 eng.mc_run(prob, exchange, shelf_idx, R, tm_max, tm_min, targeted, tl, sf, flags, rng_state, vars(cur), counters, bst,
                            **nd_kw, **(dict(self_dimer=True) if oa else {}))
-            best = SimpleNamespace(sequence=bst["seq"].tobytes().decode(), mfe_ss=bst["ss"].tobytes().decode(),
-                                   **{f: float(v) for f, v in zip(vals, bst["vals"])})
-            if nd:
-                best.esubopt_minus_Epf = best.subopt_e - best.Epf if best.mcc == 0 else 0.0
-            stats["acc_mc"] += int(counters[0]); stats["acc_mc_better"] += int(counters[1]); stats["rej_mc"] += int(counters[2])
-            stats["scored"] += Rl * exchange
+            _native_done(run, st, bst["seq"], bst["ss"], bst["vals"], counters, exchange)
         for _ in range(0 if (native_loop or not Rl) else exchange):
             if two:
                 prop = hk.propose_co(prob, oligo_state, cur.seqs, cur.mfe_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
@@ -547,44 +605,208 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                 prop = hk.propose_alt(prob, cur.seqs, cur.mfe_ss, shelf_idx, R, tm_max, tm_min, targeted, rng_state)
             p = score(prop)
             acc, better = hk.metropolis(cur.score, p.score, tl, rng_state)
-            for k in keys:
-                getattr(cur, k)[acc] = getattr(p, k)[acc]
-            na = int(acc.sum())
-            stats["acc_mc"] += na
-            stats["acc_mc_better"] += int((acc & better).sum())
-            stats["rej_mc"] += Rl - na
-            stats["scored"] += Rl
-            # the best state is tracked replica by replica in replica order, like the native loop (first strictly better wins)
-            for kb in np.nonzero(acc)[0]:
-                if (cur.mcc1[kb], cur.score[kb]) < (best.mcc, best.scoring_function):
-                    best = best_of(kb)
-        _exchange_step(run, cur.score[:Rl], bool(Rl) and bool((cur.mcc1[:Rl] == 0.0).any()), records)
-    best = _finish(run, best if Rl else None)
-    return {"best": best, "solved": run.solved, "stats": stats, "steps": run.step, "simulation_data": run.simulation_data,
-            "engine": eng, "temps": [float(t) for t in run.temps], "local": [int(r) for r in local],
-            "used_native_loop": bool(native_loop)}
+            _host_accept(run, st, p, acc, better)
+        _array_exchange(run, st)
+    return _array_result(run, st, eng, native_loop)
 
 
-def run_puzzle_set(inputs, rank=0, world=1, driver=None, **kw):
+class _RaggedSlice:
+    """One puzzle's part of a ragged scoring call, as the engine ``energy_scores.score_arrays`` asks: the -sf sum stays there"""
+
+    def __init__(self, Epf, Emfe, ss, Ed):
+        self.out = (Epf, Emfe, ss, Ed.reshape(-1, 1))
+
+    def score_batch_arrays(self, seqs_u8, flags=0):
+        return self.out
+
+
+def batch_eligible(input_file, scoring_f="Ed-Epf:1.0", negative_design="off", oligo="off", subopt="off", acgu=None, **_):
+    """Can this input run in :func:`run_puzzle_batch` under these driver keywords?  One strand, the brackets ``( ) .`` only, no
+    alternative structures; -nd, -oa and -acgu off; no Edef term."""
+    return (set(input_file.sec_struct) <= set("().") and not input_file.alt_sec_structs and negative_design == "off"
+            and oligo == "off" and subopt == "off" and acgu is None
+            and all(name != "Edef" for name, _ in es.parse_scoring_functions(scoring_f)))
+
+
+def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
+                     scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
+                     device=0, engine=None, keep_records=True, native_loop=None, num_results=None, dimer="off",
+                     negative_design="off", oligo="off"):
+    """:func:`run_design_fast` for a SET of puzzles of different lengths on one engine, all advancing in lock-step: per
+    iteration the chains of every puzzle still running are scored by ONE ragged call (``Engine.mc_run_ragged`` runs the whole
+    exchange step; with ``native_loop=False`` per iteration ``HostKernels.propose_alt`` per puzzle, one
+    ``Engine.score_ragged_arrays`` call, ``HostKernels.metropolis`` per puzzle).  Returns one result dict per input, in input
+    order, with :func:`run_design_fast`'s keys.
+
+    Every puzzle is a run of its own -- main stream, temperature ladder, replica streams, records, exchange step and stop rule
+    are those of :func:`run_design_fast` --, and the kernels' results do not depend on the batch composition: for the same
+    keywords a puzzle's records, counters and best are those of its run alone.  A puzzle whose run stops (its step count,
+    ``stop_when_solved``, the ``-sws`` rule) leaves the batch; the next call holds fewer chains.
+
+    Lock-step ties every puzzle to the pace of the longest one still running.  ``timelimit``: every run's clock starts when the
+    SET starts, so the limit bounds the whole set, not each puzzle in turn; ``steps`` is the deterministic mode.
+
+    Inputs must pass :func:`batch_eligible` (one strand, ``( ) .``, no alternative structures, ``-nd`` / ``-oa`` off, no Edef
+    term): the ragged evaluation holds one structure per sequence and the loop has no second-best or self-dimer step.  The
+    engine needs ``max_R`` = the sum of all replicas and ``max_L`` = the longest puzzle.  No replica sharding here."""
+    from . import engine as _engine
+    if stop_when_solved and num_results is not None and not keep_records:
+        raise ValueError("the -sws rule with num_results ranks the recorded sequences: it needs keep_records=True")
+    bad = [i.name for i in inputs if not batch_eligible(i, scoring_f, negative_design, oligo)]
+    if bad:
+        raise ValueError("not a puzzle for the lock-step batch (one strand, brackets ( ) . only, no alternative structures, "
+                         "-nd / -oa off, no Edef term): %s" % ", ".join(bad))
+    if not inputs:
+        return []
+    es.check_scoring_functions(es.parse_scoring_functions(scoring_f))
+    runs = [_setup(i, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results, None, dimer,
+                   oligo, keep_records=keep_records) for i in inputs]
+    P, R, sf = len(inputs), replicas, runs[0].opts.scoring_f
+    eng = engine or _engine.Engine(max_R=P * R, max_L=max(r.prob.n for r in runs), device=device)
+    hk = _engine.HostKernels()
+    flags = _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL
+
+    def score_all(act, seqs):
+        """one ragged call over the (R, L_i) candidates `seqs` of the puzzles `act` -> their score_arrays batches"""
+        flat = np.concatenate([s.ravel() for s in seqs])
+        Epf, Emfe, ss, Ed = eng.score_ragged_arrays(flat, np.repeat([runs[i].prob.n for i in act], R),
+                                                    np.repeat(np.array(act, dtype=np.int32), R), flags)
+        out, o = [], 0
+        for k, (i, s) in enumerate(zip(act, seqs)):
+            n = R * runs[i].prob.n
+            part = _RaggedSlice(Epf[k * R:(k + 1) * R], Emfe[k * R:(k + 1) * R], ss[o:o + n].reshape(R, -1), Ed[k * R:(k + 1) * R])
+            out.append(es.score_arrays(part, hk, inputs[i].sec_struct, sf, s, "none", "off"))
+            o += n
+        return out
+
+    eng.set_targets_ragged([i.sec_struct for i in inputs])      # target_of = the input's index, whatever the active set
+    init = score_all(list(range(P)), [np.tile(np.frombuffer(r.init.encode(), dtype=np.uint8), (R, 1)) for r in runs])
+    sts = [_array_state(run, b, exchange) for run, b in zip(runs, init)]
+    t0 = time.time()
+    for run in runs:
+        run.t_start = t0                                        # one clock for the set
+    if native_loop is None:
+        native_loop = True
+    native_loop = bool(native_loop and hasattr(eng, "mc_run_ragged") and all(name in eng.TERM_IDS for name, _ in sf))
+    rng_state = np.empty((P * R, _engine.RNG_WORDS), dtype=np.uint32)
+    targeted = point_mutations == "on"
+    act = list(range(P))
+    while True:
+        act = [i for i in act if _next_step(runs[i])]           # who stopped has left the batch
+        if not act:
+            break
+        A = len(act)
+        lad = [_step_ladder(runs[i], sts[i], hk, rng_state[k * R:(k + 1) * R], np.array(runs[i].shelves)) for k, i in enumerate(act)]
+        if native_loop:
+            # the whole exchange step of every active puzzle in ONE native call (drna_mc_run_ragged)
+            state = {k: np.concatenate([getattr(sts[i].cur, k).ravel() for i in act]) for k in sts[0].keys}
+            bsts = [_native_best(sts[i]) for i in act]
+            best = {k: np.concatenate([b[k] for b in bsts]) for k in ("seq", "ss")}
+            best["vals"] = np.stack([b["vals"] for b in bsts])
+            counters = np.zeros((A, 3), dtype=np.int64)
+            eng.mc_run_ragged([runs[i].prob for i in act], exchange, np.concatenate([l[1] for l in lad]), [R] * A, tm_max, tm_min,
+                              targeted, np.concatenate([l[0] for l in lad]), sf, flags, rng_state[:A * R], state, counters, best)
+            o = ob = 0
+            for k, i in enumerate(act):
+                n, cur = runs[i].prob.n, sts[i].cur
+                for key in sts[i].keys:
+                    a = state[key]
+                    getattr(cur, key)[...] = a[o:o + R * n].reshape(R, n) if key in ("seqs", "mfe_ss") else a[k * R:(k + 1) * R]
+                _native_done(runs[i], sts[i], best["seq"][ob:ob + n], best["ss"][ob:ob + n], best["vals"][k], counters[k], exchange)
+                o += R * n
+                ob += n
+        for _ in range(0 if native_loop else exchange):
+            props = [hk.propose_alt(runs[i].prob, sts[i].cur.seqs, sts[i].cur.mfe_ss, lad[k][1], R, tm_max, tm_min, targeted,
+                                    rng_state[k * R:(k + 1) * R]) for k, i in enumerate(act)]
+            for k, (i, p) in enumerate(zip(act, score_all(act, props))):
+                acc, better = hk.metropolis(sts[i].cur.score, p.score, lad[k][0], rng_state[k * R:(k + 1) * R])
+                _host_accept(runs[i], sts[i], p, acc, better)
+        for i in act:
+            _array_exchange(runs[i], sts[i])
+    return [_array_result(run, st, eng, native_loop) for run, st in zip(runs, sts)]
+
+
+def run_puzzle_set(inputs, rank=0, world=1, driver=None, batched=False, on_result=None, **kw):
     """Design every problem of `inputs` (BASELINE config 4), the set sharded over `world` ranks by sum n^3
     (``replica_exchange.shard_puzzles``): each rank runs its own puzzles with all their replicas on its GPU and the
-    results are gathered once at the end.  Returns {index: dict(name, solved, sequence, mfe_ss, score)} on every rank."""
+    results are gathered once at the end.  Returns {index: dict(name, solved, sequence, mfe_ss, score)} on every rank.
+
+    ``batched=True``: the rank's puzzles that pass :func:`batch_eligible` under `kw` advance together in ONE
+    :func:`run_puzzle_batch` (lock-step, one ragged scoring call per iteration); the others (two strands, alternative
+    structures, pseudoknot brackets, -nd / -oa / -acgu on, an Edef term) go through `driver` one after the other as without it.
+    ``on_result(index, input, result)`` is called with every full result of this rank (the CLI writes its files there)."""
     driver = driver or run_design_fast
     owner = rx.shard_puzzles([len(i.sec_struct) for i in inputs], world)
+    own = [k for k in range(len(inputs)) if owner[k] == rank]
+    together = [k for k in own if batched and batch_eligible(inputs[k], **kw)]
+    results = dict(zip(together, run_puzzle_batch([inputs[k] for k in together], **kw))) if together else {}
     mine = {}
-    for k, inp in enumerate(inputs):
-        if owner[k] != rank:
-            continue
-        res = driver(inp, **kw)
+    for k in own:
+        inp = inputs[k]
+        res = results[k] if k in results else driver(inp, **kw)
+        if on_result:
+            on_result(k, inp, res)
         b = res["best"]
         mine[k] = dict(name=inp.name, solved=bool(res["solved"]), sequence=b.sequence, mfe_ss=b.mfe_ss,
                        score=float(b.scoring_function), rank=rank)
     return rx.gather_results(mine, world)
 
 
+def _cli_driver(a, inp):
+    """(driver, its keywords beyond the common ones) for one input under the command line `a`: the Python driver has -acgu and
+    two strands together with alternative structures for itself"""
+    strands2 = "&" in inp.sec_struct
+    two = a.percs == "on" or (strands2 and bool(inp.alt_sec_structs))
+    python_host = a.python_host or two
+    if python_host:
+        extra = dict(dimer=a.dimer, oligo=a.oligo, subopt=a.subopt) if (two or strands2 or a.subopt == "on" or a.oligo == "on") else {}
+    else:
+        extra = dict(dimer=a.dimer) if strands2 else {}
+        if a.subopt == "on":
+            extra["negative_design"] = "on"
+        if a.oligo == "on":
+            extra["oligo"] = "on"
+    if a.percs == "on":
+        vals = [int(x) for x in a.acgu_content.split(",")] if a.acgu_content else [15, 30, 30, 15]
+        if sum(vals) != 100:
+            raise SystemExit("The ACGU content should sum up to 100, check your command.")
+        extra["acgu"] = dict(zip("ACGU", vals))
+    return (run_design if python_host else run_design_fast), extra
+
+
+def _cli_report(a, filename, inp, res):
+    """What the command line leaves of one finished design: with -o the reference's result files, and the summary lines"""
+    if a.outdir:
+        import os
+        from . import outputs
+        os.makedirs(a.outdir, exist_ok=True)
+        sf = es.parse_scoring_functions(a.scoring_f)
+        oligo_state, pks = oligo_state_and_pks(inp.sec_struct, a.dimer, a.oligo)
+        outname = outputs.get_outname(os.path.basename(filename), a.replicas, a.exchange, a.timlim, pks, "off", a.t_min, a.t_max,
+                                      "1999", sf, "off", "off", a.pm)
+        st = res["stats"]
+        stats = SimpleNamespace(step=st["acc_mc"] + st["rej_mc"], global_step=res["steps"], acc_mc_step=st["acc_mc"],
+                                acc_mc_better_e=st["acc_mc_better"], rej_mc_step=st["rej_mc"], acc_re_step=st["acc_re"],
+                                rej_re_step=st["rej_re"])
+        outputs.write_all(res["simulation_data"], inp.name, os.path.basename(filename), outname, stats, st["elapsed_s"], a.timlim,
+                          time.strftime("%Y%m%d.%H%M%S"), num_results=a.num_results, directory=a.outdir,
+                          alt_sec_structs=list(inp.alt_sec_structs or []) or None, engine=res.get("engine"),
+                          oligo_state=oligo_state, subopt=a.subopt, sec_struct=inp.sec_struct)
+    b = res["best"]
+    print("Design solved succesfully!" if res["solved"] else "Design not solved.")
+    print(b.sequence)
+    print(b.mfe_ss)
+    print("Epf=%.3f Ed=%.3f 1-MCC=%.3f score=%.3f  steps=%d scored=%d in %.1fs" %
+          (b.Epf, b.edesired, b.mcc, b.scoring_function, res["steps"], res["stats"]["scored"], res["stats"]["elapsed_s"]))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="GPU replica-exchange RNA design (flag names follow DesiRNA.py)")
-    ap.add_argument("-f", "--filename", required=True, dest="name")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("-f", "--filename", dest="name")
+    src.add_argument("--set", nargs="+", dest="set_files", metavar="FILE", help="design all these inputs as one set: the puzzles "
+                     "that allow it (one strand, ( ) . only, no alternative structures, -nd / -oa / -acgu off) advance in lock-step on "
+                     "one engine, the others one after the other")
     ap.add_argument("-R", "--replicas", type=int, default=10)
     ap.add_argument("-e", "--exchange", type=int, default=100)
     ap.add_argument("-t", "--timelimit", type=int, default=60, dest="timlim")
@@ -607,49 +829,25 @@ def main(argv=None):
     ap.add_argument("-o", "--outdir", default=None, help="write the reference's result files (_results.csv, _traj.csv, "
                     "_stats, _best_str, fasta files) into this directory")
     a = ap.parse_args(argv)
+    common = dict(replicas=a.replicas, exchange=a.exchange, steps=a.steps, timelimit=a.timlim, t_min=a.t_min, t_max=a.t_max,
+                  scoring_f=a.scoring_f, tm_max=a.tm_max, tm_min=a.tm_min, point_mutations=a.pm, seed=a.in_seed,
+                  stop_when_solved=a.sws == "on", num_results=a.num_results if a.sws == "on" else None)
+    if a.set_files:
+        inputs = [read_input(f) for f in a.set_files]
+        # the switches under run_design_fast's names, so that run_puzzle_set can tell which inputs may share the batch; the
+        # per-puzzle driver gets each input's own keywords (_cli_driver)
+        switches = dict(negative_design=a.subopt, oligo=a.oligo, **(dict(acgu=True) if a.percs == "on" or a.python_host else {}))
+
+        def driver(inp, negative_design="off", oligo="off", acgu=None, **kw):
+            drv, extra = _cli_driver(a, inp)
+            return drv(inp, **extra, **kw)
+
+        run_puzzle_set(inputs, driver=driver, batched=True, **common, **switches,
+                       on_result=lambda k, inp, res: _cli_report(a, a.set_files[k], inp, res))
+        return
     inp = read_input(a.name)
-    strands2 = "&" in inp.sec_struct
-    # the Python driver's own features: -acgu, and two strands together with alternative structures
-    two = a.percs == "on" or (strands2 and bool(inp.alt_sec_structs))
-    python_host = a.python_host or two
-    if python_host:
-        extra = dict(dimer=a.dimer, oligo=a.oligo, subopt=a.subopt) if (two or strands2 or a.subopt == "on" or a.oligo == "on") else {}
-    else:
-        extra = dict(dimer=a.dimer) if strands2 else {}
-        if a.subopt == "on":
-            extra["negative_design"] = "on"
-        if a.oligo == "on":
-            extra["oligo"] = "on"
-    if a.percs == "on":
-        vals = [int(x) for x in a.acgu_content.split(",")] if a.acgu_content else [15, 30, 30, 15]
-        if sum(vals) != 100:
-            raise SystemExit("The ACGU content should sum up to 100, check your command.")
-        extra["acgu"] = dict(zip("ACGU", vals))
-    res = (run_design if python_host else run_design_fast)(inp, **extra, replicas=a.replicas, exchange=a.exchange, steps=a.steps, timelimit=a.timlim, t_min=a.t_min,
-                     t_max=a.t_max, scoring_f=a.scoring_f, tm_max=a.tm_max, tm_min=a.tm_min, point_mutations=a.pm,
-                     seed=a.in_seed, stop_when_solved=a.sws == "on", num_results=a.num_results if a.sws == "on" else None)
-    if a.outdir:
-        import os
-        from . import outputs
-        os.makedirs(a.outdir, exist_ok=True)
-        sf = es.parse_scoring_functions(a.scoring_f)
-        oligo_state, pks = oligo_state_and_pks(inp.sec_struct, a.dimer, a.oligo)
-        outname = outputs.get_outname(os.path.basename(a.name), a.replicas, a.exchange, a.timlim, pks, "off", a.t_min, a.t_max,
-                                      "1999", sf, "off", "off", a.pm)
-        st = res["stats"]
-        stats = SimpleNamespace(step=st["acc_mc"] + st["rej_mc"], global_step=res["steps"], acc_mc_step=st["acc_mc"],
-                                acc_mc_better_e=st["acc_mc_better"], rej_mc_step=st["rej_mc"], acc_re_step=st["acc_re"],
-                                rej_re_step=st["rej_re"])
-        outputs.write_all(res["simulation_data"], inp.name, os.path.basename(a.name), outname, stats, st["elapsed_s"], a.timlim,
-                          time.strftime("%Y%m%d.%H%M%S"), num_results=a.num_results, directory=a.outdir,
-                          alt_sec_structs=list(inp.alt_sec_structs or []) or None, engine=res.get("engine"),
-                          oligo_state=oligo_state, subopt=a.subopt, sec_struct=inp.sec_struct)
-    b = res["best"]
-    print("Design solved succesfully!" if res["solved"] else "Design not solved.")
-    print(b.sequence)
-    print(b.mfe_ss)
-    print("Epf=%.3f Ed=%.3f 1-MCC=%.3f score=%.3f  steps=%d scored=%d in %.1fs" %
-          (b.Epf, b.edesired, b.mcc, b.scoring_function, res["steps"], res["stats"]["scored"], res["stats"]["elapsed_s"]))
+    drv, extra = _cli_driver(a, inp)
+    _cli_report(a, a.name, inp, drv(inp, **extra, **common))
 
 
 if __name__ == "__main__":

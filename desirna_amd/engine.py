@@ -65,6 +65,8 @@ _SIGNATURES = {
     "drna_self_dimer_batch": (_ci, [_vp, _ci, _ci, _str, _vp, _vp]),
     "drna_mc_run_oa": (_ci, [_vp, _ci, _ci, _ci, _str, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _dbl, _dbl, _ci, _vp,
                              _dbl, _ci, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drna_mc_run_ragged": (_ci, [_vp, _ci, _vp, _vp, _ci, _str, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _dbl, _ci, _vp, _vp, _u32, _vp,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "drna_rng_seed": (_ci, [_ci, _vp, _vp]),
     "drna_rng_random": (_ci, [_ci, _vp, _vp]),
 }
@@ -243,28 +245,41 @@ class Engine:
         self.n_ragged_targets = len(structures)
 
     def score_ragged(self, seqs, target_of=None, flags=NEED_PF | NEED_MFE | NEED_EVAL):
-        """Sequences of DIFFERENT lengths in one call (BASELINE config 4: many puzzles x replicas).  target_of[r] is the index
-        (into :meth:`set_targets_ragged`) of the structure sequence r is evaluated on.  Returns dict(Epf, Emfe, mfe_ss, Ed[R])."""
-        R = len(seqs)
+        """String form of :meth:`score_ragged_arrays`: sequences of DIFFERENT lengths in one call (BASELINE config 4: many
+        puzzles x replicas).  target_of[r] is the index (into :meth:`set_targets_ragged`) of the structure sequence r is
+        evaluated on.  Returns dict(Epf, Emfe, mfe_ss, Ed[R])."""
         lens = np.array([len(s) for s in seqs], dtype=np.int32)
-        total = int(lens.sum())
+        Epf, Emfe, ss, Ed = self.score_ragged_arrays(np.frombuffer("".join(seqs).encode("ascii"), dtype=np.uint8), lens, target_of, flags)
+        out_ss = None
+        if ss is not None:
+            b = ss.tobytes().decode("ascii")
+            offs = np.concatenate(([0], np.cumsum(lens)))
+            out_ss = [b[offs[k]:offs[k + 1]] for k in range(len(lens))]
+        return {"Epf": Epf, "Emfe": Emfe, "mfe_ss": out_ss, "Ed": Ed}
+
+    def score_ragged_arrays(self, flat_u8, lens, target_of=None, flags=NEED_PF | NEED_MFE | NEED_EVAL):
+        """Array form for hot host loops: flat_u8 holds the letters of all sequences back to back (uint8, sum(lens)), lens their
+        lengths.  Returns (Epf float64[R], Emfe int32[R], mfe_ss uint8[sum(lens)] laid out like flat_u8, Ed int32[R]); None for
+        what `flags` does not ask for (Ed also without target_of)."""
+        flat_u8 = np.ascontiguousarray(flat_u8, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        R, total = len(lens), int(lens.sum())
+        if flat_u8.shape != (total,):
+            raise ValueError("flat_u8 must hold sum(lens) letters")
         if target_of is None:
             flags &= ~NEED_EVAL
         tof = np.ascontiguousarray(target_of, dtype=np.int32) if target_of is not None else None
+        if tof is not None and tof.shape != (R,):
+            raise ValueError("target_of must name one structure per sequence")
         Epf = np.zeros(R, dtype=np.float64) if flags & NEED_PF else None
         want_mfe = flags & (NEED_MFE | NEED_PK)
         Emfe = np.zeros(R, dtype=np.int32) if want_mfe else None
         ss = np.zeros(total, dtype=np.uint8) if want_mfe else None
         Ed = np.zeros(R, dtype=np.int32) if flags & NEED_EVAL else None
         ptr = lambda a: a.ctypes.data if a is not None else None
-        self._check(self._L.drna_score_ragged(self._h, R, lens.ctypes.data, "".join(seqs).encode("ascii"), ptr(tof), flags,
+        self._check(self._L.drna_score_ragged(self._h, R, lens.ctypes.data, flat_u8.ctypes.data_as(C.c_char_p), ptr(tof), flags,
                                               ptr(Epf), ptr(Emfe), ptr(ss), ptr(Ed)))
-        out_ss = None
-        if ss is not None:
-            b = ss.tobytes().decode("ascii")
-            offs = np.concatenate(([0], np.cumsum(lens)))
-            out_ss = [b[offs[k]:offs[k + 1]] for k in range(R)]
-        return {"Epf": Epf, "Emfe": Emfe, "mfe_ss": out_ss, "Ed": Ed}
+        return Epf, Emfe, ss, Ed
 
     def cofold_batch(self, seqs, flags=NEED_PF | NEED_MFE | NEED_EVAL):
         """Two-strand scoring: seqs are 'AAAA&BBBB' strings with the same strand lengths.  Returns dict(FA, FB, FcAB, FAB
@@ -330,6 +345,44 @@ class Engine:
         self._mc_run("drna_mc_run", head, [int(flags)], ("seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"), 6 if self_dimer else 4,
                      shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state, state, counters, best, L_const,
                      subopt_e, oa=bool(self_dimer))
+
+    def mc_run_ragged(self, probs, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, flags, rng_state, state,
+                      counters, best, L_const=504.12, R_of=None):
+        """:meth:`mc_run` for a set of one-strand ``design.DesignProblem`` s of different lengths, all chains advanced together
+        (drna_mc_run_ragged): one ragged scoring call per iteration.  Chains are ordered puzzle after puzzle, puzzle p owning
+        ``R_of[p]`` of them (default: ``n_shelves[p]``, a full temperature ladder per puzzle).  `state` holds :meth:`mc_run`'s
+        arrays flat: seqs, mfe_ss (uint8, chain after chain), score, mcc1, Epf, Ed (float64 C); shelf_index, temps and rng_state
+        have one entry per chain, n_shelves one per puzzle; `counters` is (P, 3); `best` holds seq, ss (uint8, puzzle after
+        puzzle) and vals (P, 4).  The call replaces the engine's ragged target set (:meth:`set_targets_ragged`) by the
+        puzzles' targets.  Plain ``( ) .`` targets only, no Edef term."""
+        P = len(probs)
+        ns = np.ascontiguousarray(n_shelves, dtype=np.int32)
+        R_of = np.ascontiguousarray(ns if R_of is None else R_of, dtype=np.int32)
+        L_of = np.array([p.n for p in probs], dtype=np.int32)
+        C_, chars, letters = int(R_of.sum()), int(L_of.sum()), int((R_of.astype(np.int64) * L_of).sum())
+        assert ns.shape == (P,) and R_of.shape == (P,)
+        _check_rng(rng_state, C_)
+        for k in ("seqs", "mfe_ss"):
+            assert state[k].dtype == np.uint8 and state[k].shape == (letters,) and state[k].flags.c_contiguous, k
+        for k in ("score", "mcc1", "Epf", "Ed"):
+            assert state[k].dtype == np.float64 and state[k].shape == (C_,) and state[k].flags.c_contiguous, k
+        assert counters.dtype == np.int64 and counters.shape == (P, 3) and counters.flags.c_contiguous
+        assert best["vals"].dtype == np.float64 and best["vals"].shape == (P, 4) and best["vals"].flags.c_contiguous
+        for k in ("seq", "ss"):
+            assert best[k].dtype == np.uint8 and best[k].shape == (chars,) and best[k].flags.c_contiguous, k
+        ids = np.array([self.TERM_IDS[n] for n, _ in scoring_f], dtype=np.int32)
+        ws = np.array([w for _, w in scoring_f], dtype=np.float64)
+        sh = np.ascontiguousarray(shelf_index, dtype=np.int32)
+        tt = np.ascontiguousarray(temps, dtype=np.float64)
+        assert sh.shape == (C_,) and tt.shape == (C_,)
+        am = np.concatenate([_packed(q)[0] for q in probs]).astype(np.uint8)
+        p = lambda a: a.ctypes.data
+        self._check(self._L.drna_mc_run_ragged(
+            self._h, P, p(R_of), p(L_of), int(n_iter), "".join(q.sec_struct for q in probs).encode("ascii"), p(am), p(sh), p(ns),
+            float(tm_max), float(tm_min), int(bool(targeted)), p(tt), float(L_const), len(ids), p(ids), p(ws), int(flags), p(rng_state),
+            *[p(state[k]) for k in ("seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed")], p(counters), p(best["seq"]), p(best["ss"]),
+            p(best["vals"])))
+        self.n_ragged_targets = P
 
     def mc_run_cofold(self, prob, oligo_state, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state,
                       state, counters, best, L_const=504.12, subopt_e=None):

@@ -439,6 +439,32 @@ int drna_mc_run_oa(drna_engine *e, int R, int L, int n_iter, const char *target,
                    int64_t *counters, char *best_seq, char *best_ss, double *best, double *subopt_e, double *oligo_frac,
                    double *bonus);
 
+/*
+ * drna_mc_run_ragged: drna_mc_run for a SET of P design problems of different lengths (BASELINE config 4 as a design run),
+ * all advanced together for n_iter iterations: per iteration one proposal per chain, ONE ragged scoring of all chains
+ * (drna_score_ragged rules: sequences of every length side by side, one workgroup per fold or strips above 200 nt), then the
+ * Metropolis draws in chain order.  Per chain the draws, scores and results are those of drna_mc_run on that puzzle alone;
+ * the pace is that of the longest puzzle in the call.
+ * Chains are ordered puzzle after puzzle: puzzle p owns R_of[p] chains of L_of[p] letters, C = sum R_of[p] chains in all.
+ *   per puzzle   targets, allowed_mask: concatenated, sum L_of[p] chars / bytes;  n_shelves: P ints;
+ *                counters: 3 per puzzle;  best_seq, best_ss: concatenated like the targets;  best: 4 per puzzle
+ *   per chain    shelf_index, temps, score, mcc1, Epf, Ed: C values;  rng_state: C * DRNA_RNG_WORDS;
+ *                seqs, mfe_ss: concatenated chain after chain (sum R_of[p] * L_of[p] chars)
+ *   shared       n_iter, tm_max, tm_min, targeted, Lconst, the -sf terms and weights, flags: as in drna_mc_run
+ * The call installs the P targets itself, as drna_set_targets_ragged(e, P, L_of, targets) does: it REPLACES the engine's ragged
+ * target set (a caller that scores with drna_score_ragged afterwards installs its own set again).  The set of puzzles usually
+ * shrinks from call to call of a run, and a set left from an earlier call would be evaluated against the wrong structures.
+ * Scope: one strand and the plain brackets ( ) . only (a target with '&' or another bracket family is DRNA_ERR_ARG); no
+ * alternative structures, no negative-design and no self-dimer step; -sf terms 0 .. 5, sln_Epf with the chain's own length
+ * (term 6, Edef, is DRNA_ERR_ARG).  Limits, as for drna_score_ragged: C <= max_R and sum R_of[p] * L_of[p] <= max_R * max_L.
+ * A new symbol: no existing signature changes, DRNA_ABI_VERSION stays 3.
+ */
+int drna_mc_run_ragged(drna_engine *e, int P, const int32_t *R_of, const int32_t *L_of, int n_iter, const char *targets,
+                       const unsigned char *allowed_mask, const int32_t *shelf_index, const int32_t *n_shelves, double tm_max,
+                       double tm_min, int targeted, const double *temps, double Lconst, int n_terms, const int32_t *term_id,
+                       const double *term_w, uint32_t flags, uint32_t *rng_state, char *seqs, char *mfe_ss, double *score,
+                       double *mcc1, double *Epf, double *Ed, int64_t *counters, char *best_seq, char *best_ss, double *best);
+
 #ifdef __cplusplus
 }
 #endif

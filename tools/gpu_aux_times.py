@@ -1,5 +1,6 @@
 """GPU box: device times of the auxiliary paths, one JSON line with a section per path (all, or those named as arguments).
-Per shape the first round warms up and the median of the others is kept."""
+Per shape the first round warms up and the median of the others is kept.
+`puzzle_set` (only when named; minutes): the Eterna100 set as a design run, lock-step batch against one puzzle after the other."""
 import json
 import os
 import sys
@@ -219,8 +220,92 @@ def section_inputs(name):
         yield "R%d_" % R + ("L%d" % lens[0] if len(lens) == 1 else "%d+%d" % tuple(lens)), R, sum(lens), seqs
 
 
-def main(names):
+PS_REPLICAS, PS_EXCHANGE, PS_STEPS, PS_SEED = 32, 10, 5, 5          # one warm-up exchange step + four timed ones
+
+
+def _step_times(eng, method, run):
+    """wall seconds of every exchange step of run(): from one call of the engine's native loop `method` to the next (so the
+    step's Python work -- ladder, exchange, records -- counts), the last one to the end of the run"""
+    starts, inner = [], getattr(eng, method)
+
+    def timed(*a, **kw):
+        starts.append(time.perf_counter())
+        return inner(*a, **kw)
+
+    setattr(eng, method, timed)
+    try:
+        run()
+    finally:
+        delattr(eng, method)
+    starts.append(time.perf_counter())
+    return np.diff(starts)
+
+
+def _puzzle_inputs():
+    import csv
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "eterna_v1_targets.csv")
+    return [SimpleNamespace(name=r["name"], sec_struct=r["structure"], seq_restr="N" * len(r["structure"]), seed_seq=None,
+                            alt_sec_struct=None, alt_sec_structs=None) for r in csv.DictReader(open(path))]
+
+
+def _lockstep(inputs):
+    """median wall ms of an exchange step of run_puzzle_batch over `inputs` (the first step warms up)"""
+    from desirna_amd import design
+    eng = E.Engine(max_R=len(inputs) * PS_REPLICAS, max_L=max(len(i.sec_struct) for i in inputs), device=0)
+    kw = dict(replicas=PS_REPLICAS, exchange=PS_EXCHANGE, steps=PS_STEPS, seed=PS_SEED, timelimit=36000, engine=eng)
+    d = _step_times(eng, "mc_run_ragged", lambda: design.run_puzzle_batch(inputs, **kw))
+    eng.close()
+    assert len(d) == PS_STEPS
+    return float(np.median(d[1:])) * 1e3
+
+
+def puzzle_set():
+    """BASELINE config 4 as a design run: the 100 Eterna100 targets x 32 replicas, exchange = 10, fixed seed.  (a) lock-step,
+    run_puzzle_batch; (b) today's path, run_design_fast one puzzle after the other on an engine of the puzzle's size, summed.
+    Same process, same visit; the same pair for the puzzles of at most 200 nt.  The host split of the lock-step run comes from
+    a child process with DRNA_MC_PROFILE set (its stderr lines, averaged over the calls after the first)."""
+    import re
+    import subprocess
+    from desirna_amd import design
+    inputs = _puzzle_inputs()
+    short = [i for i in inputs if len(i.sec_struct) <= 200]
+    per = {}
+    for inp in inputs:
+        eng = E.Engine(max_R=PS_REPLICAS, max_L=len(inp.sec_struct), device=0)
+        kw = dict(replicas=PS_REPLICAS, exchange=PS_EXCHANGE, steps=PS_STEPS, seed=PS_SEED, timelimit=36000, engine=eng)
+        d = _step_times(eng, "mc_run", lambda: design.run_design_fast(inp, **kw))
+        eng.close()
+        assert len(d) == PS_STEPS
+        per[inp.name] = float(np.median(d[1:])) * 1e3
     out = {}
+    for key, sub in (("all", inputs), ("le200", short)):
+        lock, one_by_one = _lockstep(sub), sum(per[i.name] for i in sub)
+        chains = len(sub) * PS_REPLICAS
+        out[key] = {"puzzles": len(sub), "chains": chains, "lockstep_step_ms": lock, "per_puzzle_sum_step_ms": one_by_one,
+                    "lockstep_over_per_puzzle": lock / one_by_one,
+                    "lockstep_chain_iters_per_s": chains * PS_EXCHANGE / (lock * 1e-3),
+                    "per_puzzle_chain_iters_per_s": chains * PS_EXCHANGE / (one_by_one * 1e-3)}
+    child = subprocess.run([sys.executable, os.path.abspath(__file__), "puzzle_set_profile"], env=dict(os.environ, DRNA_MC_PROFILE="1"),
+                           stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True, check=True)
+    rows = re.findall(r"drna_mc_run_ragged: per iteration, host us: score call beyond device time ([-0-9.]+), per-replica work ([-0-9.]+), "
+                      r"bookkeeping ([-0-9.]+)", child.stderr)
+    rows = np.array(rows[1:], dtype=np.float64)
+    out["all"]["host_us_per_iteration"] = dict(zip(("score_call_beyond_device", "per_chain_work", "bookkeeping"),
+                                                   (float(x) for x in np.median(rows, axis=0))))
+    return out
+
+
+def main(names):
+    if names == ["puzzle_set_profile"]:                      # the child of puzzle_set: the lock-step run alone, profile lines on stderr
+        _lockstep(_puzzle_inputs())
+        return
+    out = {}
+    if "puzzle_set" in names:
+        out["puzzle_set"] = puzzle_set()
+        names = [n for n in names if n != "puzzle_set"]
+        if not names:
+            print(json.dumps(out))
+            return
     for one_round, (_, _, _, rounds, derived) in SECTIONS.items():
         if names and one_round.__name__ not in names:
             continue
