@@ -87,7 +87,9 @@ struct drna_engine {
   hipEvent_t ev_o0 = nullptr, ev_o1 = nullptr, ev_o2 = nullptr;
   hipEvent_t ev_gate = nullptr;                // the partition function's launch waits for it (see pf_gate_round)
   float timing_edef[2] = {0, 0};
-  // ragged batches: per-sequence descriptors (len, off, target, two index lists) and the structures' pair tables
+  // ragged batches: per-sequence descriptors (len, off, target, two index lists) and the structures' pair tables.  Three blocks
+  // of 7 max_R ints (rg_block): a lock-step loop keeps its scoring plan, its ensemble-defect plan and the second-best fold's
+  // lists on the device side by side
   int* d_rg = nullptr;
   short* d_rpt = nullptr;
   int* d_rpt_off = nullptr;
@@ -949,9 +951,10 @@ static int outside_workspace(drna_engine* e) {
 }
 
 // the inside kernel, then the outside kernel on its tables, both on the partition function's stream and timed (timing_edef);
-// the R sequences are the caller's r_base, r_base + 1, ...
+// the R sequences are the caller's r_base, r_base + 1, ... or, with order (a ragged batch), status word q is that of the caller's order[q]
 template <class Inside, class Outside>
-static int inside_outside(drna_engine* e, int R, int r_base, const char* internal_msg, Inside&& inside, Outside&& outside) {
+static int inside_outside(drna_engine* e, int R, int r_base, const char* internal_msg, Inside&& inside, Outside&& outside,
+                          const int* order = nullptr) {
   reset_status(e);
   HIP_TRY(hipEventRecord(e->ev_o0, e->s_pf));
   inside();
@@ -963,7 +966,7 @@ static int inside_outside(drna_engine* e, int R, int r_base, const char* interna
   HIP_TRY(hipStreamSynchronize(e->s_pf));
   HIP_TRY(hipEventElapsedTime(&e->timing_edef[0], e->ev_o0, e->ev_o1));
   HIP_TRY(hipEventElapsedTime(&e->timing_edef[1], e->ev_o1, e->ev_o2));
-  return fold_status(e, R, false, true, nullptr, r_base, internal_msg);
+  return fold_status(e, R, false, true, order, r_base, internal_msg);
 }
 
 // one batch that fits the workspaces; its sequences are the caller's r_base, r_base + 1, ...
@@ -1133,10 +1136,11 @@ extern "C" int drna_set_targets_ragged(drna_engine* e, int n_targets, const int3
 // One fold of a ragged batch of R sequences sorted longest first (lengths h[q]), in chunks of ws_slots consecutive positions q:
 // per chunk the strip kernels take idxC (one launch per number of strips, most strips first), the general kernel idxD, the LDS-
 // resident kernel idxA.  set_chunk(c0) points the fold's arguments at the chunk's workspace; a launch gets the number of its
-// sequences and their index list on the device (a strip launch also the number of strips and the first flag slot).
+// sequences and their index list on the device, in the plan's descriptor block d_rg (a strip launch also the number of strips and
+// the first flag slot).
 template <class SetChunk, class Strips, class General, class Lds>
 static void ragged_fold(drna_engine* e, int R, const int* h, const int* idxA, int nA, const int* idxC, int nC, const int* idxD, int nD,
-                        SetChunk&& set_chunk, Strips&& launch_strips, General&& launch_general, Lds&& launch_lds) {
+                        const int* d_rg, SetChunk&& set_chunk, Strips&& launch_strips, General&& launch_general, Lds&& launch_lds) {
   const int ld = e->max_L + 2;
   // first entry of an index list (ascending q) that is not below q: the list's part in the chunk [c0, c1) is [lo(c0), lo(c1))
   auto lo = [](const int* idx, int cnt, int q) { return (int)(std::lower_bound(idx, idx + cnt, q) - idx); };
@@ -1147,12 +1151,12 @@ static void ragged_fold(drna_engine* e, int R, const int* h, const int* idxA, in
       const int S = strips_for(e, h[idxC[k]], ld);
       int k2 = k;
       while (k2 < end && strips_for(e, h[idxC[k2]], ld) == S) k2++;
-      launch_strips(k2 - k, S, k, e->d_rg + (size_t)5 * R + k);
+      launch_strips(k2 - k, S, k, d_rg + (size_t)5 * R + k);
       k = k2;
     }
     const int fD = lo(idxD, nD, c0), mD = lo(idxD, nD, c1) - fD, fA = lo(idxA, nA, c0), mA = lo(idxA, nA, c1) - fA;
-    if (mD) launch_general(mD, e->d_rg + (size_t)6 * R + fD);
-    if (mA) launch_lds(mA, e->d_rg + (size_t)3 * R + fA);
+    if (mD) launch_general(mD, d_rg + (size_t)6 * R + fD);
+    if (mA) launch_lds(mA, d_rg + (size_t)3 * R + fA);
   }
 }
 // R results of the sorted order back from the device into the caller's order
@@ -1179,7 +1183,21 @@ struct RaggedPlan {
   std::vector<int> order, h;
   std::vector<size_t> src_off;                     // of the caller's sequence r
   std::vector<char> sorted;                        // the sequences going up / the structures coming back, in sorted order
+  int* d_rg = nullptr;                             // the plan's descriptor block on the device (rg_block)
 };
+// the descriptor blocks: the scoring plan's, the ensemble-defect plan's, the second-best fold's
+enum : int { RG_SCORE = 0, RG_EDEF = 1, RG_SUB = 2, RG_BLOCKS = 3 };
+static int rg_block(drna_engine* e, int which, int** out) {
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->d_rg) HIP_TRY(hipMalloc((void**)&e->d_rg, (size_t)RG_BLOCKS * 7 * e->max_R * sizeof(int)));
+  *out = e->d_rg + (size_t)which * 7 * e->max_R;
+  return DRNA_OK;
+}
+// the indices 0 .. order.size() - 1 by length, longest first (stable: equal lengths keep the caller's order)
+static void longest_first(std::vector<int>& order, const int32_t* lens) {
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
+}
 // the three kernel classes of the plan's lengths under the engine's strip option, and the descriptor block on the device
 static int ragged_classes(drna_engine* e, RaggedPlan& p) {
   const int R = p.R, ld = e->max_L + 2;
@@ -1192,29 +1210,30 @@ static int ragged_classes(drna_engine* e, RaggedPlan& p) {
     else idxD[p.nD++] = q;
   }
   p.strips = e->strips;
-  HIP_TRY(hipSetDevice(e->device));
-  if (!e->d_rg) HIP_TRY(hipMalloc((void**)&e->d_rg, (size_t)7 * e->max_R * sizeof(int)));
-  HIP_TRY(hipMemcpy(e->d_rg, p.h.data(), p.h.size() * sizeof(int), hipMemcpyHostToDevice));
+  { const int rc = rg_block(e, RG_SCORE, &p.d_rg); if (rc != DRNA_OK) return rc; }
+  HIP_TRY(hipMemcpy(p.d_rg, p.h.data(), p.h.size() * sizeof(int), hipMemcpyHostToDevice));
   return DRNA_OK;
 }
-static int ragged_plan(drna_engine* e, int R, const int32_t* lens, const int32_t* target_of, uint32_t flags, RaggedPlan& p) {
+// the checks of a ragged batch (who names the entry point in the message), its sorted order (longest first) and the descriptors
+// len | off | target_of; the index lists behind them are the caller's
+static int ragged_layout(drna_engine* e, const char* who, int R, const int32_t* lens, const int32_t* target_of, uint32_t flags,
+                         RaggedPlan& p) {
   const bool want_ev = flags & DRNA_NEED_EVAL;
   p.R = R; p.flags = flags; p.total = 0;
   p.order.resize(R);
-  std::iota(p.order.begin(), p.order.end(), 0);
   for (int r = 0; r < R; r++) {
-    if (lens[r] < 1 || lens[r] > e->max_L) { e->err = "drna_score_ragged: sequence length outside [1, max_L]"; return DRNA_ERR_ARG; }
+    if (lens[r] < 1 || lens[r] > e->max_L) { e->err = std::string(who) + ": sequence length outside [1, max_L]"; return DRNA_ERR_ARG; }
     p.total += (size_t)lens[r];
     if (want_ev) {
       const int t = target_of[r];
       if (t < 0 || t >= (int)e->rt_len.size() || e->rt_len[t] != lens[r]) {
-        e->err = "drna_score_ragged: target_of[r] must name a structure of drna_set_targets_ragged() with the sequence's length";
+        e->err = std::string(who) + ": target_of[r] must name a structure of drna_set_targets_ragged() with the sequence's length";
         return DRNA_ERR_ARG;
       }
     }
   }
-  if (p.total > (size_t)e->max_R * e->max_L) { e->err = "drna_score_ragged: more nucleotides than max_R * max_L"; return DRNA_ERR_ARG; }
-  std::stable_sort(p.order.begin(), p.order.end(), [&](int a, int b) { return lens[a] > lens[b]; });   // longest first
+  if (p.total > (size_t)e->max_R * e->max_L) { e->err = std::string(who) + ": more nucleotides than max_R * max_L"; return DRNA_ERR_ARG; }
+  longest_first(p.order, lens);
   p.src_off.resize(R);
   { size_t o = 0; for (int r = 0; r < R; r++) { p.src_off[r] = o; o += (size_t)lens[r]; } }
   p.h.assign((size_t)7 * R, 0);
@@ -1227,6 +1246,11 @@ static int ragged_plan(drna_engine* e, int R, const int32_t* lens, const int32_t
     o += (size_t)lens[r];
     if (want_ev) p.h[(size_t)2 * R + q] = target_of[r];
   }
+  return DRNA_OK;
+}
+static int ragged_plan(drna_engine* e, int R, const int32_t* lens, const int32_t* target_of, uint32_t flags, RaggedPlan& p) {
+  { const int rc = ragged_layout(e, "drna_score_ragged", R, lens, target_of, flags, p); if (rc != DRNA_OK) return rc; }
+  const bool want_ev = flags & DRNA_NEED_EVAL;
   { const int rc = ragged_classes(e, p); if (rc != DRNA_OK) return rc; }
   if (want_ev && !e->d_Ed) HIP_TRY(hipMalloc((void**)&e->d_Ed, (size_t)e->max_R * std::max(1, e->n_targets) * sizeof(int32_t)));
   return DRNA_OK;
@@ -1256,7 +1280,7 @@ static int ragged_run(drna_engine* e, RaggedPlan& p, const char* seqs, double* E
   reset_status(e);
   if ((want_pf || want_mfe) && nC) { const int rc = strip_flags(e, want_mfe); if (rc != DRNA_OK) return rc; }
   Ragged rg;
-  rg.len = e->d_rg; rg.off = e->d_rg + R;
+  rg.len = p.d_rg; rg.off = p.d_rg + R;
   HIP_TRY(hipEventRecord(e->ev_start, e->s_mfe));
   HIP_TRY(hipStreamWaitEvent(e->s_pf, e->ev_start, 0));
   HIP_TRY(hipStreamWaitEvent(e->s_eval, e->ev_start, 0));
@@ -1264,7 +1288,7 @@ static int ragged_run(drna_engine* e, RaggedPlan& p, const char* seqs, double* E
     MfeArgs a = mfe_args(e, e->d_seqs, 0, ld, want_pk ? 3 : 0, e->d_Emfe, e->d_ss);
     a.rg = rg;
     HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
-    ragged_fold(e, R, h, idxA, nA, idxC, nC, idxD, nD,
+    ragged_fold(e, R, h, idxA, nA, idxC, nC, idxD, nD, p.d_rg,
                 [&](int c0) { a.ws = e->d_ws_mfe - (long long)c0 * a.ws_stride; a.rg.idx = nullptr; },
                 [&](int n, int S, int k, const int* idx) { launch_mfe_strips(e, a, n, S, k, idx, e->s_mfe); },
                 [&](int n, const int* idx) { a.rg.idx = idx; hipLaunchKernelGGL(mfe_kernel<1024>, dim3(n), dim3(1024), 0, e->s_mfe, a); },
@@ -1276,7 +1300,7 @@ static int ragged_run(drna_engine* e, RaggedPlan& p, const char* seqs, double* E
     PfArgs a = pf_args(e, e->d_seqs, 0, ld, e->d_Epf);
     a.rg = rg;
     HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
-    ragged_fold(e, R, h, idxA, nA, idxC, nC, idxD, nD,
+    ragged_fold(e, R, h, idxA, nA, idxC, nC, idxD, nD, p.d_rg,
                 [&](int c0) { a.ws = e->d_ws_pf - (long long)c0 * a.ws_stride; a.rg.idx = nullptr; },
                 [&](int n, int S, int k, const int* idx) { launch_pf_strips(e, a, n, S, k, idx, e->s_pf); },
                 [&](int n, const int* idx) { a.rg.idx = idx; hipLaunchKernelGGL(pf_kernel<1024>, dim3(n), dim3(1024), 0, e->s_pf, a); },
@@ -1288,7 +1312,7 @@ static int ragged_run(drna_engine* e, RaggedPlan& p, const char* seqs, double* E
   if (want_ev) {
     EvalArgs a = eval_args(e, e->d_seqs, 0, e->d_Ed);
     a.pt = e->d_rpt; a.n_targets = 1;
-    a.rg = rg; a.target_of = e->d_rg + (size_t)2 * R; a.pt_off = e->d_rpt_off;
+    a.rg = rg; a.target_of = p.d_rg + (size_t)2 * R; a.pt_off = e->d_rpt_off;
     HIP_TRY(hipEventRecord(e->ev_e0, e->s_eval));
     hipLaunchKernelGGL(eval_kernel, dim3(R), dim3(WAVE), 0, e->s_eval, a);
     HIP_TRY(hipGetLastError());
@@ -1330,6 +1354,103 @@ extern "C" int drna_score_ragged(drna_engine* e, int R, const int32_t* lens, con
   RaggedPlan p;
   const int rc = ragged_plan(e, R, lens, target_of, flags, p);
   return rc != DRNA_OK ? rc : ragged_run(e, p, seqs, Epf, Emfe, mfe_ss, Ed);
+}
+
+// ---------------------------------------------------------------- ensemble defect of a ragged batch
+
+// The plan of drna_ensemble_defect_ragged (made once per drna_mc_run_ragged_nd call): the layout of a ragged batch, split by the
+// rule of the uniform path (edef_batch_device) per length -- with option "edef_lds" the sequences of at most EDEF_LDS_HOST_MAX
+// nucleotides take the fused LDS kernel (list A), every other one pf_kernel + outside_kernel (list D, a prefix of the sorted order)
+static int edef_ragged_plan(drna_engine* e, const char* who, int R, const int32_t* lens, const int32_t* target_of, RaggedPlan& p) {
+  { const int rc = ragged_layout(e, who, R, lens, target_of, DRNA_NEED_EVAL, p); if (rc != DRNA_OK) return rc; }
+  int *idxA = p.h.data() + (size_t)3 * R, *idxD = p.h.data() + (size_t)6 * R;
+  p.nA = p.nC = p.nD = 0;
+  for (int q = 0; q < R; q++) {
+    if (e->edef_lds && p.h[q] <= EDEF_LDS_HOST_MAX) idxA[p.nA++] = q;
+    else idxD[p.nD++] = q;
+  }
+  { const int rc = rg_block(e, RG_EDEF, &p.d_rg); if (rc != DRNA_OK) return rc; }
+  HIP_TRY(hipMemcpy(p.d_rg, p.h.data(), p.h.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (!e->d_edef) HIP_TRY(hipMalloc((void**)&e->d_edef, (size_t)e->max_R * sizeof(double)));
+  if (!e->d_F4) HIP_TRY(hipMalloc((void**)&e->d_F4, (size_t)4 * e->max_R * sizeof(double)));
+  return p.nD ? outside_workspace(e) : DRNA_OK;
+}
+// One pass of the plan's batch (seqs: the letters in the caller's order): list D in chunks of ws_slots positions, each chunk's
+// two launches through inside_outside on the chunk's slots; then ONE launch of the fused kernel for all of list A, whatever their
+// lengths.  A failed sequence is named by the caller's index; timing_edef = the sums over the chunks and the fused launch
+static int edef_ragged_run(drna_engine* e, RaggedPlan& p, const char* seqs, double* edef) {
+  const int R = p.R, ld = e->max_L + 2;
+  const int *h = p.h.data(), *off = h + R;
+  for (int q = 0; q < R; q++) memcpy(p.sorted.data() + off[q], seqs + p.src_off[p.order[q]], (size_t)h[q]);
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipMemcpy(e->d_seqs, p.sorted.data(), p.total, hipMemcpyHostToDevice));
+  Ragged rg;
+  rg.len = p.d_rg; rg.off = p.d_rg + R;
+  const int* d_target_of = p.d_rg + (size_t)2 * R;
+  float sum[2] = {0, 0};
+  int rc = DRNA_OK;
+  if (p.nD) {
+    PfArgs a = pf_args(e, e->d_seqs, 0, ld, e->d_Epf);
+    a.rg = rg;
+    a.q5_stride = outside_ws_stride(ld);
+    OutArgs o;
+    o.T = e->d_pfT; o.plan = e->d_plan; o.scale = e->d_scale; o.eMLb = e->d_eMLb;
+    o.seqs = e->d_seqs; o.L = 0; o.ld = ld;
+    o.ws_stride = a.ws_stride; o.wo_stride = a.q5_stride;
+    o.pt = e->d_rpt; o.edef = e->d_edef; o.pf_status = e->d_status + e->max_R;
+    o.rg = rg; o.target_of = d_target_of; o.pt_off = e->d_rpt_off;
+    int c1 = 0;
+    ragged_fold(e, R, h, nullptr, 0, nullptr, 0, h + (size_t)6 * R, p.nD, p.d_rg,
+                [&](int c0) {            // the chunk's slots: every workspace pointer moved back by c0 slots
+                  c1 = std::min(R, c0 + e->ws_slots);
+                  a.ws = e->d_ws_pf - (long long)c0 * a.ws_stride;
+                  o.wo = e->d_ws_out - (long long)c0 * o.wo_stride;
+                  a.q5out = o.wo + (size_t)4 * ld * ld;
+                  o.ws = a.ws;
+                },
+                [](int, int, int, const int*) {},
+                [&](int n, const int* idx) {
+                  if (rc != DRNA_OK) return;
+                  a.rg.idx = o.rg.idx = idx;
+                  rc = inside_outside(e, c1, 0, "unexpected status of the partition function",
+                                      [&] { hipLaunchKernelGGL(pf_kernel<1024>, dim3(n), dim3(1024), 0, e->s_pf, a); },
+                                      [&] { hipLaunchKernelGGL((outside_kernel<1024, true>), dim3(n), dim3(1024), 0, e->s_pf, o); },
+                                      p.order.data());
+                  sum[0] += e->timing_edef[0]; sum[1] += e->timing_edef[1];
+                },
+                [](int, const int*) {});
+    if (rc != DRNA_OK) return rc;
+  }
+  if (p.nA) {
+    EdefLdsArgs a;
+    a.in = co_args(e, e->d_seqs, 0, 0, 0);
+    a.out.F = e->d_pfT; a.out.plan = e->d_plan; a.out.scale = e->d_scale; a.out.eMLb = e->d_eMLb;
+    a.out.seqs = e->d_seqs; a.out.eDuplexInit = a.in.eDuplexInit;
+    a.out.pt = e->d_rpt; a.out.edef = e->d_edef; a.out.status_pf = a.in.status_pf;
+    a.rg = rg; a.rg.idx = p.d_rg + (size_t)3 * R;
+    a.target_of = d_target_of; a.pt_off = e->d_rpt_off;
+    e->edef_lds_calls++;
+    rc = inside_outside(e, R, 0, "unexpected status of the ensemble-defect kernel",
+                        [&] { hipLaunchKernelGGL((edef_lds_kernel<1024, true, true>), dim3(p.nA), dim3(1024), 0, e->s_pf, a); }, [] {},
+                        p.order.data());
+    if (rc != DRNA_OK) return rc;
+    sum[0] += e->timing_edef[0]; sum[1] += e->timing_edef[1];
+  }
+  e->timing_edef[0] = sum[0]; e->timing_edef[1] = sum[1];
+  return scatter_back(e, e->d_edef, p.order, edef);
+}
+
+extern "C" int drna_ensemble_defect_ragged(drna_engine* e, int R, const int32_t* lens, const char* seqs, const int32_t* target_of,
+                                           double* edef) {
+  if (!e) return DRNA_ERR_ARG;
+  const char* who = "drna_ensemble_defect_ragged";
+  if (R < 1 || R > e->max_R || !lens || !seqs || !target_of || !edef) {
+    e->err = std::string(who) + ": bad argument (R within the engine's limit max_R; lens, seqs, target_of and edef required)";
+    return DRNA_ERR_ARG;
+  }
+  RaggedPlan p;
+  const int rc = edef_ragged_plan(e, who, R, lens, target_of, p);
+  return rc != DRNA_OK ? rc : edef_ragged_run(e, p, seqs, edef);
 }
 
 // ---------------------------------------------------------------- second-best structure energy (-nd on), one and two strands
@@ -1412,6 +1533,65 @@ static int second_best_mapped(drna_engine* e, int H, int L, int cut) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->s_mfe));
   return fold_status(e, H, true, false, nullptr, 0, cut ? "unexpected status of the second-best co-fold" : "unexpected status of the second-best fold");
+}
+
+// The second-best folds of R sequences of lengths lens (one strand), their letters one after the other at d_seqs (device or
+// host-mapped), in one launch per kernel: with option "subopt_lds" the sequences of at most SUB_LDS_MAX nucleotides keep their
+// tables in LDS, the others use their workspace slot.  Nothing is permuted: the descriptors len | off are in the caller's order
+// and a workgroup list (longest first; the general kernel's part is its prefix) maps workgroups to sequences, so E2 / E12, the
+// status word and the workspace slot of sequence r are at r (R <= ws_slots, fits_workspace) and an error names the caller's index
+static int second_best_ragged(drna_engine* e, int R, const int32_t* lens, const char* d_seqs, int32_t* d_E2,
+                              int32_t* d_E12) {
+  std::vector<int> h((size_t)3 * R), order(R);
+  longest_first(order, lens);
+  int nG = 0;
+  { int o = 0; for (int r = 0; r < R; r++) { h[r] = lens[r]; h[(size_t)R + r] = o; o += lens[r]; } }
+  for (int q = 0; q < R; q++) {
+    h[(size_t)2 * R + q] = order[q];
+    nG += !(e->subopt_lds && lens[order[q]] <= SUB_LDS_MAX);
+  }
+  int* d_rg = nullptr;
+  { const int rc = rg_block(e, RG_SUB, &d_rg); if (rc != DRNA_OK) return rc; }
+  HIP_TRY(hipMemcpy(d_rg, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+  reset_status(e);
+  SuboptArgs a = subopt_args(e, e->max_L, 0, 2);       // slots of the largest size; the kernels take length and pitch from rg
+  a.L = 0;
+  a.seqs = d_seqs; a.E2 = d_E2; a.E12 = d_E12;
+  a.rg.len = d_rg; a.rg.off = d_rg + R;
+  HIP_TRY(hipEventRecord(e->ev_m0, e->s_mfe));
+  if (nG) { a.rg.idx = d_rg + (size_t)2 * R; hipLaunchKernelGGL((subopt_kernel<1024, true>), dim3(nG), dim3(1024), 0, e->s_mfe, a); }
+  if (R - nG) { a.rg.idx = d_rg + (size_t)2 * R + nG; hipLaunchKernelGGL((subopt_lds_kernel<1024, true>), dim3(R - nG), dim3(1024), 0, e->s_mfe, a); }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_m1, e->s_mfe));
+  HIP_TRY(hipStreamSynchronize(e->s_mfe));
+  HIP_TRY(hipEventElapsedTime(&e->timing[0], e->ev_m0, e->ev_m1));
+  e->timing[1] = e->timing[2] = 0.f; e->timing[3] = e->timing[0];
+  return fold_status(e, R, true, false, nullptr, 0, "unexpected status of the second-best fold");
+}
+
+extern "C" int drna_subopt_energy_ragged(drna_engine* e, int R, const int32_t* lens, const char* seqs, int32_t* E2, int32_t* E12) {
+  if (!e) return DRNA_ERR_ARG;
+  const char* who = "drna_subopt_energy_ragged";
+  if (R < 1 || R > e->max_R || !lens || !seqs || !E2) {
+    e->err = std::string(who) + ": bad argument (R within the engine's limit max_R; lens, seqs and E2 required)";
+    return DRNA_ERR_ARG;
+  }
+  { const int rc = fits_workspace(e, who, R); if (rc != DRNA_OK) return rc; }
+  size_t total = 0;
+  for (int r = 0; r < R; r++) {
+    if (lens[r] < 1 || lens[r] > e->max_L) {
+      e->err = std::string(who) + ": sequence " + std::to_string(r) + ": length outside [1, max_L]";
+      return DRNA_ERR_ARG;
+    }
+    total += (size_t)lens[r];
+  }
+  if (total > (size_t)e->max_R * e->max_L) { e->err = std::string(who) + ": more nucleotides than max_R * max_L"; return DRNA_ERR_ARG; }
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipMemcpy(e->d_seqs, seqs, total, hipMemcpyHostToDevice));
+  { const int rc = second_best_ragged(e, R, lens, e->d_seqs, e->d_Emfe, E12 ? reinterpret_cast<int32_t*>(e->d_Epf) : nullptr); if (rc != DRNA_OK) return rc; }
+  HIP_TRY(hipMemcpy(E2, e->d_Emfe, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (E12) HIP_TRY(hipMemcpy(E12, e->d_Epf, (size_t)2 * R * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return DRNA_OK;
 }
 
 // the ranked structures of R sequences (cut > 0: pairs) through the K-best workspace in chunks of kb_chunk.  One slot size serves
@@ -2279,14 +2459,22 @@ extern "C" int drna_mc_run_cofold_nd(MC_RUN_CO_PARAMS, double* subopt_e) {
 
 // drna_mc_run for P problems of different lengths: the chains of all problems make one ragged batch per iteration.  The plan of
 // that batch (lengths do not change inside a call) is made once; an iteration uploads the proposals, launches, and scatters back.
-extern "C" int drna_mc_run_ragged(drna_engine* e, int P, const int32_t* R_of, const int32_t* L_of, int n_iter, const char* targets,
-                                  const unsigned char* allowed_mask, const int32_t* shelf_index, const int32_t* n_shelves,
-                                  double tm_max, double tm_min, int targeted, const double* temps, double Lconst, int n_terms,
-                                  const int32_t* term_id, const double* term_w, uint32_t flags, uint32_t* rng_state, char* seqs,
-                                  char* mfe_ss, double* score, double* mcc1, double* Epf, double* Ed, int64_t* counters,
-                                  char* best_seq, char* best_ss, double* best) {
+// drna_mc_run_ragged_nd adds what drna_mc_run_nd adds to drna_mc_run: the ensemble defect as a scoring term (aux: one ragged
+// ensemble-defect pass per iteration, planned once like the score) and the negative-design step (subopt_e given: the solved
+// proposals of an iteration, whatever their puzzles, get their second-best folds in one ragged launch set).
+#define MC_RAGGED_PARAMS                                                                                                           \
+  drna_engine *e, int P, const int32_t *R_of, const int32_t *L_of, int n_iter, const char *targets,                                \
+      const unsigned char *allowed_mask, const int32_t *shelf_index, const int32_t *n_shelves, double tm_max, double tm_min,       \
+      int targeted, const double *temps, double Lconst, int n_terms, const int32_t *term_id, const double *term_w, uint32_t flags, \
+      uint32_t *rng_state, char *seqs, char *mfe_ss, double *score, double *mcc1, double *Epf, double *Ed, int64_t *counters,      \
+      char *best_seq, char *best_ss, double *best
+#define MC_RAGGED_ARGS                                                                                                              \
+  e, P, R_of, L_of, n_iter, targets, allowed_mask, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, Lconst, n_terms, term_id, \
+      term_w, flags, rng_state, seqs, mfe_ss, score, mcc1, Epf, Ed, counters, best_seq, best_ss, best
+
+// aux false: drna_mc_run_ragged (term 6 refused, no negative design); true: drna_mc_run_ragged_nd
+static int mc_run_ragged_impl(const char* who, MC_RAGGED_PARAMS, bool aux, double* subopt_e) {
   using namespace drna_host;
-  const char* who = "drna_mc_run_ragged";
   if (!e) return DRNA_ERR_ARG;
   if (P < 1 || !R_of || !L_of || n_iter < 0 || !targets || !allowed_mask || !shelf_index || !n_shelves || !temps || n_terms < 1 ||
       !term_id || !term_w || !rng_state || !seqs || !mfe_ss || !score || !mcc1 || !Epf || !Ed || !counters || !best_seq || !best_ss ||
@@ -2296,9 +2484,9 @@ extern "C" int drna_mc_run_ragged(drna_engine* e, int P, const int32_t* R_of, co
   }
   bool want_edef = false;
   { const int rc = mc_terms(e, who, n_terms, term_id, &want_edef); if (rc != DRNA_OK) return rc; }
-  if (want_edef) { e->err = std::string(who) + ": scoring term 6 (Edef) is not available for a set of puzzles"; return DRNA_ERR_ARG; }
+  if (want_edef && !aux) { e->err = std::string(who) + ": scoring term 6 (Edef) is not available for a set of puzzles"; return DRNA_ERR_ARG; }
   McChains ch;
-  ch.P = P; ch.best_vals = 4; ch.poff.resize(P);
+  ch.P = P; ch.best_vals = subopt_e ? 5 : 4; ch.poff.resize(P);
   size_t chars = 0, n_chains = 0;
   for (int p = 0; p < P; p++) {
     if (R_of[p] < 1 || L_of[p] < 1) { e->err = std::string(who) + ": puzzle " + std::to_string(p) + ": R_of < 1 or L_of < 1"; return DRNA_ERR_ARG; }
@@ -2328,6 +2516,7 @@ extern "C" int drna_mc_run_ragged(drna_engine* e, int P, const int32_t* R_of, co
     }
   }
   const int C = (int)n_chains;
+  if (subopt_e) { const int rc = fits_workspace(e, who, C); if (rc != DRNA_OK) return rc; }
   std::vector<ProposeCtx> ctx(P);
   std::vector<int32_t> lens(C);
   ch.of.resize(C); ch.len.resize(C); ch.off.resize(C);
@@ -2351,12 +2540,19 @@ extern "C" int drna_mc_run_ragged(drna_engine* e, int P, const int32_t* R_of, co
   { const int rc = drna_set_targets_ragged(e, P, L_of, targets); if (rc != DRNA_OK) return rc; }
   RaggedPlan plan;
   { const int rc = ragged_plan(e, C, lens.data(), ch.of.data(), flags | DRNA_NEED_PF | DRNA_NEED_MFE | DRNA_NEED_EVAL, plan); if (rc != DRNA_OK) return rc; }
+  RaggedPlan edef_plan;
+  if (want_edef) { const int rc = edef_ragged_plan(e, who, C, lens.data(), ch.of.data(), edef_plan); if (rc != DRNA_OK) return rc; }
   McScored S;
   S.ss.resize(ch.total); S.Epf.resize(C); S.ed.resize(C); S.Emfe.resize(C);
-  std::vector<int32_t> pEmfe(C), pEd(C);
+  if (want_edef) S.edef.resize(C);
+  std::vector<int32_t> pEmfe(C), pEd(C), hit_len(subopt_e ? C : 0);
   auto score_all = [&](const char* prop) -> int {
-    const int rc = ragged_run(e, plan, prop, S.Epf.data(), pEmfe.data(), S.ss.data(), pEd.data());
+    int rc = ragged_run(e, plan, prop, S.Epf.data(), pEmfe.data(), S.ss.data(), pEd.data());
     if (rc != DRNA_OK) return rc;
+    if (want_edef) {                        // inside + outside recursion of every proposal of every puzzle
+      rc = edef_ragged_run(e, edef_plan, prop, S.edef.data());
+      if (rc != DRNA_OK) return rc;
+    }
     for (int r = 0; r < C; r++) { S.ed[r] = pEd[r] / 100.0; S.Emfe[r] = pEmfe[r] / 100.0; }
     return DRNA_OK;
   };
@@ -2365,8 +2561,24 @@ extern "C" int drna_mc_run_ragged(drna_engine* e, int P, const int32_t* R_of, co
     m = sim_metrics(ctx[ch.of[r]].pt.data(), pq, ch.len[r]);
     return true;
   };
-  auto second_best = [](const char*, const int*, int) -> int { return DRNA_OK; };   // (no negative design here)
+  // the solved proposals, whatever their puzzles, one after the other in the staging buffer: E2 of hit h comes back in hm_Emfe[h]
+  auto second_best = [&](const char* prop, const int* hits, int H) -> int {
+    size_t o = 0;
+    for (int k = 0; k < H; k++) {
+      const int r = hits[k];
+      hit_len[k] = ch.len[r];
+      std::memcpy(e->hm_seqs + o, prop + ch.off[r], (size_t)ch.len[r]);
+      o += (size_t)ch.len[r];
+    }
+    return second_best_ragged(e, H, hit_len.data(), e->dm_seqs, e->dm_Emfe, nullptr);
+  };
   return mc_loop(e, who, ch, n_iter, ctx.data(), shelf_index, targeted, temps, Lconst, n_terms, term_id, term_w, rng_state, seqs,
-                 mfe_ss, score, mcc1, Epf, Ed, nullptr, nullptr, nullptr, counters, best_seq, best_ss, best, S, score_all, metrics,
+                 mfe_ss, score, mcc1, Epf, Ed, nullptr, nullptr, subopt_e, counters, best_seq, best_ss, best, S, score_all, metrics,
                  second_best);
+}
+
+extern "C" int drna_mc_run_ragged(MC_RAGGED_PARAMS) { return mc_run_ragged_impl("drna_mc_run_ragged", MC_RAGGED_ARGS, false, nullptr); }
+
+extern "C" int drna_mc_run_ragged_nd(MC_RAGGED_PARAMS, double* subopt_e) {
+  return mc_run_ragged_impl("drna_mc_run_ragged_nd", MC_RAGGED_ARGS, true, subopt_e);
 }

@@ -30,6 +30,7 @@ __host__ __device__ constexpr int tri_cells(int n) { return 1 + n * (n - 1) / 2;
 // the packed triangle of cofold_pf_body / cofold_outside_body: n nucleotides in all, the first strand cut long
 struct CoTri {
   int n, cut;
+  long long off;                                 // of the letters in the sequence buffer (uniform batch: r * n)
   static constexpr bool homodimer = false;
   __device__ __forceinline__ int at(int d, int p) const {
     return d <= 0 ? 0 : 1 + (d - 1) * n - ((d - 1) * d >> 1) + (p - 1);     // slot 0: the empty segment
@@ -38,7 +39,7 @@ struct CoTri {
   __device__ __forceinline__ int zeros() const { return 1; }
   template <int NT, class SM>
   __device__ __forceinline__ void load(SM& sm, const char* seqs, int r, int tid) const {
-    load_sequence<NT>(sm, seqs + (long long)r * n, n, tid);
+    load_sequence<NT>(sm, seqs + off, n, tid);
   }
 };
 
@@ -66,24 +67,33 @@ static_assert(sizeof(EdefLdsSmem<EDEF_LDS_MAX + 1, true>) > 160 * 1024, "EDEF_LD
 
 // in: the inside sweep's arguments (wsp unused; F4: 4 doubles per sequence, meaningless for one strand; status_pf), out: the
 // outside sweep's (wsp / wu unused; the same status_pf).  ONE: in.cut = in.L.
+// One strand only: a ragged batch (drna_ensemble_defect_ragged) -- workgroup b folds sequence rg.idx[b] of its own length, its
+// letters at rg.off, against its own structure (pair tables of drna_set_targets_ragged in out.pt, that of sequence r at
+// pt_off[target_of[r]]); edef and the status word go to the sequence's position.  All null: the uniform batch.
 struct EdefLdsArgs {
   CoArgs in;
   CoOutArgs out;
+  Ragged rg;
+  const int* target_of = nullptr;
+  const int* pt_off = nullptr;
 };
 
-// the host launches this for in.L <= the bound only (one strand: <= EDEF_LDS_HOST_MAX); a longer one leaves at once with the status of an internal error
-template <int NT, bool ONE>
+// the host launches this for lengths <= the bound only (one strand: <= EDEF_LDS_HOST_MAX); a longer one leaves at once with the status of an internal error
+// RAGGED (one strand only): the instance of the ragged launches; the uniform instances never look at the descriptors
+template <int NT, bool ONE, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void edef_lds_kernel(EdefLdsArgs A) {
+  static_assert(ONE || !RAGGED, "no ragged pairs");
   constexpr int N = ONE ? EDEF_LDS_MAX : CO_EDEF_LDS_MAX;
   constexpr int TAB_U = ONE ? 0 : 7;             // the first of the four tables without joining pairs (one strand: none)
   __shared__ EdefLdsSmem<N, ONE> sm;
-  const int r = blockIdx.x;
-  const int n = A.in.L, cut = ONE ? A.in.L : A.in.cut;
+  const int r = RAGGED ? A.rg.seq_of(blockIdx.x) : blockIdx.x;
+  const int n = RAGGED ? A.rg.len_of(r, A.in.L) : A.in.L, cut = ONE ? n : A.in.cut;
   if (n > N) {
     if (threadIdx.x == 0) { A.in.status_pf[r] = ST_TRACEBACK; A.out.edef[r] = 0.0; }
     return;
   }
-  const CoTri lay{n, cut};
+  const CoTri lay{n, cut, RAGGED ? A.rg.off_of(r, n) : (long long)r * n};
+  if (RAGGED && A.target_of) A.out.pt += A.pt_off[A.target_of[r]];
   cofold_pf_body<NT>(sm, A.in, r, sm.tab[0], sm.tab[1], sm.tab[2], sm.INFO, lay);
   __syncthreads();                               // wave 0 finished q5 and the status word; a bad letter left every wave early
   const CoOutTables tb{sm.tab[0], sm.tab[1], sm.tab[2], sm.INFO, sm.tab[3], sm.tab[4], sm.tab[5], sm.tab[6],

@@ -40,6 +40,12 @@ struct OutArgs {
   double* edef = nullptr;          // R
   double* bpp = nullptr;           // optional: R x (L+1) x (L+1), P[i,j] at [i*(L+1)+j], i < j, 1-based
   const int32_t* pf_status = nullptr;   // R: status words written by pf_kernel
+  // ragged batch (drna_ensemble_defect_ragged): on the tables the ragged pf_kernel left -- the same pitch ld for every sequence,
+  // q5 in the sequence's own slot -- each sequence against its own structure: pt holds the pair tables of
+  // drna_set_targets_ragged, pt_off[target_of[r]] is where that of sequence r starts.  bpp is not offered (null)
+  Ragged rg;
+  const int* target_of = nullptr;
+  const int* pt_off = nullptr;
 };
 
 inline long long outside_ws_stride(int ld) { return (long long)4 * ld * ld + ld + 6; }   // doubles per sequence
@@ -49,14 +55,16 @@ struct OutSmem : PfSmem {
   double q3[MAXN + 3];
 };
 
-template <int NT>
+// RAGGED: the instance of the ragged launches reads A.rg / A.target_of; the uniform instance never looks at them (its code is
+// what it was before the descriptors existed)
+template <int NT, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void outside_kernel(OutArgs A) {
   __shared__ OutSmem sm;
   constexpr int NW = NT / WAVE;
   const PfTables& T = *A.T;
   const Plan& P = *A.plan;
-  const int r = blockIdx.x;
-  const int n = A.L, ld = A.ld;
+  const int r = RAGGED ? A.rg.seq_of(blockIdx.x) : blockIdx.x;
+  const int n = RAGGED ? A.rg.len_of(r, A.L) : A.L, ld = A.ld;
   const int tid = threadIdx.x, lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
   const int segG = P.seg[PK_GENERIC];
@@ -82,7 +90,7 @@ __global__ __launch_bounds__(NT) void outside_kernel(OutArgs A) {
   stage_energy_tables<NT>(sm, T, tid);
   for (int k = tid; k <= n; k += NT) sm.q5[k] = q5g[k];
   for (int e = tid; e < NPLAN; e += NT) { sm.plan_u[e] = P.u1[e] | (P.u2[e] << 8) | (P.kind[e] << 16); sm.plan_W[e] = P.W[e]; }
-  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
+  load_sequence<NT>(sm, A.seqs + (RAGGED ? A.rg.off_of(r, n) : (long long)r * n), n, tid);
   if (A.pf_status[r] != ST_OK) {          // bad character / PF out of range: the host reports it
     if (tid == 0) A.edef[r] = 0.0;
     return;
@@ -266,7 +274,7 @@ __global__ __launch_bounds__(NT) void outside_kernel(OutArgs A) {
 
   // probabilities and ensemble defect (ViennaRNA vrna_ensemble_defect: '(' ')' pairs of the target only)
   const double Z = sm.q5[n];
-  const short* pt = A.pt;
+  const short* pt = RAGGED && A.target_of ? A.pt + A.pt_off[A.target_of[r]] : A.pt;
   for (int k = tid + 1; k <= n; k += NT) {
     double val;
     const int m = pt[k];

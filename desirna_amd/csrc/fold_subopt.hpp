@@ -57,6 +57,10 @@ struct SuboptArgs {
   int32_t* E = nullptr;           // R x K energies, ascending (INF_REF where the sequence has fewer structures)
   char* ss = nullptr;             // R x K x L dot-bracket strings (all dots where E = INF_REF)
   int32_t* status = nullptr;      // R
+  // ragged batch (drna_subopt_energy_ragged; the one-strand second-best kernels only): lengths and letter offsets per sequence,
+  // workgroup -> sequence.  A sequence of n nucleotides then folds at its OWN pitch n + 2 (ld is ignored) inside its workspace
+  // slot of ws_stride words, so every table cell sits where the uniform call of that length puts it
+  Ragged rg;
 };
 // the three kernels had an argument struct each; launch code written against those names keeps compiling
 using SubArgs = SuboptArgs;
@@ -297,11 +301,13 @@ struct SubSmem : MfeSmemCore<MAXN> {
   TopK<2> F[MAXN + 2];
 };
 
-template <int NT>
+// RAGGED: the instance of the ragged launches; the uniform instance never looks at A.rg
+template <int NT, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void subopt_kernel(SuboptArgs A) {
   __shared__ SubSmem sm;
   const MfeTables& T = *A.T;
-  const int r = blockIdx.x;
+  const int r = RAGGED ? A.rg.seq_of(blockIdx.x) : blockIdx.x;
+  if (RAGGED && A.rg.len) { A.L = A.rg.len[r]; A.ld = A.L + 2; }
   const int n = A.L, ld = A.ld;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
@@ -314,7 +320,7 @@ __global__ __launch_bounds__(NT) void subopt_kernel(SuboptArgs A) {
   tk_init(none);
   for (int d = 0; d <= TURN && d < n; d++)
     for (int k = tid; k < ld; k += NT) { C[d * ld + k] = none; M[d * ld + k] = none; M2[d * ld + k] = none; }
-  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
+  load_sequence<NT>(sm, A.seqs + (RAGGED ? A.rg.off_of(r, n) : (long long)r * n), n, tid);
   if (sm.flag) {
     if (tid == 0) second_best_report(A, r, ST_BAD_CHAR, 0, INF_DEV);
     return;

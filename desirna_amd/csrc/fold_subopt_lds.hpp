@@ -38,12 +38,12 @@ static_assert(sizeof(SubLdsSmem) <= SUB_LDS_BYTES, "the second-best tables of SU
 static_assert(sizeof(SubLdsSmemT<SUB_LDS_MAX + 1>) > SUB_LDS_BYTES, "SUB_LDS_MAX is the longest sequence that fits");
 static_assert(SUB_LDS_MAX >= 64, "every pair of the co-fold LDS path (CO_LDS_MAX, fold_cofold_lds.hpp) gets its second-best fold in LDS, too");
 
-// CO = false: subopt_kernel, CO = true: cofold_subopt_kernel, with the tables in sm.  The host launches this for A.L <=
-// SUB_LDS_MAX with the pitch A.ld = A.L + 2 only; anything else leaves at once with the status of an internal error
+// CO = false: subopt_kernel, CO = true: cofold_subopt_kernel, with the tables in sm, for sequence r (A.L letters at seq).  The
+// host launches this for A.L <= SUB_LDS_MAX with the pitch A.ld = A.L + 2 only; anything else leaves at once with the status
+// of an internal error
 template <int NT, bool CO>
-__device__ __forceinline__ void second_best_lds(SubLdsSmem& sm, const SuboptArgs& A) {
+__device__ __forceinline__ void second_best_lds(SubLdsSmem& sm, const SuboptArgs& A, int r, const char* seq) {
   const MfeTables& T = *A.T;
-  const int r = blockIdx.x;
   const int n = A.L, ld = A.ld;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
@@ -61,7 +61,7 @@ __device__ __forceinline__ void second_best_lds(SubLdsSmem& sm, const SuboptArgs
     for (int k = tid; k < ld; k += NT) { C[d * ld + k] = none; M[d * ld + k] = none; M2[d * ld + k] = none; }
   if constexpr (CO)
     for (int k = tid; k <= n + 2; k += NT) { sm.fcA[k] = TopK<2>{{0, INF_DEV}}; sm.fcB[k] = TopK<2>{{0, INF_DEV}}; }   // empty / one-nt segments
-  load_sequence<NT>(sm, A.seqs + (long long)r * n, n, tid);
+  load_sequence<NT>(sm, seq, n, tid);
   if (sm.flag) {
     if (tid == 0) second_best_report(A, r, ST_BAD_CHAR, 0, INF_DEV);
     return;
@@ -76,16 +76,19 @@ __device__ __forceinline__ void second_best_lds(SubLdsSmem& sm, const SuboptArgs
   }
 }
 
-template <int NT>
+// RAGGED: the instance of the ragged launches; the uniform instance never looks at A.rg
+template <int NT, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void subopt_lds_kernel(SuboptArgs A) {
   __shared__ SubLdsSmem sm;
-  second_best_lds<NT, false>(sm, A);
+  const int r = RAGGED ? A.rg.seq_of(blockIdx.x) : blockIdx.x;
+  if (RAGGED && A.rg.len) { A.L = A.rg.len[r]; A.ld = A.L + 2; }     // the workgroup's own length and pitch
+  second_best_lds<NT, false>(sm, A, r, A.seqs + (RAGGED ? A.rg.off_of(r, A.L) : (long long)r * A.L));
 }
 
 template <int NT>
 __global__ __launch_bounds__(NT) void cofold_subopt_lds_kernel(SuboptArgs A) {
   __shared__ SubLdsSmem sm;
-  second_best_lds<NT, true>(sm, A);
+  second_best_lds<NT, true>(sm, A, blockIdx.x, A.seqs + (long long)blockIdx.x * A.L);
 }
 
 }  // namespace drna

@@ -613,11 +613,18 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
 class _RaggedSlice:
     """One puzzle's part of a ragged scoring call, as the engine ``energy_scores.score_arrays`` asks: the -sf sum stays there"""
 
-    def __init__(self, Epf, Emfe, ss, Ed):
+    def __init__(self, Epf, Emfe, ss, Ed, edef=None, eng=None):
         self.out = (Epf, Emfe, ss, Ed.reshape(-1, 1))
+        self.edef, self.eng = edef, eng
 
     def score_batch_arrays(self, seqs_u8, flags=0):
         return self.out
+
+    def ensemble_defect_arrays(self, seqs_u8):
+        return self.edef                                  # the puzzle's part of the set's one ragged ensemble-defect call
+
+    def subopt_energy(self, seqs):
+        return self.eng.subopt_energy(seqs)               # the solved candidates of ONE puzzle: equal lengths, the uniform call
 
 
 def batch_eligible(input_file, scoring_f="Ed-Epf:1.0", negative_design="off", oligo="off", subopt="off", acgu=None, **_):
@@ -638,6 +645,12 @@ def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60
     ``Engine.score_ragged_arrays`` call, ``HostKernels.metropolis`` per puzzle).  Returns one result dict per input, in input
     order, with :func:`run_design_fast`'s keys.
 
+    ``negative_design="on"`` and an ``Edef`` term run in lock-step, too (``Engine.mc_run_ragged_nd``): per iteration one ragged
+    ensemble-defect pass over all chains, and the solved proposals of all puzzles in one ragged second-best launch set.  With
+    ``native_loop=False`` (a diagnostic path) the ensemble defect is one ``Engine.ensemble_defect_ragged_arrays`` call per
+    iteration; the second-best energies are one ``Engine.subopt_energy`` call per puzzle with solved candidates.  Records and
+    ``best`` carry ``subopt_e`` / ``esubopt_minus_Epf`` and ``Edef`` as :func:`run_design_fast`'s do.
+
     Every puzzle is a run of its own -- main stream, temperature ladder, replica streams, records, exchange step and stop rule
     are those of :func:`run_design_fast` --, and the kernels' results do not depend on the batch composition: for the same
     keywords a puzzle's records, counters and best are those of its run alone.  A puzzle whose run stops (its step count,
@@ -646,22 +659,24 @@ def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60
     Lock-step ties every puzzle to the pace of the longest one still running.  ``timelimit``: every run's clock starts when the
     SET starts, so the limit bounds the whole set, not each puzzle in turn; ``steps`` is the deterministic mode.
 
-    Inputs must pass :func:`batch_eligible` (one strand, ``( ) .``, no alternative structures, ``-nd`` / ``-oa`` off, no Edef
-    term): the ragged evaluation holds one structure per sequence and the loop has no second-best or self-dimer step.  The
-    engine needs ``max_R`` = the sum of all replicas and ``max_L`` = the longest puzzle.  No replica sharding here."""
+    Inputs: one strand, the brackets ``( ) .`` only, no alternative structures, ``oligo="off"``: the ragged evaluation holds
+    one structure per sequence and the loop has no self-dimer step.  (:func:`batch_eligible`, which routes ``--set``, is narrower:
+    it still sends ``-nd on`` and ``Edef`` sets to the per-puzzle driver.)  The engine needs ``max_R`` = the sum of all replicas
+    and ``max_L`` = the longest puzzle.  No replica sharding here."""
     from . import engine as _engine
     if stop_when_solved and num_results is not None and not keep_records:
         raise ValueError("the -sws rule with num_results ranks the recorded sequences: it needs keep_records=True")
-    bad = [i.name for i in inputs if not batch_eligible(i, scoring_f, negative_design, oligo)]
+    bad = [i.name for i in inputs if not (set(i.sec_struct) <= set("().") and not i.alt_sec_structs and oligo == "off")]
     if bad:
-        raise ValueError("not a puzzle for the lock-step batch (one strand, brackets ( ) . only, no alternative structures, "
-                         "-nd / -oa off, no Edef term): %s" % ", ".join(bad))
+        raise ValueError("not a puzzle for the lock-step batch (still refused: two strands, brackets other than ( ) ., "
+                         "alternative structures, -oa on): %s" % ", ".join(bad))
     if not inputs:
         return []
     es.check_scoring_functions(es.parse_scoring_functions(scoring_f))
     runs = [_setup(i, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results, None, dimer,
                    oligo, keep_records=keep_records) for i in inputs]
     P, R, sf = len(inputs), replicas, runs[0].opts.scoring_f
+    nd, want_edef = negative_design == "on", any(name == "Edef" for name, _ in sf)
     eng = engine or _engine.Engine(max_R=P * R, max_L=max(r.prob.n for r in runs), device=device)
     hk = _engine.HostKernels()
     flags = _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL
@@ -669,25 +684,28 @@ def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60
     def score_all(act, seqs):
         """one ragged call over the (R, L_i) candidates `seqs` of the puzzles `act` -> their score_arrays batches"""
         flat = np.concatenate([s.ravel() for s in seqs])
-        Epf, Emfe, ss, Ed = eng.score_ragged_arrays(flat, np.repeat([runs[i].prob.n for i in act], R),
-                                                    np.repeat(np.array(act, dtype=np.int32), R), flags)
+        lens, tof = np.repeat([runs[i].prob.n for i in act], R), np.repeat(np.array(act, dtype=np.int32), R)
+        Epf, Emfe, ss, Ed = eng.score_ragged_arrays(flat, lens, tof, flags)
+        edef = eng.ensemble_defect_ragged_arrays(flat, lens, tof) if want_edef else None      # ONE call for all active puzzles
         out, o = [], 0
         for k, (i, s) in enumerate(zip(act, seqs)):
-            n = R * runs[i].prob.n
-            part = _RaggedSlice(Epf[k * R:(k + 1) * R], Emfe[k * R:(k + 1) * R], ss[o:o + n].reshape(R, -1), Ed[k * R:(k + 1) * R])
-            out.append(es.score_arrays(part, hk, inputs[i].sec_struct, sf, s, "none", "off"))
+            n, rows = R * runs[i].prob.n, slice(k * R, (k + 1) * R)
+            part = _RaggedSlice(Epf[rows], Emfe[rows], ss[o:o + n].reshape(R, -1), Ed[rows], edef[rows] if want_edef else None, eng)
+            out.append(es.score_arrays(part, hk, inputs[i].sec_struct, sf, s, "none", "off", nd))
             o += n
         return out
 
     eng.set_targets_ragged([i.sec_struct for i in inputs])      # target_of = the input's index, whatever the active set
     init = score_all(list(range(P)), [np.tile(np.frombuffer(r.init.encode(), dtype=np.uint8), (R, 1)) for r in runs])
-    sts = [_array_state(run, b, exchange) for run, b in zip(runs, init)]
+    sts = [_array_state(run, b, exchange, False, False, nd) for run, b in zip(runs, init)]
     t0 = time.time()
     for run in runs:
         run.t_start = t0                                        # one clock for the set
     if native_loop is None:
         native_loop = True
-    native_loop = bool(native_loop and hasattr(eng, "mc_run_ragged") and all(name in eng.TERM_IDS for name, _ in sf))
+    aux = nd or want_edef                                       # the loop with the auxiliary folds (drna_mc_run_ragged_nd)
+    native_loop = bool(native_loop and hasattr(eng, "mc_run_ragged_nd" if aux else "mc_run_ragged")
+                       and all(name in eng.TERM_IDS for name, _ in sf))
     rng_state = np.empty((P * R, _engine.RNG_WORDS), dtype=np.uint32)
     targeted = point_mutations == "on"
     act = list(range(P))
@@ -698,14 +716,18 @@ def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60
         A = len(act)
         lad = [_step_ladder(runs[i], sts[i], hk, rng_state[k * R:(k + 1) * R], np.array(runs[i].shelves)) for k, i in enumerate(act)]
         if native_loop:
-            # the whole exchange step of every active puzzle in ONE native call (drna_mc_run_ragged)
+            # the whole exchange step of every active puzzle in ONE native call (drna_mc_run_ragged[_nd])
             state = {k: np.concatenate([getattr(sts[i].cur, k).ravel() for i in act]) for k in sts[0].keys}
             bsts = [_native_best(sts[i]) for i in act]
             best = {k: np.concatenate([b[k] for b in bsts]) for k in ("seq", "ss")}
             best["vals"] = np.stack([b["vals"] for b in bsts])
             counters = np.zeros((A, 3), dtype=np.int64)
-            eng.mc_run_ragged([runs[i].prob for i in act], exchange, np.concatenate([l[1] for l in lad]), [R] * A, tm_max, tm_min,
-                              targeted, np.concatenate([l[0] for l in lad]), sf, flags, rng_state[:A * R], state, counters, best)
+            args = ([runs[i].prob for i in act], exchange, np.concatenate([l[1] for l in lad]), [R] * A, tm_max, tm_min, targeted,
+                    np.concatenate([l[0] for l in lad]), sf, flags, rng_state[:A * R], state, counters, best)
+            if aux:
+                eng.mc_run_ragged_nd(*args, subopt_e=state["subopt_e"] if nd else None)
+            else:
+                eng.mc_run_ragged(*args)
             o = ob = 0
             for k, i in enumerate(act):
                 n, cur = runs[i].prob.n, sts[i].cur

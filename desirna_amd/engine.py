@@ -67,6 +67,10 @@ _SIGNATURES = {
                              _dbl, _ci, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "drna_mc_run_ragged": (_ci, [_vp, _ci, _vp, _vp, _ci, _str, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _dbl, _ci, _vp, _vp, _u32, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drna_ensemble_defect_ragged": (_ci, [_vp, _ci, _vp, _str, _vp, _vp]),
+    "drna_subopt_energy_ragged": (_ci, [_vp, _ci, _vp, _str, _vp, _vp]),
+    "drna_mc_run_ragged_nd": (_ci, [_vp, _ci, _vp, _vp, _ci, _str, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _dbl, _ci, _vp, _vp, _u32, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "drna_rng_seed": (_ci, [_ci, _vp, _vp]),
     "drna_rng_random": (_ci, [_ci, _vp, _vp]),
 }
@@ -355,6 +359,25 @@ class Engine:
         have one entry per chain, n_shelves one per puzzle; `counters` is (P, 3); `best` holds seq, ss (uint8, puzzle after
         puzzle) and vals (P, 4).  The call replaces the engine's ragged target set (:meth:`set_targets_ragged`) by the
         puzzles' targets.  Plain ``( ) .`` targets only, no Edef term."""
+        self._mc_run_ragged("drna_mc_run_ragged", probs, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f,
+                            flags, rng_state, state, counters, best, L_const, R_of, 4, [])
+
+    def mc_run_ragged_nd(self, probs, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, flags, rng_state,
+                         state, counters, best, L_const=504.12, R_of=None, subopt_e=None):
+        """:meth:`mc_run_ragged` with the auxiliary folds (drna_mc_run_ragged_nd): `scoring_f` may hold an ``Edef`` term (one ragged
+        ensemble-defect pass over all chains per iteration), and with `subopt_e` (float64 C, in/out: the second-best energy of every
+        chain's state, kcal/mol) the loop runs the negative-design step -- the solved proposals of an iteration, whatever their
+        puzzles, in one ragged launch set -- and ``best["vals"]`` is (P, 5), the fifth value the best state's subopt_e."""
+        nd = subopt_e is not None
+        if nd:
+            C_ = int(np.sum(n_shelves if R_of is None else R_of))
+            assert subopt_e.dtype == np.float64 and subopt_e.shape == (C_,) and subopt_e.flags.c_contiguous
+        self._mc_run_ragged("drna_mc_run_ragged_nd", probs, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f,
+                            flags, rng_state, state, counters, best, L_const, R_of, 4 + nd, [subopt_e.ctypes.data if nd else None])
+
+    def _mc_run_ragged(self, name, probs, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, flags, rng_state,
+                       state, counters, best, L_const, R_of, n_vals, tail):
+        """the call both ragged loops share; `tail`: the arguments behind `best`"""
         P = len(probs)
         ns = np.ascontiguousarray(n_shelves, dtype=np.int32)
         R_of = np.ascontiguousarray(ns if R_of is None else R_of, dtype=np.int32)
@@ -367,7 +390,7 @@ class Engine:
         for k in ("score", "mcc1", "Epf", "Ed"):
             assert state[k].dtype == np.float64 and state[k].shape == (C_,) and state[k].flags.c_contiguous, k
         assert counters.dtype == np.int64 and counters.shape == (P, 3) and counters.flags.c_contiguous
-        assert best["vals"].dtype == np.float64 and best["vals"].shape == (P, 4) and best["vals"].flags.c_contiguous
+        assert best["vals"].dtype == np.float64 and best["vals"].shape == (P, n_vals) and best["vals"].flags.c_contiguous
         for k in ("seq", "ss"):
             assert best[k].dtype == np.uint8 and best[k].shape == (chars,) and best[k].flags.c_contiguous, k
         ids = np.array([self.TERM_IDS[n] for n, _ in scoring_f], dtype=np.int32)
@@ -377,11 +400,11 @@ class Engine:
         assert sh.shape == (C_,) and tt.shape == (C_,)
         am = np.concatenate([_packed(q)[0] for q in probs]).astype(np.uint8)
         p = lambda a: a.ctypes.data
-        self._check(self._L.drna_mc_run_ragged(
+        self._check(getattr(self._L, name)(
             self._h, P, p(R_of), p(L_of), int(n_iter), "".join(q.sec_struct for q in probs).encode("ascii"), p(am), p(sh), p(ns),
             float(tm_max), float(tm_min), int(bool(targeted)), p(tt), float(L_const), len(ids), p(ids), p(ws), int(flags), p(rng_state),
             *[p(state[k]) for k in ("seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed")], p(counters), p(best["seq"]), p(best["ss"]),
-            p(best["vals"])))
+            p(best["vals"]), *tail))
         self.n_ragged_targets = P
 
     def mc_run_cofold(self, prob, oligo_state, n_iter, shelf_index, n_shelves, tm_max, tm_min, targeted, temps, scoring_f, rng_state,
@@ -417,6 +440,17 @@ class Engine:
         E12 = np.zeros((R, 2), dtype=np.int32) if want_both else None
         self._check(self._L.drna_subopt_energy_batch(self._h, R, L, "".join(seqs).encode("ascii"), E2.ctypes.data,
                                                      E12.ctypes.data if want_both else None))
+        return (E2, E12) if want_both else E2
+
+    def subopt_energy_ragged(self, seqs, want_both=False):
+        """:meth:`subopt_energy` for sequences of DIFFERENT lengths in one call (drna_subopt_energy_ragged): per sequence the
+        values of :meth:`subopt_energy` on its own length.  At most ``workspace_slots`` sequences."""
+        lens = np.array([len(s) for s in seqs], dtype=np.int32)
+        R = len(lens)
+        E2 = np.zeros(R, dtype=np.int32)
+        E12 = np.zeros((R, 2), dtype=np.int32) if want_both else None
+        self._check(self._L.drna_subopt_energy_ragged(self._h, R, lens.ctypes.data, "".join(seqs).encode("ascii"), E2.ctypes.data,
+                                                      E12.ctypes.data if want_both else None))
         return (E2, E12) if want_both else E2
 
     def cofold_subopt_energy(self, seqs, want_both=False):
@@ -486,6 +520,29 @@ class Engine:
         self._check(self._L.drna_ensemble_defect_batch(self._h, R, L, seqs_u8.ctypes.data_as(C.c_char_p), ed.ctypes.data,
                                                        bpp.ctypes.data if want_bpp else None))
         return (ed, bpp) if want_bpp else ed
+
+    def ensemble_defect_ragged(self, seqs, target_of):
+        """String form of :meth:`ensemble_defect_ragged_arrays` (seqs: strings of different lengths)."""
+        lens = np.array([len(s) for s in seqs], dtype=np.int32)
+        return self.ensemble_defect_ragged_arrays(np.frombuffer("".join(seqs).encode("ascii"), dtype=np.uint8), lens, target_of)
+
+    def ensemble_defect_ragged_arrays(self, flat_u8, lens, target_of):
+        """Ensemble defect of sequences of DIFFERENT lengths in one call (drna_ensemble_defect_ragged): flat_u8 holds their letters
+        back to back (uint8, sum(lens)), target_of[r] names the structure of :meth:`set_targets_ragged` sequence r is measured
+        against.  Returns float64[R], per sequence the value of :meth:`ensemble_defect` on its own length and target.  No pair
+        probabilities.  All sequences of at most ``get_option("edef_lds_max")`` nucleotides share ONE fused launch."""
+        flat_u8 = np.ascontiguousarray(flat_u8, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        tof = np.ascontiguousarray(target_of, dtype=np.int32)
+        R = len(lens)
+        if flat_u8.shape != (int(lens.sum()),):
+            raise ValueError("flat_u8 must hold sum(lens) letters")
+        if tof.shape != (R,):
+            raise ValueError("target_of must name one structure per sequence")
+        ed = np.zeros(R, dtype=np.float64)
+        self._check(self._L.drna_ensemble_defect_ragged(self._h, R, lens.ctypes.data, flat_u8.ctypes.data_as(C.c_char_p),
+                                                        tof.ctypes.data, ed.ctypes.data))
+        return ed
 
     def last_edef_timing(self):
         out = (C.c_float * 2)()

@@ -465,6 +465,39 @@ int drna_mc_run_ragged(drna_engine *e, int P, const int32_t *R_of, const int32_t
                        const double *term_w, uint32_t flags, uint32_t *rng_state, char *seqs, char *mfe_ss, double *score,
                        double *mcc1, double *Epf, double *Ed, int64_t *counters, char *best_seq, char *best_ss, double *best);
 
+/*
+ * The auxiliary folds of a ragged batch, and the lock-step loop with them.  New symbols; DRNA_ABI_VERSION stays 3.
+ *
+ * drna_ensemble_defect_ragged: the ensemble defect (ScoreSeq.get_ensemble_defect, utils/energy_scores.py:362-374) of R sequences of
+ * lengths lens[r], concatenated, each against structure target_of[r] of drna_set_targets_ragged.  Argument rules of
+ * drna_score_ragged (R <= max_R, lengths within max_L, target_of[r] names a structure of the sequence's length, sum of lengths
+ * <= max_R * max_L).  Per sequence the value is drna_ensemble_defect_batch's for that length, bit for bit: with option
+ * "edef_lds" the sequences of at most 40 nt share ONE launch of the fused LDS kernel (counted in "edef_lds_calls"), the others
+ * go through pf_kernel + outside_kernel in chunks of the workspace slots.  No pair probabilities.  drna_last_edef_timing is the
+ * sum over the launches.  A failed sequence is named by the caller's index r.
+ *
+ * drna_subopt_energy_ragged: the second-best energy (get_first_suboptimal_structure_and_energy(seq, fc, 1)[1],
+ * utils/energy_scores.py:104-108) of R sequences of lengths lens[r], concatenated.  E2 / E12 as drna_subopt_energy_batch returns
+ * them for each length (E12 may be NULL); with option "subopt_lds" the sequences of at most 79 nt fold in LDS.  R <= max_R and
+ * R <= workspace slots, as for drna_subopt_energy_batch.
+ *
+ * drna_mc_run_ragged_nd: drna_mc_run_ragged with what drna_mc_run_nd adds to drna_mc_run.  -sf term 6 (Edef) is accepted: every
+ * iteration adds one ragged ensemble-defect pass over all chains.  subopt_e (C doubles, one per chain; NULL: no negative design):
+ * the solved proposals of an iteration (utils/energy_scores.py:93-94,104-108), whatever their puzzles, get their second-best
+ * folds in one ragged launch set; subopt_e[r] is the second-best energy of chain r's state (0 where unsolved) and best holds
+ * 5 values per puzzle (best[4] = that of the best state); needs C <= workspace slots.  Per chain the draws, scores and results
+ * are those of drna_mc_run_nd on that puzzle alone.  Everything else as in drna_mc_run_ragged.
+ */
+int drna_ensemble_defect_ragged(drna_engine *e, int R, const int32_t *lens, const char *seqs, const int32_t *target_of,
+                                double *edef);
+int drna_subopt_energy_ragged(drna_engine *e, int R, const int32_t *lens, const char *seqs, int32_t *E2, int32_t *E12);
+int drna_mc_run_ragged_nd(drna_engine *e, int P, const int32_t *R_of, const int32_t *L_of, int n_iter, const char *targets,
+                          const unsigned char *allowed_mask, const int32_t *shelf_index, const int32_t *n_shelves, double tm_max,
+                          double tm_min, int targeted, const double *temps, double Lconst, int n_terms, const int32_t *term_id,
+                          const double *term_w, uint32_t flags, uint32_t *rng_state, char *seqs, char *mfe_ss, double *score,
+                          double *mcc1, double *Epf, double *Ed, int64_t *counters, char *best_seq, char *best_ss, double *best,
+                          double *subopt_e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """GPU box: device times of the auxiliary paths, one JSON line with a section per path (all, or those named as arguments).
 Per shape the first round warms up and the median of the others is kept.
-`puzzle_set` (only when named; minutes): the Eterna100 set as a design run, lock-step batch against one puzzle after the other."""
+`puzzle_set` (only when named; minutes): the Eterna100 set as a design run, lock-step batch against one puzzle after the other.
+`puzzle_set_aux` (only when named): the same pair for the puzzles of at most 200 nt with -nd on, and with an Edef term added."""
 import json
 import os
 import sys
@@ -248,12 +249,12 @@ def _puzzle_inputs():
                             alt_sec_struct=None, alt_sec_structs=None) for r in csv.DictReader(open(path))]
 
 
-def _lockstep(inputs):
+def _lockstep(inputs, method="mc_run_ragged", **switches):
     """median wall ms of an exchange step of run_puzzle_batch over `inputs` (the first step warms up)"""
     from desirna_amd import design
     eng = E.Engine(max_R=len(inputs) * PS_REPLICAS, max_L=max(len(i.sec_struct) for i in inputs), device=0)
-    kw = dict(replicas=PS_REPLICAS, exchange=PS_EXCHANGE, steps=PS_STEPS, seed=PS_SEED, timelimit=36000, engine=eng)
-    d = _step_times(eng, "mc_run_ragged", lambda: design.run_puzzle_batch(inputs, **kw))
+    kw = dict(replicas=PS_REPLICAS, exchange=PS_EXCHANGE, steps=PS_STEPS, seed=PS_SEED, timelimit=36000, engine=eng, **switches)
+    d = _step_times(eng, method, lambda: design.run_puzzle_batch(inputs, **kw))
     eng.close()
     assert len(d) == PS_STEPS
     return float(np.median(d[1:])) * 1e3
@@ -295,14 +296,49 @@ def puzzle_set():
     return out
 
 
+AUX_SWITCHES = (("nd", dict(negative_design="on")), ("nd_edef", dict(negative_design="on", scoring_f="Ed-Epf:1.0,Edef:1.0")))
+
+
+def puzzle_set_aux():
+    """The 71 Eterna100 targets of at most 200 nt x 32 replicas, exchange = 10, fixed seed, with -nd on and then with Edef:1.0
+    added to the scoring function: (a) lock-step, run_puzzle_batch on drna_mc_run_ragged_nd; (b) run_design_fast one puzzle after
+    the other on an engine of the puzzle's size, summed.  Same process, same visit, medians after a warm-up step."""
+    from desirna_amd import design
+    from desirna_amd import energy_scores as es
+    keep_first = es.parse_scoring_functions
+    es.parse_scoring_functions = lambda s, first_term_only=True: keep_first(s, False)     # (the reference keeps the first -sf term only)
+    inputs = [i for i in _puzzle_inputs() if len(i.sec_struct) <= 200]
+    out = {}
+    for key, switches in AUX_SWITCHES:
+        one_by_one = 0.0
+        for inp in inputs:
+            eng = E.Engine(max_R=PS_REPLICAS, max_L=len(inp.sec_struct), device=0)
+            kw = dict(replicas=PS_REPLICAS, exchange=PS_EXCHANGE, steps=PS_STEPS, seed=PS_SEED, timelimit=36000, engine=eng, **switches)
+            d = _step_times(eng, "mc_run", lambda: design.run_design_fast(inp, **kw))
+            eng.close()
+            assert len(d) == PS_STEPS
+            one_by_one += float(np.median(d[1:])) * 1e3
+        lock = _lockstep(inputs, "mc_run_ragged_nd", **switches)
+        chains = len(inputs) * PS_REPLICAS
+        out[key] = {"puzzles": len(inputs), "chains": chains, "lockstep_step_ms": lock, "per_puzzle_sum_step_ms": one_by_one,
+                    "lockstep_over_per_puzzle": lock / one_by_one,
+                    "lockstep_chain_iters_per_s": chains * PS_EXCHANGE / (lock * 1e-3),
+                    "per_puzzle_chain_iters_per_s": chains * PS_EXCHANGE / (one_by_one * 1e-3)}
+    es.parse_scoring_functions = keep_first
+    return out
+
+
 def main(names):
     if names == ["puzzle_set_profile"]:                      # the child of puzzle_set: the lock-step run alone, profile lines on stderr
         _lockstep(_puzzle_inputs())
         return
     out = {}
-    if "puzzle_set" in names:
-        out["puzzle_set"] = puzzle_set()
-        names = [n for n in names if n != "puzzle_set"]
+    whole_runs = {"puzzle_set": puzzle_set, "puzzle_set_aux": puzzle_set_aux}
+    if set(names) & set(whole_runs):
+        for n in names:
+            if n in whole_runs:
+                out[n] = whole_runs[n]()
+        names = [n for n in names if n not in whole_runs]
         if not names:
             print(json.dumps(out))
             return
