@@ -44,52 +44,52 @@ STRIP_SHAPES = ((15, 15, 40), (0, 30, 40), (15, 16, 12))       # (u1, u2, left o
 _emus = {}
 
 
-def _emu(kind):
-    """this process's emulator of one kind (built once per process)"""
-    if kind not in _emus:
-        from desirna_amd import params
-        blob = params.load_blob()
+def _emu(kind, params_name="turner1999"):
+    """this process's emulator of one kind on one parameter set of tests/probe_params.py (built once per process)"""
+    if (kind, params_name) not in _emus:
+        from tests.probe_params import probe_blob
+        blob = probe_blob(params_name)
         if kind == "emu":
             from tests.emu.emu import Emu
-            _emus[kind] = Emu(blob)
+            _emus[kind, params_name] = Emu(blob)
         elif kind == "co_lds":
             from tests.emu.emu_cofold_lds import EmuCofoldLds
-            _emus[kind] = EmuCofoldLds(blob)
+            _emus[kind, params_name] = EmuCofoldLds(blob)
         else:
             from tests.emu.emu_self_dimer import EmuSelfDimer
-            _emus[kind] = EmuSelfDimer(blob)
-    return _emus[kind]
+            _emus[kind, params_name] = EmuSelfDimer(blob)
+    return _emus[kind, params_name]
 
 
-def _job(job):
+def _job(job, params_name="turner1999"):
     """(kind, sequence[, target]) -> plain Python values; runs in a worker process"""
     kind, s = job[0], job[1]
     if kind in ("gen", "lds"):
         nt = 128 if kind == "gen" else -256
-        E, ss, st = _emu("emu").mfe([s], nt=nt)
-        Ep, stp = _emu("emu").pf([s], nt=nt)
+        E, ss, st = _emu("emu", params_name).mfe([s], nt=nt)
+        Ep, stp = _emu("emu", params_name).pf([s], nt=nt)
         return int(E[0]), ss[0], float(Ep[0]), int(st[0]), int(stp[0])
     if kind == "dual":
-        E, ss, st = _emu("emu").mfe_dual([s], nt=256)
+        E, ss, st = _emu("emu", params_name).mfe_dual([s], nt=256)
         return int(E[0]), ss[0], int(st[0])
     if kind == "subopt":
-        E2, E12, st = _emu("emu").subopt([s], nt=64)
+        E2, E12, st = _emu("emu", params_name).subopt([s], nt=64)
         return int(E2[0]), (int(E12[0, 0]), int(E12[0, 1])), int(st[0])
     if kind == "co_gen":
-        E, ss, F4, st, Ed = _emu("emu").cofold([s], job[2], nt=64)
+        E, ss, F4, st, Ed = _emu("emu", params_name).cofold([s], job[2], nt=64)
         return int(E[0]), ss[0], [float(x) for x in F4[0]], [int(x) for x in st], int(Ed[0])
     if kind == "co_lds":
-        E, ss, F4, st = _emu("co_lds").cofold([s], nt=128)
+        E, ss, F4, st = _emu("co_lds", params_name).cofold([s], nt=128)
         return int(E[0]), ss[0], [float(x) for x in F4[0]], [int(x) for x in st]
     if kind == "sd":
         out = []
         for lds in (True, False):
-            F4, st = _emu("sd").fold([s], nt=128, lds=lds)
+            F4, st = _emu("sd", params_name).fold([s], nt=128, lds=lds)
             out.append(([float(x) for x in F4[0]], int(st[0])))
         return out
     assert kind == "strip"
-    E, ss, st = _emu("emu").mfe_strip([s], 2, nt=256)
-    Ep, stp = _emu("emu").pf_strip([s], 2, nt=256)
+    E, ss, st = _emu("emu", params_name).mfe_strip([s], 2, nt=256)
+    Ep, stp = _emu("emu", params_name).pf_strip([s], 2, nt=256)
     return int(E[0]), ss[0], float(Ep[0]), int(st[0]), int(stp[0])
 
 
