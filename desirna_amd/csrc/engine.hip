@@ -149,7 +149,7 @@ struct drna_engine {
   long long srec_stride = 0;
   long long* d_sclk = nullptr;    // DRNA_STRIP_DEBUG=1: start / end clocks of the MFE strip workgroups of the last launch
   int* d_sdbg = nullptr;          // DRNA_STRIP_DEBUG=1: [2][max_R][8] words written by a strip whose wait failed
-  std::string err;
+  std::string err; drna_host::MotifSet motifs;   // motifs (drna_set_motifs): what every drna_mc_run* loop adds to its proposals' scores; empty: none
 };
 
 #define HIP_TRY(call)                                                                      \
@@ -466,6 +466,7 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "mc_threads_used")) { *value = 1; return DRNA_OK; }       // drna_mc_run's host work runs on the calling thread
   if (!strcmp(name, "workspace_slots")) { *value = e->ws_slots; return DRNA_OK; }
   if (!strcmp(name, "flag_resets")) { *value = e->flag_resets; return DRNA_OK; }
+  if (!strcmp(name, "motifs")) { *value = (int)e->motifs.motifs.size(); return DRNA_OK; }      // set by drna_set_motifs only
   if (!strcmp(name, "debug_epoch")) { *value = std::max(e->pflags.epoch, std::max(e->sflags.epoch, e->dflags.epoch)); return DRNA_OK; }
   return DRNA_ERR_ARG;
 }
@@ -1798,6 +1799,26 @@ extern "C" int drna_simscore_batch(int R, int L, const char* ref, const char* qu
   return DRNA_OK;
 }
 
+extern "C" int drna_motif_score_batch(int R, int L, const char* seqs, int n_motifs, const int32_t* motif_len, const char* motifs,
+                                      const double* value, double* out) {
+  using namespace drna_host;
+  if (R < 0 || L < 1 || n_motifs < 0 || (R > 0 && (!seqs || !out)) || (n_motifs > 0 && (!motif_len || !motifs || !value))) return DRNA_ERR_ARG;
+  MotifSet set;
+  if (!motif_compile(n_motifs, motif_len, motifs, value, set)) return DRNA_ERR_ARG;
+  for (int r = 0; r < R; r++) out[r] = motif_score(set, seqs + (size_t)r * L, L);
+  return DRNA_OK;
+}
+
+extern "C" int drna_set_motifs(drna_engine* e, int n_motifs, const int32_t* motif_len, const char* motifs, const double* value) {
+  if (!e) return DRNA_ERR_ARG;
+  if (n_motifs < 0 || (n_motifs > 0 && (!motif_len || !motifs || !value))) { e->err = "drna_set_motifs: bad argument"; return DRNA_ERR_ARG; }
+  if (!drna_host::motif_compile(n_motifs, motif_len, motifs, value, e->motifs)) {          // (the engine's set stays as it was)
+    e->err = "drna_set_motifs: a motif holds a letter other than A C G T U W S M K R Y B D H V N, or has a negative length";
+    return DRNA_ERR_ARG;
+  }
+  return DRNA_OK;
+}
+
 extern "C" int drna_rng_seed(int R, const uint64_t* seeds, uint32_t* rng_state) {
   if (R < 0 || (R > 0 && (!seeds || !rng_state))) return DRNA_ERR_ARG;
   for (int r = 0; r < R; r++) drna_host::mt_seed_int(drna_host::Mt{rng_state + (size_t)r * drna_host::RNG_WORDS}, seeds[r]);
@@ -2085,7 +2106,9 @@ static McChains mc_uniform(int R, int L) {
 // whose 1 - MCC is exactly 0 get their second-best fold in ONE launch (second_best(prop, hits, H) leaves E2 of hit h in
 // e->hm_Emfe[h]) and lose E2 / 100 - Epf; sub[r] is the second-best energy of replica r's current state (0 where it is unsolved)
 // and best[4] (two strands: best[6]) that of the best state.  So an iteration is two passes over the chains: scores of all
-// proposals first, then the Metropolis draws in chain order, each from its chain's own stream as before
+// proposals first, then the Metropolis draws in chain order, each from its chain's own stream as before.
+// Sequence motifs (the engine's set, drna_set_motifs; utils/energy_scores.py:121-123): the term of every proposal's own string is
+// the last addition of all, the same set for every problem of the loop; with an empty set nothing is searched
 template <class ScoreAll, class Metrics, class SecondBest>
 static int mc_loop(drna_engine* e, const char* who, const McChains& ch, int n_iter, const ProposeCtx* ctx, const int32_t* shelf_index,
                    int targeted, const double* temps, double Lconst, int n_terms, const int32_t* term_id, const double* term_w,
@@ -2107,6 +2130,7 @@ static int mc_loop(drna_engine* e, const char* who, const McChains& ch, int n_it
   std::vector<SimMetrics> cur_m(R);
   std::vector<char> mark(ch.max_len);
   int fail = DRNA_OK;              // the last failure; the other chains go on, as without it
+  const bool with_motifs = !e->motifs.empty();
   auto refresh_pool = [&](int r) {
     if (targeted) cur_np[r] = targeted_pool(ctx[ch.of[r]], cur_pq.data() + off[r], mark.data(), cur_pool.data() + off[r]);
   };
@@ -2177,6 +2201,8 @@ static int mc_loop(drna_engine* e, const char* who, const McChains& ch, int n_it
       if (bad[r]) continue;
       if (xs0) pscore[r] += S.x1[r];                          // oligomer / monomer-fraction bonus: the last addition
       const int L = ch.len[r];
+      if (with_motifs) pscore[r] += motif_score(e->motifs, prop.data() + off[r], L);     // ... but for the motif term (drna_set_motifs;
+                                                                                         // two strands: the string holds the '&')
       const bool same_ss = same[r];
       const SimMetrics& m = pm[r];
       int* ppq = prop_pq.data() + off[r];

@@ -176,4 +176,91 @@ static inline SimMetrics sim_metrics(const int* pr, const int* pq, int n) {
                     py_round3((double)tp / ((double)(tp + fp) + 0.001))};
 }
 
+// ---- sequence motifs (-motifs KEY,VALUE,...; DesiRNA.py:212-224, utils/sequence_utils.py:1231-1251): a motif that occurs
+// anywhere in a candidate adds its value to the score, once (a search, not a count).  A motif letter is a class over the five
+// letters a sequence may hold, one bit each: A 1, C 2, G 4, U 8, T 16.  T stands for itself only and is in no other class (N = ACGU
+// does not match it); any other character of a sequence ('&' of two strands included) is in no class, so no motif matches
+// across the nick.  Motifs of at most 64 letters are searched bit-parallel (Shift-And: bit j of the state = the motif's first
+// j + 1 letters end here); longer ones by a window scan over their class bytes.
+struct MotifLut {
+  unsigned char code[256];                    // sequence letter -> 0 .. 4 (A C G U T), 5 = in no class
+  unsigned char cls[256];                     // motif letter -> its class bits, 0 = not a motif letter
+  MotifLut() {
+    static const char SEQ[] = "ACGUT";
+    static const struct { char ch; unsigned char bits; } IUPAC[] = {
+        {'A', 1}, {'C', 2}, {'G', 4}, {'U', 8}, {'T', 16}, {'W', 1 | 8}, {'S', 2 | 4}, {'M', 1 | 2}, {'K', 4 | 8}, {'R', 1 | 4},
+        {'Y', 2 | 8}, {'B', 2 | 4 | 8}, {'D', 1 | 4 | 8}, {'H', 1 | 2 | 8}, {'V', 1 | 2 | 4}, {'N', 1 | 2 | 4 | 8}};
+    for (int k = 0; k < 256; k++) { code[k] = 5; cls[k] = 0; }
+    for (int k = 0; k < 5; k++) code[(unsigned char)SEQ[k]] = (unsigned char)k;
+    for (const auto& m : IUPAC) cls[(unsigned char)m.ch] = m.bits;
+  }
+};
+static inline const MotifLut& motif_lut() { static const MotifLut lut; return lut; }
+
+struct Motif {
+  int len = 0;
+  double value = 0.0;
+  uint64_t at[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // len <= 64: at[c] bit j = letter c is in the class of motif position j (at[5 ..] stay 0)
+  size_t cls_off = 0;                         // len > 64: its class bytes in MotifSet::cls
+};
+struct MotifSet {
+  std::vector<Motif> motifs;                  // in the order given: the order of additions
+  std::vector<unsigned char> cls;
+  bool empty() const { return motifs.empty(); }
+};
+
+// n_motifs motifs, concatenated in `letters`, -> out; false (out untouched) on a letter that is no motif letter or a negative length
+static inline bool motif_compile(int n_motifs, const int32_t* motif_len, const char* letters, const double* value, MotifSet& out) {
+  const MotifLut& lut = motif_lut();
+  MotifSet set;
+  set.motifs.resize(n_motifs > 0 ? n_motifs : 0);
+  size_t o = 0;
+  for (int k = 0; k < n_motifs; k++) {
+    Motif& m = set.motifs[k];
+    if (motif_len[k] < 0) return false;
+    m.len = motif_len[k]; m.value = value[k]; m.cls_off = set.cls.size();
+    for (int j = 0; j < m.len; j++) {
+      const unsigned char bits = lut.cls[(unsigned char)letters[o + j]];
+      if (!bits) return false;
+      if (m.len > 64) set.cls.push_back(bits);
+      else
+        for (int c = 0; c < 5; c++)
+          if (bits >> c & 1u) m.at[c] |= 1ull << j;
+    }
+    o += (size_t)m.len;
+  }
+  out.motifs.swap(set.motifs); out.cls.swap(set.cls);
+  return true;
+}
+
+static inline bool motif_occurs(const MotifSet& set, const Motif& m, const char* s, int n) {
+  const unsigned char* code = motif_lut().code;
+  if (m.len == 0) return true;                // the empty motif occurs in every sequence
+  if (m.len > n) return false;
+  if (m.len <= 64) {
+    const uint64_t last = 1ull << (m.len - 1);
+    uint64_t d = 0;
+    for (int i = 0; i < n; i++) {
+      d = (d << 1 | 1u) & m.at[code[(unsigned char)s[i]]];
+      if (d & last) return true;
+    }
+    return false;
+  }
+  const unsigned char* cls = set.cls.data() + m.cls_off;
+  for (int i = 0; i + m.len <= n; i++) {
+    int j = 0;
+    while (j < m.len && (cls[j] >> code[(unsigned char)s[i + j]] & 1u)) j++;      // (code 5 tests bit 5, which no class has)
+    if (j == m.len) return true;
+  }
+  return false;
+}
+
+// the motif term of one sequence: 0 + the values of the motifs that occur, in their order
+static inline double motif_score(const MotifSet& set, const char* s, int n) {
+  double total = 0.0;
+  for (const Motif& m : set.motifs)
+    if (motif_occurs(set, m, s, n)) total += m.value;
+  return total;
+}
+
 }  // namespace drna_host

@@ -29,7 +29,12 @@ switch between their Watson-Crick colourings) as in the reference (:143-388, :10
 ``-nd on`` (negative design) runs through both drivers (``run_design_fast(negative_design="on")``: the second-best fold of the
 solved candidates per iteration, or inside the native loop), and so does ``-oa on`` (``run_design_fast(oligo="on")``: every
 candidate folded against a copy of itself, ``Engine.self_dimer`` per iteration or inside the native loop); ``-acgu on``
-(weighted letter choices) and motifs are available in the Python driver (``run_design``) only.
+(weighted letter choices) is available in the Python driver (``run_design``) only.
+
+Sequence motifs (``-motifs KEY,VALUE,...``, ``motifs=`` of every driver: ``energy_scores.parse_motifs``): a motif that occurs in
+a candidate adds its value to the score, last of all additions.  ``run_design`` searches with the reference's regular
+expressions (``energy_scores.score_motifs``); ``run_design_fast`` and ``run_puzzle_batch`` with the native matcher
+(``HostKernels.motif_score`` per iteration, or the engine's motif set -- ``Engine.set_motifs`` -- inside every native loop).
 
 Two strands (hetero-dimer, ``-d on`` homodimer) run through both drivers; together with alternative structures through
 ``run_design`` only.
@@ -311,11 +316,14 @@ def oligo_state_and_pks(sec_struct, dimer="off", oligo="off"):
 # drivers differ in their inner iterations and in how they hold the replica state only.
 
 def _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results, shards,
-           dimer="off", oligo="off", subopt="off", acgu=None, keep_records=True):
-    """The run: problem, options, shards, temperature ladder, main stream and initial sequence (the same on every rank)"""
+           dimer="off", oligo="off", subopt="off", acgu=None, keep_records=True, motifs=None):
+    """The run: problem, options, shards, temperature ladder, main stream and initial sequence (the same on every rank).
+    `motifs`: the ``-motifs`` text or what ``energy_scores.parse_motifs`` makes of it; opts.motifs holds the latter, or None"""
+    if isinstance(motifs, str):
+        motifs = es.parse_motifs(motifs)
     prob = DesignProblem(input_file.sec_struct, input_file.seq_restr, input_file.alt_sec_structs, acgu=acgu)
     oligo_state, pks = oligo_state_and_pks(input_file.sec_struct, dimer, oligo)
-    opts = SimpleNamespace(oligo_state=oligo_state, pks=pks, subopt=subopt, motifs=None, param="1999",
+    opts = SimpleNamespace(oligo_state=oligo_state, pks=pks, subopt=subopt, motifs=motifs or None, param="1999",
                            scoring_f=es.parse_scoring_functions(scoring_f))
     shards = shards or rx.ReplicaShards(replicas, 0, 1)
     run = SimpleNamespace(prob=prob, opts=opts, shards=shards, local=shards.local, steps=steps, timelimit=timelimit,
@@ -378,7 +386,7 @@ def _finish(run, best):
 def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
                device=0, shards=None, scorer=None, progress=None, dimer="off", oligo="off", acgu=None, subopt="off",
-               num_results=None):
+               num_results=None, motifs=None):
     """Replica-exchange Monte-Carlo design of one target.  Returns dict(best=ScoreSeq, solved=bool, history=..., stats=...).
 
     ``shards`` (a ``replica_exchange.ReplicaShards``) splits the replicas over ranks; every rank proposes and scores its
@@ -389,9 +397,12 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
     Loop semantics of the reference (``DesiRNA.py:361-383``): the time limit holds also when ``steps`` is given; records
     carry ``sim_step = global_step * exchange``; ``stop_when_solved`` with ``num_results`` is the reference's ``-sws on``
     (every 10th step: stop when the best ``num_results`` distinct sequences are all solved), without it the run stops at the
-    first solved replica (an extension used by the tests and by the puzzle-set driver)."""
+    first solved replica (an extension used by the tests and by the puzzle-set driver).
+
+    ``motifs`` (``-motifs``: the text ``"KEY,VALUE,..."`` or ``energy_scores.parse_motifs`` of it): the scorer adds the motif
+    term to every candidate (``ReplicaScorer.score``).  A ``scorer`` handed in scores with its own ``sim_options``."""
     run = _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results,
-                 shards, dimer, oligo, subopt, acgu)
+                 shards, dimer, oligo, subopt, acgu, motifs=motifs)
     prob, local = run.prob, run.local
     scorer = scorer or es.ReplicaScorer(input_file, run.opts, max_replicas=max(1, len(local)), device=device)
     cur = scorer.score([run.init] * len(local)) if local else []
@@ -531,7 +542,7 @@ def _array_result(run, st, eng, native_loop):
 def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                     scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
                     device=0, engine=None, keep_records=True, native_loop=None, shards=None, num_results=None, dimer="off",
-                    negative_design="off", oligo="off"):
+                    negative_design="off", oligo="off", motifs=None):
     """Same loop as :func:`run_design` with the per-replica host work in native code and no per-step Python objects:
     proposals, SimScore and Metropolis run batched in the C library, the replica state lives in numpy arrays (the batch of
     ``energy_scores.score_arrays``, of which it keeps what ``Engine.mc_run`` holds).  The
@@ -556,7 +567,13 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
     every candidate is folded against a copy of itself (``Engine.self_dimer`` per iteration, or the self-dimer step of
     ``Engine.mc_run(self_dimer=True)``) and ``-kT ln(1 - oligo_fraction)`` is the last addition to its score, after the
     negative-design term.  Records and ``best`` carry ``oligo_fraction`` and ``monomer_bonus`` as :func:`run_design`'s do.  With a
-    two-strand target the ``&`` decides, as in ``oligo_state_and_pks``: the switch is then without effect."""
+    two-strand target the ``&`` decides, as in ``oligo_state_and_pks``: the switch is then without effect.
+
+    ``motifs`` (``-motifs``: the text ``"KEY,VALUE,..."`` or ``energy_scores.parse_motifs`` of it; reference
+    ``utils/energy_scores.py:121-123``): the motif term of every candidate's string (two strands: with its ``&``) is the last
+    addition to its score, from ``HostKernels.motif_score`` per iteration or inside the native loop, which takes the set from
+    the engine: the run sets it (``Engine.set_motifs``) before its first native call -- to the empty set when it has none, so
+    that an engine handed in does not carry an earlier run's motifs into this one.  No column of its own in the records."""
     from . import engine as _engine
     if stop_when_solved and num_results is not None and not keep_records:
         raise ValueError("the -sws rule with num_results ranks the recorded sequences: it needs keep_records=True "
@@ -567,19 +584,22 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                                   "proposer has no snake moves)")
     es.check_scoring_functions(es.parse_scoring_functions(scoring_f))
     run = _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results,
-                 shards, dimer, oligo, keep_records=keep_records)
+                 shards, dimer, oligo, keep_records=keep_records, motifs=motifs)
     prob, sf, oligo_state, nd = run.prob, run.opts.scoring_f, run.opts.oligo_state, negative_design == "on"
     oa = oligo_state == "avoid"
     R, L, Rl = replicas, prob.n, len(run.local)
     eng = engine or _engine.Engine(max_R=max(1, Rl), max_L=L - 1 if two else L, device=device)      # L counts the '&'
     hk = _engine.HostKernels()
     eng.set_targets([input_file.sec_struct.replace("&", "")] + list(input_file.alt_sec_structs or []))
-    score = lambda seqs_u8: es.score_arrays(eng, hk, input_file.sec_struct, sf, seqs_u8, oligo_state, run.opts.pks, nd, self_dimer=oa)
+    score = lambda seqs_u8: es.score_arrays(eng, hk, input_file.sec_struct, sf, seqs_u8, oligo_state, run.opts.pks, nd, self_dimer=oa,
+                                            motifs=run.opts.motifs)
     st = _array_state(run, score(np.tile(np.frombuffer(run.init.encode(), dtype=np.uint8), (max(1, Rl), 1))), exchange, two, oa, nd)
     cur = st.cur
     if native_loop is None:
         native_loop = True
     native_loop = native_loop and all(name in eng.TERM_IDS for name, _ in sf)   # (every -sf term, Edef included, has a native id)
+    if native_loop and Rl:
+        eng.set_motifs(run.opts.motifs)                   # this run's set or none: the engine may come from another run
     flags = _engine.NEED_PF | _engine.NEED_MFE | _engine.NEED_EVAL | (_engine.NEED_PK if run.opts.pks == "on" else 0)
     rng_state = np.empty((max(1, Rl), _engine.RNG_WORDS), dtype=np.uint32)
     shelves = np.array(run.shelves)
@@ -638,7 +658,7 @@ def batch_eligible(input_file, scoring_f="Ed-Epf:1.0", negative_design="off", ol
 def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                      scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
                      device=0, engine=None, keep_records=True, native_loop=None, num_results=None, dimer="off",
-                     negative_design="off", oligo="off"):
+                     negative_design="off", oligo="off", motifs=None):
     """:func:`run_design_fast` for a SET of puzzles of different lengths on one engine, all advancing in lock-step: per
     iteration the chains of every puzzle still running are scored by ONE ragged call (``Engine.mc_run_ragged`` runs the whole
     exchange step; with ``native_loop=False`` per iteration ``HostKernels.propose_alt`` per puzzle, one
@@ -650,6 +670,9 @@ def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60
     ``native_loop=False`` (a diagnostic path) the ensemble defect is one ``Engine.ensemble_defect_ragged_arrays`` call per
     iteration; the second-best energies are one ``Engine.subopt_energy`` call per puzzle with solved candidates.  Records and
     ``best`` carry ``subopt_e`` / ``esubopt_minus_Epf`` and ``Edef`` as :func:`run_design_fast`'s do.
+
+    ``motifs`` as in :func:`run_design_fast`, the same set for every puzzle: per iteration ``HostKernels.motif_score`` per puzzle,
+    or the engine's set (``Engine.set_motifs``, set or cleared before the first native call) inside the lock-step loops.
 
     Every puzzle is a run of its own -- main stream, temperature ladder, replica streams, records, exchange step and stop rule
     are those of :func:`run_design_fast` --, and the kernels' results do not depend on the batch composition: for the same
@@ -673,8 +696,10 @@ def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60
     if not inputs:
         return []
     es.check_scoring_functions(es.parse_scoring_functions(scoring_f))
+    if isinstance(motifs, str):
+        motifs = es.parse_motifs(motifs)
     runs = [_setup(i, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results, None, dimer,
-                   oligo, keep_records=keep_records) for i in inputs]
+                   oligo, keep_records=keep_records, motifs=motifs) for i in inputs]
     P, R, sf = len(inputs), replicas, runs[0].opts.scoring_f
     nd, want_edef = negative_design == "on", any(name == "Edef" for name, _ in sf)
     eng = engine or _engine.Engine(max_R=P * R, max_L=max(r.prob.n for r in runs), device=device)
@@ -691,7 +716,7 @@ def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60
         for k, (i, s) in enumerate(zip(act, seqs)):
             n, rows = R * runs[i].prob.n, slice(k * R, (k + 1) * R)
             part = _RaggedSlice(Epf[rows], Emfe[rows], ss[o:o + n].reshape(R, -1), Ed[rows], edef[rows] if want_edef else None, eng)
-            out.append(es.score_arrays(part, hk, inputs[i].sec_struct, sf, s, "none", "off", nd))
+            out.append(es.score_arrays(part, hk, inputs[i].sec_struct, sf, s, "none", "off", nd, motifs=runs[i].opts.motifs))
             o += n
         return out
 
@@ -706,6 +731,8 @@ def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60
     aux = nd or want_edef                                       # the loop with the auxiliary folds (drna_mc_run_ragged_nd)
     native_loop = bool(native_loop and hasattr(eng, "mc_run_ragged_nd" if aux else "mc_run_ragged")
                        and all(name in eng.TERM_IDS for name, _ in sf))
+    if native_loop:
+        eng.set_motifs(runs[0].opts.motifs)                     # the set's motifs or none: the engine may come from another run
     rng_state = np.empty((P * R, _engine.RNG_WORDS), dtype=np.uint32)
     targeted = point_mutations == "on"
     act = list(range(P))
@@ -847,6 +874,8 @@ def main(argv=None):
     ap.add_argument("-nd", "--negative_design", default="off", choices=["off", "on"], dest="subopt")
     ap.add_argument("-acgu", "--ACGU", default="off", choices=["off", "on"], dest="percs", help="weighted nucleotide choices")
     ap.add_argument("-acgu_content", "--ACGU_content", default="", dest="acgu_content", help="A,C,G,U percentages (sum 100)")
+    ap.add_argument("-motifs", "--motif_sequences", default=None, dest="motifs", help="Sequence motifs along with their "
+                    "bonuses(-)/penalties(+). Provide comma-separated key,value,key,value sequence.")
     ap.add_argument("--python-host", action="store_true", help="per-replica Python host loop instead of the native batched one")
     ap.add_argument("-o", "--outdir", default=None, help="write the reference's result files (_results.csv, _traj.csv, "
                     "_stats, _best_str, fasta files) into this directory")
@@ -854,6 +883,11 @@ def main(argv=None):
     common = dict(replicas=a.replicas, exchange=a.exchange, steps=a.steps, timelimit=a.timlim, t_min=a.t_min, t_max=a.t_max,
                   scoring_f=a.scoring_f, tm_max=a.tm_max, tm_min=a.tm_min, point_mutations=a.pm, seed=a.in_seed,
                   stop_when_solved=a.sws == "on", num_results=a.num_results if a.sws == "on" else None)
+    if a.motifs is not None:                                      # (only with the flag: without it the drivers' keywords are as before)
+        try:
+            common["motifs"] = es.parse_motifs(a.motifs)
+        except ValueError as err:
+            ap.error(str(err))
     if a.set_files:
         inputs = [read_input(f) for f in a.set_files]
         # the switches under run_design_fast's names, so that run_puzzle_set can tell which inputs may share the batch; the

@@ -12,7 +12,8 @@ There is ONE scorer and it works on arrays: ``SF_TERMS`` is the ``-sf`` table (n
 :func:`score_arrays` scores an (R, L) uint8 batch of candidates -- one strand, two strands, alternative structures,
 ``-nd on`` -- in the reference's order of additions, and :func:`record` turns one row of its result into a ``ScoreSeq``.
 ``ReplicaScorer.score`` (``design.run_design``) is ``record`` over every row, plus ``-oa`` (through its own 2 L engine;
-``score_arrays(self_dimer=True)`` is the fast driver's form, ``Engine.self_dimer``) and the motifs;
+``score_arrays(self_dimer=True)`` is the fast driver's form, ``Engine.self_dimer``) and the motifs (``score_motifs`` on the
+regular expressions of :func:`parse_motifs`; ``score_arrays(motifs=...)`` is the fast drivers' form, ``HostKernels.motif_score``);
 ``design.run_design_fast`` keeps the arrays as its replica state and calls ``record`` for its records only.  The native
 loop (``mc_loop`` in ``csrc/engine.hip``) is the same sum in C, on the same term ids.
 
@@ -167,6 +168,30 @@ def _install_setters(cls):
 _install_setters(ScoreSeq)
 
 
+# letters of a -motifs key and the sequence letters each stands for (T is a letter of its own: N does not match it)
+MOTIF_LETTERS = {"A": "A", "C": "C", "G": "G", "U": "U", "T": "T", "W": "AU", "S": "CG", "M": "AC", "K": "GU", "R": "AG", "Y": "CU",
+                 "B": "CGU", "D": "AGU", "H": "ACU", "V": "ACG", "N": "ACGU"}
+
+
+def parse_motifs(text):
+    """``-motifs KEY,VALUE,KEY,VALUE,...`` (reference DesiRNA.py:212-224) -> the dict ``sim_options.motifs`` holds there:
+    key -> (compiled regular expression, float value), in the order given; a repeated key keeps its first position and takes
+    its last value; the empty key is legal and occurs in every sequence.  An empty text: no motifs.  An odd number of items, a
+    letter outside ``MOTIF_LETTERS`` (lower case included) or a value that is no float raises ValueError with the
+    reference's message."""
+    import re
+    if not text:
+        return {}
+    items = text.split(",")
+    try:
+        if len(items) % 2:
+            raise IndexError(len(items))
+        return {key: (re.compile("".join(MOTIF_LETTERS[ch] if len(MOTIF_LETTERS[ch]) == 1 else "[%s]" % MOTIF_LETTERS[ch] for ch in key)),
+                      float(value)) for key, value in zip(items[::2], items[1::2])}
+    except (KeyError, ValueError, IndexError):
+        raise ValueError("Something is wrong with your motifs") from None
+
+
 def score_motifs(seq, sim_options):
     """reference utils/sequence_utils.py:1231-1251"""
     motif_score = 0
@@ -176,7 +201,7 @@ def score_motifs(seq, sim_options):
     return motif_score
 
 
-def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pks="off", nd=False, self_dimer=False):
+def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pks="off", nd=False, self_dimer=False, motifs=None):
     """THE scorer (reference score_sequence(), :70-118, for a whole batch): `eng` an ``engine.Engine`` whose targets are
     sec_struct (+ the alternative structures) without the '&', `hk` an ``engine.HostKernels``, seqs_u8 the (R, L) uint8 candidates
     (two strands -- oligo_state heterodimer / homodimer --: with the '&' column).  Returns the batch as arrays, named like the
@@ -187,6 +212,10 @@ def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pk
     `self_dimer` (opt-in, with oligo_state "avoid" = -oa on only): oligo_fraction of every candidate folded against a copy of
     itself from ``eng.self_dimer`` and bonus = -kT ln(1 - oligo_fraction), added last (reference :118-119, :412-419).  Off by
     default: ``ReplicaScorer.score`` adds that term itself.
+
+    `motifs` (opt-in; :func:`parse_motifs`'s dict, or any form ``HostKernels.motif_score`` takes): the motif term of every
+    candidate's string (two strands: with the '&'), the last addition of all (reference :121-123).  Off by default:
+    ``ReplicaScorer.score`` adds that term itself, too.
 
     The reference's order of additions: the -sf sum; + (Ed2 - Epf) with alternative structures, every energy / 100 first, then
     the sum, then / count (one strand only, as the two-strand scorer always had it); - (subopt_e - Epf) on the candidates with
@@ -243,6 +272,8 @@ def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pk
         b.bonus = np.array([float(kTlog_monomer_fraction(f)) for f in b.oligo_fraction])
         b.bonus_field = "monomer_bonus"
         b.score = b.score + b.bonus
+    if motifs:                                            # reference :121-123
+        b.score = b.score + hk.motif_score(motifs, seqs_u8)
     return b
 
 
@@ -280,7 +311,7 @@ def record(b, k):
 
 class ReplicaScorer:
     """Binds an engine to one design problem (target + alt structures + options) and scores batches: :func:`score_arrays` and
-    :func:`record`, plus what only ``design.run_design`` has (-oa on and the motifs)."""
+    :func:`record`, plus the two terms ``design.run_design`` adds record by record (-oa on and the motifs)."""
 
     def __init__(self, input_file, sim_options, max_replicas, device=0, engine=None):
         self.oligo_state = getattr(sim_options, "oligo_state", "none")

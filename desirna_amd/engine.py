@@ -71,6 +71,8 @@ _SIGNATURES = {
     "drna_subopt_energy_ragged": (_ci, [_vp, _ci, _vp, _str, _vp, _vp]),
     "drna_mc_run_ragged_nd": (_ci, [_vp, _ci, _vp, _vp, _ci, _str, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _dbl, _ci, _vp, _vp, _u32, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drna_motif_score_batch": (_ci, [_ci, _ci, _vp, _ci, _vp, _str, _vp, _vp]),
+    "drna_set_motifs": (_ci, [_vp, _ci, _vp, _str, _vp]),
     "drna_rng_seed": (_ci, [_ci, _vp, _vp]),
     "drna_rng_random": (_ci, [_ci, _vp, _vp]),
 }
@@ -93,6 +95,19 @@ def _packed(prob):
     if getattr(prob, "_native_pack", None) is None:
         HostKernels._pack(prob)
     return prob._native_pack
+
+
+def _motif_arrays(motifs):
+    """motifs -- an ordered mapping key -> value (or key -> (compiled regex, value), what ``energy_scores.parse_motifs`` returns)
+    or a list of (key, value); a repeated key keeps its first position and takes its last value, as in a dict; None or empty:
+    no motifs -- -> (count, int32 lengths, the keys concatenated as bytes, float64 values) of drna_set_motifs /
+    drna_motif_score_batch.  A key outside ASCII can be no motif: bytes the library refuses."""
+    d = {}
+    for key, v in (motifs.items() if hasattr(motifs, "items") else motifs or ()):
+        d[key] = float(v[1] if isinstance(v, tuple) else v)
+    keys = [k.encode("ascii", "replace") for k in d]
+    return (len(d), np.array([len(k) for k in keys] or [0], dtype=np.int32), b"".join(keys),
+            np.array(list(d.values()) or [0.0], dtype=np.float64))
 
 
 def _check_rng(rng_state, R):
@@ -215,6 +230,14 @@ class Engine:
             raise ValueError("all target structures must have the same length")
         self._check(self._L.drna_set_targets(self._h, len(targets), L, "".join(targets).encode("ascii")))
         self.n_targets, self.L = len(targets), L
+
+    def set_motifs(self, motifs):
+        """Sequence motifs (``-motifs``; drna_set_motifs) of every ``mc_run*`` call from now on: each proposal whose string holds
+        a motif gets the motif's value added to its score, last of all additions.  `motifs`: an ordered mapping key -> value
+        (``energy_scores.parse_motifs``'s dict is one) or a list of (key, value); None or empty clears the set.  It is engine
+        state: whoever shares an engine between runs sets it before each run.  ``get_option("motifs")`` is the count."""
+        n, lens, keys, values = _motif_arrays(motifs)
+        self._check(self._L.drna_set_motifs(self._h, n, lens.ctypes.data, keys, values.ctypes.data))
 
     def score_batch(self, seqs, flags=NEED_PF | NEED_MFE | NEED_EVAL):
         """String form of :meth:`score_batch_arrays`: seqs is a list of equal-length strings.  Returns dict(Epf, Emfe, mfe_ss, Ed)
@@ -569,7 +592,7 @@ class Engine:
 
 
 class HostKernels:
-    """Native batched host helpers of the MC inner loop (no GPU needed): SimScore, proposals, Metropolis."""
+    """Native batched host helpers of the MC inner loop (no GPU needed): SimScore, proposals, Metropolis, the motif term."""
 
     def __init__(self, lib=None):
         self._L = load_library(lib)
@@ -619,6 +642,18 @@ class HostKernels:
         if rc != 0:
             raise EngineError(rc, "drna_simscore_batch")
         return mcc, rec, prec
+
+    def motif_score(self, motifs, seqs_u8):
+        """The motif term of every sequence of seqs_u8 ((R, L) uint8; two strands with the '&' column): 0 + the values of the
+        motifs that occur in it, in their order (drna_motif_score_batch).  `motifs` as for ``Engine.set_motifs``."""
+        s = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
+        R, L = s.shape
+        n, lens, keys, values = _motif_arrays(motifs)
+        out = np.zeros(R, dtype=np.float64)
+        rc = self._L.drna_motif_score_batch(R, L, s.ctypes.data, n, lens.ctypes.data, keys, values.ctypes.data, out.ctypes.data)
+        if rc != 0:
+            raise EngineError(rc, "drna_motif_score_batch")
+        return out
 
     def _propose(self, name, struct, problem, seqs_u8, ss_u8, shelf_index, n_shelves, tm_max, tm_min, targeted, rng_state):
         """drna_propose_batch[_alt|_co] (`name`): `problem` are the arguments between the structure and the sequences"""

@@ -281,6 +281,37 @@ int drna_simscore_batch(int R, int L, const char *ref, const char *queries, doub
                         double *precision);
 
 /*
+ * Sequence motifs (-motifs KEY,VALUE,KEY,VALUE,...; DesiRNA.py:212-224, score_motifs of utils/sequence_utils.py:1231-1251): a
+ * motif that occurs anywhere in a sequence adds its value to the sequence's score, once however often it occurs; the term of
+ * a sequence is 0 + the values of the motifs that occur, in the order given, and it is the last addition to the score (after
+ * the -sf sum, the alternative-structure term, the negative-design term and the oligomer / monomer-fraction bonus,
+ * utils/energy_scores.py:121-123).  A motif is a string over A C G T U W S M K R Y B D H V N: W = AU, S = GC, M = AC, K = GU,
+ * R = AG, Y = CU, B = CGU, D = AGU, H = ACU, V = ACG, N = ACGU; A C G U T match themselves only (N does not match T).  Any other
+ * character of a sequence matches nothing: a two-strand string is searched with its '&' in place, so no motif matches across
+ * the nick.  The empty motif occurs in every sequence.  Motifs of at most 64 letters are searched bit-parallel (one pass over
+ * the sequence per motif, ended by the first hit), longer ones by a window scan.
+ *   n_motifs    >= 0
+ *   motif_len   n_motifs ints, each >= 0
+ *   motifs      the motifs' letters, concatenated (sum of motif_len chars, no terminator needed)
+ *   value       n_motifs doubles
+ * A letter outside the sixteen above (lower case included) is DRNA_ERR_ARG.
+ *
+ * drna_motif_score_batch (no engine needed): out[r] = the term of sequence r of R sequences of L >= 1 chars; n_motifs == 0
+ * writes zeros.
+ *
+ * drna_set_motifs: the motif set of the ENGINE, which every drna_mc_run* loop (drna_mc_run, _nd, _oa, _cofold, _cofold_nd,
+ * _ragged, _ragged_nd) adds to the score of every proposal -- the term of the chain's own string, two strands with the '&', the
+ * same set for every puzzle of a ragged loop.  n_motifs == 0 clears the set; a loop with an empty set does no work for it and
+ * returns what it returned before the set existed.  The set stays until the next call: a caller that shares an engine between
+ * runs sets it (or clears it) before each run.  On DRNA_ERR_ARG the engine's set is unchanged.  The read-only option "motifs"
+ * (drna_get_option) is the number of motifs set.
+ * New symbols: no existing signature or buffer changes, DRNA_ABI_VERSION stays 3.
+ */
+int drna_motif_score_batch(int R, int L, const char *seqs, int n_motifs, const int32_t *motif_len, const char *motifs,
+                           const double *value, double *out);
+int drna_set_motifs(drna_engine *e, int n_motifs, const int32_t *motif_len, const char *motifs, const double *value);
+
+/*
  * Per-replica random streams of the host helpers: the reference's worker calls random.seed(replica_index) at the start of
  * every exchange step (utils/replica_exchange_monte_carlo.py:227-228 with seeds = [0 .. R-1], :250) and then draws from
  * Python's global Mersenne Twister.  drna_rng_seed(seeds) = random.seed(int) for each of R streams (MT19937 init_by_array
