@@ -737,7 +737,8 @@ typedef struct {
   double *qb, *qm, *qm1, *q5, *scale, *eMLb;
 } pfctx;
 
-static void pf_fill(const orc_params *P, pfctx *F, const char *seq, int n) {
+/* fi, fj: the mask of orc_pf_forbid (fi == 0: none), applied to the pair-type table and nowhere else */
+static void pf_fill(const orc_params *P, pfctx *F, const char *seq, int n, int fi, int fj) {
   const int W = n + 2;
   size_t W2 = (size_t)W * (size_t)W;
   F->n = n;
@@ -779,6 +780,10 @@ static void pf_fill(const orc_params *P, pfctx *F, const char *seq, int n) {
     }
   for (int i = 1; i <= n; i++)
     for (int j = i + TURN + 1; j <= n; j++) F->pty[IDX(i, j)] = (unsigned char)PAIR[S[i]][S[j]];
+  if (fi >= 1 && fi <= n) {
+    if (fj > 0) { if (fj <= n && fj != fi) F->pty[IDX(MIN2(fi, fj), MAX2(fi, fj))] = 0; }
+    else for (int k = 1; k <= n; k++) { F->pty[IDX(fi, k)] = 0; F->pty[IDX(k, fi)] = 0; }
+  }
   /* ViennaRNA part_func.c fill_arrays: j ascending, i descending */
   for (int j = TURN + 2; j <= n; j++) {
     for (int i = j - TURN - 1; i >= 1; i--) {
@@ -853,22 +858,30 @@ static void pf_free(pfctx *F) {
   free(F->scale); free(F->eMLb);
 }
 
-double orc_pf(const orc_params *P, const char *seq, int n) {
+double orc_pf_forbid(const orc_params *P, const char *seq, int n, int fi, int fj) {
   pfctx F;
-  pf_fill(P, &F, seq, n);
+  pf_fill(P, &F, seq, n, fi, fj);
   double Z = F.q5[n];
   double e = (-log(Z) - n * log(P->pf_scale)) * P->kT / 1000.0;
   pf_free(&F);
   return e;
 }
 
+double orc_pf(const orc_params *P, const char *seq, int n) { return orc_pf_forbid(P, seq, n, 0, 0); }
+
+void orc_pf_forbid_batch(const orc_params *P, const char *seq, int n, int m, const int32_t *fi, const int32_t *fj, double *F) {
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int k = 0; k < m; k++) F[k] = orc_pf_forbid(P, seq, n, fi[k], fj[k]);
+}
+
 /* Outside recursion -> base-pair probabilities -> ensemble defect (reference
  * energy_scores.py:362-374; ViennaRNA vrna_ensemble_defect).  NOT golden-pinned (no vector in the
  * reference); Z, every P(i,j) and the defect are checked against the explicit sum over ALL structures weighted by
- * orc_boltzmann_weight (tests/test_oracle_golden.py::test_pf_bpp_defect_against_enumeration). */
+ * orc_boltzmann_weight (tests/test_oracle_golden.py::test_pf_bpp_defect_against_enumeration) and, up to 400 nt, against
+ * 1 - exp(-(F[not (i,j)] - F) / kT) from orc_pf_forbid (tests/test_pair_prob_reference.py). */
 double orc_ensemble_defect(const orc_params *P, const char *seq, int n, const char *target, double *bpp) {
   pfctx F;
-  pf_fill(P, &F, seq, n);
+  pf_fill(P, &F, seq, n, 0, 0);
   const int W = n + 2;
   size_t W2 = (size_t)W * (size_t)W;
   int *S = F.S;
@@ -1442,7 +1455,14 @@ int orc_cofold_mfe(const orc_params *P, const char *seq, int n, int cut, char *s
 
 /* out[0] = FA, out[1] = FB, out[2] = FcAB (true hybrids, DuplexInit and symmetry applied), out[3] = FAB */
 void orc_cofold_pf(const orc_params *P, const char *seq, int n, int cut, double out[4]) {
+  orc_cofold_pf_forbid(P, seq, n, cut, 0, 0, out);
+}
+
+/* the same fill with a mask on the pair-type look-up PT(): fj > 0 forbids the pair (fi,fj), fj == 0 every pair of fi,
+ * fi == 0 nothing */
+void orc_cofold_pf_forbid(const orc_params *P, const char *seq, int n, int cut, int fi, int fj, double out[4]) {
   const int W = n + 2;
+  if (fj > 0 && fj < fi) { int x = fi; fi = fj; fj = x; }
   size_t W2 = (size_t)W * (size_t)W;
   int *S = encode_seq(seq, n);
   char *up = (char *)malloc((size_t)n + 1);
@@ -1459,7 +1479,8 @@ void orc_cofold_pf(const orc_params *P, const char *seq, int n, int cut, double 
   double *scale = (double *)malloc(sizeof(double) * (size_t)(n + 3)), *eMLb = (double *)malloc(sizeof(double) * (size_t)(n + 3));
   scale[0] = 1.0; eMLb[0] = 1.0;
   for (int k = 1; k <= n + 2; k++) { scale[k] = scale[k - 1] / P->pf_scale; eMLb[k] = eMLb[k - 1] * P->eMLbase / P->pf_scale; }
-#define PT(i, j) (((j) - (i) > TURN || !SAMESTR(i, j)) ? PAIR[S[i]][S[j]] : 0)
+#define MASKED(i, j) (fi > 0 && (fj > 0 ? ((i) == fi && (j) == fj) : ((i) == fi || (j) == fi)))
+#define PT(i, j) ((((j) - (i) > TURN || !SAMESTR(i, j)) && !MASKED(i, j)) ? PAIR[S[i]][S[j]] : 0)
   for (int i = n; i >= 1; i--) {
     if (i == cut) {
       qB5[cut] = 1.0;
@@ -1542,6 +1563,7 @@ void orc_cofold_pf(const orc_params *P, const char *seq, int n, int cut, double 
     q5[j] = q;
   }
 #undef PT
+#undef MASKED
   const double kT = P->kT / 1000.0, lsc = log(P->pf_scale);
   const double QA = qA3[1], QB = qB5[n], Q0 = q5[n];
   double QAB = (Q0 - QA * QB) * exp(-(double)P->DuplexInit * 10.0 / P->kT);
@@ -1552,6 +1574,12 @@ void orc_cofold_pf(const orc_params *P, const char *seq, int n, int cut, double 
   out[2] = QAB > 1e-17 ? -kT * (log(QAB) + n * lsc) : 999.0;
   out[3] = -kT * (log(Qtot) + n * lsc);
   free(S); free(up); free(qb); free(qm); free(qm1); free(q5); free(qA3); free(qB5); free(scale); free(eMLb);
+}
+
+void orc_cofold_pf_forbid_batch(const orc_params *P, const char *seq, int n, int cut, int m, const int32_t *fi,
+                                const int32_t *fj, double *out) {
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int k = 0; k < m; k++) orc_cofold_pf_forbid(P, seq, n, cut, fi[k], fj[k], out + 4 * (size_t)k);
 }
 
 /* ---------------------------------------------------------------- second-best structure

@@ -15,8 +15,9 @@
  * structures, pk-annotated structures, 1-MCC/recall/precision) and
  * eterna_benchmark/Eterna100V1_benchmark_results (MFE(sequence) == structure).  See
  * tests/golden/ and tests/test_oracle_golden.py.  Outside recursion / ensemble defect has no
- * golden vector in the reference ("parity unpinned" for that one quantity); it is verified against
- * an explicit Boltzmann-weighted sum over all structures of short sequences instead.
+ * golden vector in the reference; it is verified against an explicit Boltzmann-weighted sum over
+ * all structures of short sequences, and at any length against pair probabilities taken from the
+ * pinned inside fills alone (orc_pf_forbid, orc_cofold_pf_forbid; tests/pair_prob_ref.py).
  *
  * Model in force (reference energy_scores.py:27-28 sets only compute_bpp=0): 37 degC, dangles=2,
  * noLP=0, noGU=0, special hairpins on, TURN=3, MAXLOOP=30, linear, no G-quadruplexes,
@@ -50,6 +51,14 @@ int orc_mfe(const orc_params *P, const char *seq, int n, const unsigned char *no
 /* fc.pf()[1] with compute_bpp=0: ensemble free energy in kcal/mol */
 double orc_pf(const orc_params *P, const char *seq, int n);
 
+/* The same fill with ONE condition added to the pair-type look-up: fj > 0 forbids the pair (fi,fj), fj == 0 forbids every pair
+ * of fi, fi == 0 is orc_pf (same bits).  Positions are 1-based.  With F = orc_pf and kT in kcal/mol, exactly
+ *   P(fi,fj) = 1 - exp(-(F[not (fi,fj)] - F) / kT),   sum_j P(fi,j) = 1 - exp(-(F[not fi] - F) / kT):
+ * pair probabilities without an outside recursion (tests/pair_prob_ref.py).  _batch: m masks on one sequence, OpenMP over the
+ * masks with the thread count of the environment. */
+double orc_pf_forbid(const orc_params *P, const char *seq, int n, int fi, int fj);
+void orc_pf_forbid_batch(const orc_params *P, const char *seq, int n, int m, const int32_t *fi, const int32_t *fj, double *F);
+
 /* get_pk_struct(): greedy pseudoknot annotation by up to three constrained re-folds */
 void orc_pk_struct(const orc_params *P, const char *seq, int n, const char *ss_nopk, char *ss_pk);
 
@@ -76,6 +85,10 @@ void orc_score_batch(const orc_params *P, int R, int L, const char *seqs, int n_
  * and energy (dcal/mol); fc.pf_dimer() -> out[0..3] = FA, FB, FcAB, FAB (kcal/mol; the reference uses [-1] = FAB) */
 int orc_cofold_mfe(const orc_params *P, const char *seq, int n, int cut, char *ss);
 void orc_cofold_pf(const orc_params *P, const char *seq, int n, int cut, double out[4]);
+/* orc_cofold_pf with the mask of orc_pf_forbid (positions over the concatenation); _batch writes out[4 * k .. 4 * k + 3] */
+void orc_cofold_pf_forbid(const orc_params *P, const char *seq, int n, int cut, int fi, int fj, double out[4]);
+void orc_cofold_pf_forbid_batch(const orc_params *P, const char *seq, int n, int cut, int m, const int32_t *fi,
+                                const int32_t *fj, double *out);
 
 /* the two lowest structure energies (dcal/mol; e[1] = 10000000 if there is one structure only) and the number the reference
  * takes from ViennaRNA's subopt for -nd on: energy of the second entry of the sorted list (0 beyond 49 kcal/mol) */

@@ -15,6 +15,15 @@ _LIB = os.path.join(_HERE, "liboracle.so")
 FLAG_PF, FLAG_MFE, FLAG_PK, FLAG_PIN = 1, 2, 4, 8      # FLAG_PIN: bind worker threads to cores for this call (bench.py only)
 
 
+KT = 1.98717e-3 * 310.15                                # kcal/mol at 37 degC, the kT of oracle.c
+
+
+def _masks(fi, fj):
+    fi = np.ascontiguousarray(fi, dtype=np.int32)
+    fj = np.ascontiguousarray(np.broadcast_to(np.asarray(fj, dtype=np.int32), fi.shape))
+    return fi, fj
+
+
 def build(force=False):
     if force or not os.path.exists(_LIB) or (
             os.path.getmtime(_LIB) < max(os.path.getmtime(os.path.join(_HERE, f)) for f in ("oracle.c", "oracle.h"))):
@@ -141,6 +150,53 @@ class Oracle:
         self._L.orc_cofold_pf.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
         self._L.orc_cofold_pf(self._P, s.encode(), len(s), len(a), out)
         return tuple(out)
+
+    def pf_forbid(self, seq, fi, fj=0):
+        """orc_pf with a mask on the pair-type look-up (1-based positions): fj > 0 forbids the pair (fi, fj), fj == 0 every pair
+        of fi, fi == 0 nothing (the bits of pf()).  fi an int -> float; fi, fj sequences -> float64[m], one fill per mask,
+        OpenMP over the masks (thread count from the environment)."""
+        if np.ndim(fi) == 0:
+            self._L.orc_pf_forbid.restype = C.c_double
+            self._L.orc_pf_forbid.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
+            return self._L.orc_pf_forbid(self._P, seq.encode(), len(seq), int(fi), int(fj))
+        fi, fj = _masks(fi, fj)
+        F = np.zeros(fi.size)
+        self._L.orc_pf_forbid_batch.restype = None
+        self._L.orc_pf_forbid_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._L.orc_pf_forbid_batch(self._P, seq.encode(), len(seq), fi.size, fi.ctypes.data, fj.ctypes.data, F.ctypes.data)
+        return F
+
+    def cofold_pf_forbid(self, seq_with_amp, fi, fj=0):
+        """cofold_pf with the mask of pf_forbid (positions over the concatenation, '&' not counted).  fi an int -> the 4-tuple;
+        fi, fj sequences -> float64[m, 4]"""
+        a, b = seq_with_amp.split("&")
+        s = (a + b).encode()
+        if np.ndim(fi) == 0:
+            out = (C.c_double * 4)()
+            self._L.orc_cofold_pf_forbid.restype = None
+            self._L.orc_cofold_pf_forbid.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+            self._L.orc_cofold_pf_forbid(self._P, s, len(s), len(a), int(fi), int(fj), out)
+            return tuple(out)
+        fi, fj = _masks(fi, fj)
+        out = np.zeros((fi.size, 4))
+        self._L.orc_cofold_pf_forbid_batch.restype = None
+        self._L.orc_cofold_pf_forbid_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
+        self._L.orc_cofold_pf_forbid_batch(self._P, s, len(s), len(a), fi.size, fi.ctypes.data, fj.ctypes.data, out.ctypes.data)
+        return out
+
+    def pair_probs_by_forbidding(self, seq, pairs=(), bases=()):
+        """Pair probabilities WITHOUT an outside recursion (seq with '&': two strands, ensemble of cofold_pf's FAB):
+            P(i,j) = 1 - exp(-(F[not (i,j)] - F) / kT)   for each (i, j) of `pairs`,
+            sum_j P(i,j) = 1 - exp(-(F[not i] - F) / kT) for each i of `bases`
+        as (float64[len(pairs)], float64[len(bases)]), from one masked fill each; -expm1 of the free-energy difference, never a
+        difference of partition functions, so a probability of 1e-12 keeps its digits."""
+        pairs, bases = list(pairs), list(bases)
+        fi = [p[0] for p in pairs] + bases + [0]
+        fj = [p[1] for p in pairs] + [0] * (len(bases) + 1)
+        F = self.cofold_pf_forbid(seq, fi, fj)[:, 3] if "&" in seq else self.pf_forbid(seq, fi, fj)
+        p = -np.expm1(-(F[:-1] - F[-1]) / KT)
+        return p[:len(pairs)], p[len(pairs):]
 
     def two_best(self, seq):
         """the two lowest structure energies in dcal/mol (second = 10000000 if there is only one structure)"""

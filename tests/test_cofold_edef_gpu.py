@@ -1,9 +1,11 @@
 """Two-strand pair probabilities and ensemble defect on the GPU (drna_cofold_ensemble_defect_batch, cofold_outside_kernel):
 -sf Edef and -sf Ed-MFE for heterodimer / homodimer designs.
 
-The reference pins no value here.  The GPU is checked against the CPU emulation of the same kernel source (which
+The reference holds no value here.  This file checks the GPU against the CPU emulation of the same kernel source (which
 tests/test_cofold_edef_emulated.py checks against exhaustive enumeration), against the identities that follow from the
-definition at lengths the enumeration cannot reach, and through the scorer and the command line."""
+definition, and through the scorer and the command line.  The independent values at lengths the enumeration cannot
+reach (1+1 to 150+250) are in tests/test_pair_prob_reference_gpu.py: pair probabilities from forbidden-pair free energies of the
+oracle's inside fill (tests/pair_prob_ref.py)."""
 import os
 import subprocess
 import sys
@@ -129,7 +131,8 @@ def test_identities_long(eng):
 
 
 def test_golden_two_strand_rows(eng, traj_golden, example_inputs):
-    """18+18 is beyond enumeration: this pins consistency (ranges, and the defect recomputed from the returned matrix)"""
+    """the reference's own 18+18 rows: ranges, structural zeros, and the defect recomputed from the returned matrix.  The values
+    themselves at 18+18 are held to an independent reference in tests/test_pair_prob_reference_gpu.py"""
     for run in ("RNA_RNA_complex_design_input", "Homodimer_design_input"):
         tg = example_inputs[run]["sec_struct"][0]
         rows = [r for r in traj_golden if r["run"] == run][:64]
