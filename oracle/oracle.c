@@ -1688,3 +1688,333 @@ int orc_subopt_energy(const orc_params *P, const char *seq, int n) {
   if (e[1] >= INF / 2 || e[1] - e[0] > 4900) return 0;
   return e[1];
 }
+
+/* ---------------------------------------------------------------- K lowest energies: two references for the ranked folds
+ *
+ * The structure set is the one the K-best kernels fold over (desirna_amd/csrc/fold_subopt.hpp): canonical non-crossing pairs;
+ * a pair inside one strand encloses at least TURN nucleotides, a pair that joins the strands (i <= cut < j) any number; an
+ * interior loop (exactly one inner stem, both unpaired stretches inside a strand) holds at most MAXLOOP unpaired nucleotides.
+ * Two equal strands are not reduced by symmetry.  cut = length of the first strand, 0 = one strand.
+ *
+ *   orc_enum_kbest       walks EVERY structure of the set and scores it with orc_eval_structure_cut, nothing else: the root of
+ *                        trust.  Its cost follows the number of structures, not the length (positions without any partner are
+ *                        never branched on).
+ *   orc_count_structures the size of that set by the counting recursion (the decomposition below with 1 for every energy).
+ *   orc_kbest_energies   the serial K-list dynamic programme: orc_two_best's recurrences with lists of K and, for two strands,
+ *                        the nick rules of co_fill.  Sequential loops and sorted inserts; every pair of list entries is
+ *                        combined (no rank cut).
+ */
+#define KB_MAXK 8
+#define KSAME(a, b) (!(cut > 0 && (a) <= cut && (b) > cut))             /* a <= b: no nick between a and b */
+#define KPAIR(i, j) (((j) - (i) > TURN || !KSAME(i, j)) ? PAIR[S[i]][S[j]] : 0)
+
+typedef struct { int v[KB_MAXK]; } topk;
+
+static void tk_clear(topk *t) { for (int r = 0; r < KB_MAXK; r++) t->v[r] = INF; }
+static void tk_put(topk *t, int K, int v) {              /* sorted insert, duplicates kept */
+  if (v >= INF / 2) return;
+  for (int r = 0; r < K; r++)
+    if (v < t->v[r]) { int x = t->v[r]; t->v[r] = v; v = x; }
+}
+static void tk_put_sum(topk *t, int K, const topk *x, int e) {
+  for (int a = 0; a < K && x->v[a] < INF / 2; a++) tk_put(t, K, x->v[a] + e);
+}
+static void tk_put_sum2(topk *t, int K, const topk *x, const topk *y, int e) {
+  for (int a = 0; a < K && x->v[a] < INF / 2; a++)
+    for (int b = 0; b < K && y->v[b] < INF / 2; b++) tk_put(t, K, x->v[a] + y->v[b] + e);
+}
+
+static char *upper_seq(const char *seq, int n) {
+  char *up = (char *)malloc((size_t)n + 1);
+  for (int i = 0; i < n; i++) {
+    char ch = seq[i];
+    ch = (ch >= 'a' && ch <= 'z') ? (char)(ch - 32) : ch;
+    up[i] = (ch == 'T') ? 'U' : ch;
+  }
+  up[n] = 0;
+  return up;
+}
+
+int orc_kbest_energies(const orc_params *P, const char *seq, int n, int cut, int K, int32_t *E) {
+  if (K < 1 || K > KB_MAXK || n < 1 || cut < 0 || cut >= n) return 0;
+  const int W = n + 2;
+  size_t W2 = (size_t)W * (size_t)W;
+  int *S = encode_seq(seq, n);
+  char *up = upper_seq(seq, n);
+  topk *C = (topk *)malloc(W2 * sizeof(topk)), *M = (topk *)malloc(W2 * sizeof(topk)), *M2 = (topk *)malloc(W2 * sizeof(topk));
+  topk *Fu = (topk *)malloc(sizeof(topk) * (size_t)(n + 2)), *Fc = (topk *)malloc(sizeof(topk) * (size_t)(n + 2));
+  topk *fcA = (topk *)malloc(sizeof(topk) * (size_t)(n + 3)), *fcB = (topk *)malloc(sizeof(topk) * (size_t)(n + 3));
+  for (size_t k = 0; k < W2; k++) { tk_clear(&C[k]); tk_clear(&M[k]); tk_clear(&M2[k]); }
+  for (int k = 0; k < n + 3; k++) { tk_clear(&fcA[k]); tk_clear(&fcB[k]); }
+  if (cut > 0) {
+    /* the empty decompositions, and the single nucleotide next to the nick */
+    fcA[cut + 1].v[0] = 0; fcA[cut].v[0] = 0;
+    fcB[cut].v[0] = 0; fcB[cut + 1].v[0] = 0;
+  }
+  for (int d = (cut > 0 ? 1 : TURN + 1); d < n; d++) {
+    for (int i = 1; i + d <= n; i++) {
+      const int j = i + d;
+      const int same = KSAME(i, j), adj_i = KSAME(i, i + 1), adj_j = KSAME(j - 1, j);
+      const int t = KPAIR(i, j);
+      topk c, m, m2;
+      tk_clear(&c); tk_clear(&m); tk_clear(&m2);
+      if (t) {
+        if (same) tk_put(&c, K, E_Hairpin(P, j - i - 1, t, S[i + 1], S[j - 1], up + i - 1));
+        else      /* the loop that holds the nick: exterior-like */
+          tk_put_sum2(&c, K, &fcA[i + 1], &fcB[j - 1], E_ExtLoop(P, RTYPE[t], adj_j ? S[j - 1] : -1, adj_i ? S[i + 1] : -1));
+        for (int p = i + 1; p <= MIN2(j - 2, i + MAXLOOP + 1); p++) {
+          if (!KSAME(i, p)) break;
+          for (int q = j - 1; q > p; q--) {
+            if (p - i - 1 + j - q - 1 > MAXLOOP) break;
+            if (!KSAME(q, j)) break;
+            int t2 = KPAIR(p, q);
+            if (!t2) continue;
+            tk_put_sum(&c, K, &C[IDX(p, q)], E_IntLoop(P, p - i - 1, j - q - 1, t, RTYPE[t2], S[i + 1], S[j - 1], S[p - 1], S[q + 1]));
+          }
+        }
+        if (adj_i && adj_j && d >= 2)
+          tk_put_sum(&c, K, &M2[IDX(i + 1, j - 1)], P->MLclosing + E_MLstem(P, RTYPE[t], S[j - 1], S[i + 1]));
+      }
+      C[IDX(i, j)] = c;
+      if (adj_j) {
+        tk_put_sum(&m, K, &M[IDX(i, j - 1)], P->MLbase);
+        tk_put_sum(&m2, K, &M2[IDX(i, j - 1)], P->MLbase);
+      }
+      for (int k = i; k < j; k++) {
+        int tk = KPAIR(k, j);
+        if (!tk) continue;
+        const topk *ck = &C[IDX(k, j)];
+        if (ck->v[0] >= INF / 2) continue;
+        int st = E_MLstem(P, tk, (k > 1 && KSAME(k - 1, k)) ? S[k - 1] : -1, (j < n && KSAME(j, j + 1)) ? S[j + 1] : -1);
+        if (KSAME(i, k)) tk_put_sum(&m, K, ck, (k - i) * P->MLbase + st);
+        if (k > i && KSAME(k - 1, k)) {
+          tk_put_sum2(&m, K, &M[IDX(i, k - 1)], ck, st);
+          tk_put_sum2(&m2, K, &M[IDX(i, k - 1)], ck, st);
+        }
+      }
+      M[IDX(i, j)] = m;
+      M2[IDX(i, j)] = m2;
+    }
+    if (cut > 0) {
+      /* exterior decompositions next to the nick, one entry per diagonal: [cut-d .. cut] and [cut+1 .. cut+1+d] */
+      if (cut - d >= 1) {
+        const int x = cut - d;
+        topk f;
+        tk_clear(&f);
+        tk_put_sum(&f, K, &fcA[x + 1], 0);
+        for (int k = x + 1; k <= cut; k++) {
+          int t = KPAIR(x, k);
+          if (!t) continue;
+          tk_put_sum2(&f, K, &C[IDX(x, k)], &fcA[k + 1], E_ExtLoop(P, t, x > 1 ? S[x - 1] : -1, k < cut ? S[k + 1] : -1));
+        }
+        fcA[x] = f;
+      }
+      if (cut + 1 + d <= n) {
+        const int y = cut + 1 + d;
+        topk f;
+        tk_clear(&f);
+        tk_put_sum(&f, K, &fcB[y - 1], 0);
+        for (int k = cut + 1; k < y; k++) {
+          int t = KPAIR(k, y);
+          if (!t) continue;
+          tk_put_sum2(&f, K, &fcB[k - 1], &C[IDX(k, y)], E_ExtLoop(P, t, k > cut + 1 ? S[k - 1] : -1, y < n ? S[y + 1] : -1));
+        }
+        fcB[y] = f;
+      }
+    }
+  }
+  /* exterior level.  Two strands: Fu = no pair joins the strands, Fc = exactly one exterior-level pair joins them (two would
+   * cross), so every structure is derived once and DuplexInit goes to the connected ones only */
+  tk_clear(&Fu[0]); Fu[0].v[0] = 0;
+  tk_clear(&Fc[0]);
+  for (int j = 1; j <= n; j++) {
+    topk fu, fc;
+    tk_clear(&fu); tk_clear(&fc);
+    tk_put_sum(&fu, K, &Fu[j - 1], 0);
+    tk_put_sum(&fc, K, &Fc[j - 1], 0);
+    for (int i = j - 1; i >= 1; i--) {
+      int t = KPAIR(i, j);
+      if (!t || C[IDX(i, j)].v[0] >= INF / 2) continue;
+      int ext = E_ExtLoop(P, t, (i > 1 && KSAME(i - 1, i)) ? S[i - 1] : -1, (j < n && KSAME(j, j + 1)) ? S[j + 1] : -1);
+      if (KSAME(i, j)) {
+        tk_put_sum2(&fu, K, &Fu[i - 1], &C[IDX(i, j)], ext);
+        tk_put_sum2(&fc, K, &Fc[i - 1], &C[IDX(i, j)], ext);
+      } else tk_put_sum2(&fc, K, &Fu[i - 1], &C[IDX(i, j)], ext);
+    }
+    Fu[j] = fu; Fc[j] = fc;
+  }
+  topk f = Fu[n];
+  if (cut > 0) tk_put_sum(&f, K, &Fc[n], P->DuplexInit);
+  for (int r = 0; r < K; r++) E[r] = f.v[r];
+  free(S); free(up); free(C); free(M); free(M2); free(Fu); free(Fc); free(fcA); free(fcB);
+  return 1;
+}
+
+/* the decomposition of orc_kbest_energies with the number 1 in place of every energy; saturates at 9e18 */
+long long orc_count_structures(const char *seq, int n, int cut) {
+  if (n < 1 || cut < 0 || cut >= n) return 0;
+  const int W = n + 2;
+  size_t W2 = (size_t)W * (size_t)W;
+  int *S = encode_seq(seq, n);
+  double *C = (double *)calloc(W2, sizeof(double)), *M = (double *)calloc(W2, sizeof(double)), *M2 = (double *)calloc(W2, sizeof(double));
+  double *Fu = (double *)calloc((size_t)n + 2, sizeof(double)), *Fc = (double *)calloc((size_t)n + 2, sizeof(double));
+  double *A = (double *)calloc((size_t)n + 3, sizeof(double)), *B = (double *)calloc((size_t)n + 3, sizeof(double));
+  if (cut > 0) { A[cut + 1] = A[cut] = 1.0; B[cut] = B[cut + 1] = 1.0; }
+  for (int d = (cut > 0 ? 1 : TURN + 1); d < n; d++) {
+    for (int i = 1; i + d <= n; i++) {
+      const int j = i + d;
+      const int same = KSAME(i, j), adj_i = KSAME(i, i + 1), adj_j = KSAME(j - 1, j);
+      double c = 0.0, m = 0.0, m2 = 0.0;
+      if (KPAIR(i, j)) {
+        c = same ? 1.0 : A[i + 1] * B[j - 1];
+        for (int p = i + 1; p <= MIN2(j - 2, i + MAXLOOP + 1); p++) {
+          if (!KSAME(i, p)) break;
+          for (int q = j - 1; q > p; q--) {
+            if (p - i - 1 + j - q - 1 > MAXLOOP) break;
+            if (!KSAME(q, j)) break;
+            if (KPAIR(p, q)) c += C[IDX(p, q)];
+          }
+        }
+        if (adj_i && adj_j && d >= 2) c += M2[IDX(i + 1, j - 1)];
+      }
+      C[IDX(i, j)] = c;
+      if (adj_j) { m = M[IDX(i, j - 1)]; m2 = M2[IDX(i, j - 1)]; }
+      for (int k = i; k < j; k++) {
+        if (!KPAIR(k, j)) continue;
+        double ck = C[IDX(k, j)];
+        if (KSAME(i, k)) m += ck;
+        if (k > i && KSAME(k - 1, k)) { m += M[IDX(i, k - 1)] * ck; m2 += M[IDX(i, k - 1)] * ck; }
+      }
+      M[IDX(i, j)] = m;
+      M2[IDX(i, j)] = m2;
+    }
+    if (cut > 0) {
+      if (cut - d >= 1) {
+        const int x = cut - d;
+        double f = A[x + 1];
+        for (int k = x + 1; k <= cut; k++) if (KPAIR(x, k)) f += C[IDX(x, k)] * A[k + 1];
+        A[x] = f;
+      }
+      if (cut + 1 + d <= n) {
+        const int y = cut + 1 + d;
+        double f = B[y - 1];
+        for (int k = cut + 1; k < y; k++) if (KPAIR(k, y)) f += B[k - 1] * C[IDX(k, y)];
+        B[y] = f;
+      }
+    }
+  }
+  Fu[0] = 1.0;
+  for (int j = 1; j <= n; j++) {
+    double fu = Fu[j - 1], fc = Fc[j - 1];
+    for (int i = j - 1; i >= 1; i--) {
+      if (!KPAIR(i, j)) continue;
+      if (KSAME(i, j)) { fu += Fu[i - 1] * C[IDX(i, j)]; fc += Fc[i - 1] * C[IDX(i, j)]; }
+      else fc += Fu[i - 1] * C[IDX(i, j)];
+    }
+    Fu[j] = fu; Fc[j] = fc;
+  }
+  double tot = Fu[n] + Fc[n];
+  free(S); free(C); free(M); free(M2); free(Fu); free(Fc); free(A); free(B);
+  return tot >= 9e18 ? (long long)9e18 : (long long)(tot + 0.5);
+}
+
+typedef struct {
+  const orc_params *P;
+  const char *seq;
+  const int *S;
+  int n, cut, K, kept;
+  const unsigned char *ok;   /* (n+2)^2: the pair (i,j) exists */
+  const int *nextp;          /* smallest position >= i that has a partner at all (n + 1: none) */
+  char *db;                  /* the structure under construction */
+  int *stk, *pt;
+  int32_t *E;
+  char *ss;                  /* K strings of n characters */
+  long long count;
+} enumctx;
+
+/* an interior loop of more than MAXLOOP unpaired nucleotides?  (a structural test: no energy is computed here) */
+static int en_long_interior(enumctx *X) {
+  const int n = X->n, cut = X->cut;
+  int sp = 0, *pt = X->pt;
+  for (int i = 1; i <= n; i++) {
+    pt[i] = 0;
+    if (X->db[i - 1] == '(') X->stk[sp++] = i;
+    else if (X->db[i - 1] == ')') { int o = X->stk[--sp]; pt[o] = i; pt[i] = o; }
+  }
+  for (int i = 1; i <= n; i++) {
+    if (pt[i] <= i) continue;
+    const int j = pt[i];
+    int stems = 0, fp = 0, fq = 0;
+    for (int p = i + 1; p < j;) {
+      if (pt[p] > p) { if (!stems) { fp = p; fq = pt[p]; } stems++; p = pt[p] + 1; }
+      else p++;
+    }
+    if (stems == 1 && KSAME(i, fp) && KSAME(fq, j) && fp - i - 1 + j - fq - 1 > MAXLOOP) return 1;
+  }
+  return 0;
+}
+
+static void en_visit(enumctx *X) {
+  if (en_long_interior(X)) return;
+  X->count++;
+  const int n = X->n, K = X->K;
+  const int e = orc_eval_structure_cut(X->P, X->seq, X->db, n, X->cut);
+  /* keep the K lowest, ties by string */
+  int pos = X->kept;
+  while (pos > 0 && (e < X->E[pos - 1] || (e == X->E[pos - 1] && memcmp(X->db, X->ss + (size_t)(pos - 1) * n, (size_t)n) < 0))) pos--;
+  if (pos >= K) return;
+  const int last = X->kept < K ? X->kept : K - 1;
+  for (int r = last; r > pos; r--) {
+    X->E[r] = X->E[r - 1];
+    memcpy(X->ss + (size_t)r * n, X->ss + (size_t)(r - 1) * n, (size_t)n);
+  }
+  X->E[pos] = e;
+  memcpy(X->ss + (size_t)pos * n, X->db, (size_t)n);
+  if (X->kept < K) X->kept++;
+}
+
+typedef struct encell { int i, j; const struct encell *next; } encell;
+
+/* every structure of [i..j], then of the intervals that follow: the first position that can pair is unpaired, or pairs with k */
+static void en_rec(enumctx *X, int i, int j, const encell *next) {
+  const int W = X->n + 2;
+  const int p = i <= j ? X->nextp[i] : j + 1;
+  if (p > j) {
+    if (next) en_rec(X, next->i, next->j, next->next);
+    else en_visit(X);
+    return;
+  }
+  en_rec(X, p + 1, j, next);
+  for (int k = p + 1; k <= j; k++) {
+    if (!X->ok[IDX(p, k)]) continue;
+    X->db[p - 1] = '('; X->db[k - 1] = ')';
+    encell rest = {k + 1, j, next};
+    en_rec(X, p + 1, k - 1, &rest);
+    X->db[p - 1] = '.'; X->db[k - 1] = '.';
+  }
+}
+
+int orc_enum_kbest(const orc_params *P, const char *seq, int n, int cut, int K, int32_t *E, char *ss, long long *count) {
+  if (K < 1 || n < 1 || cut < 0 || cut >= n) return 0;
+  const int W = n + 2;
+  int *S = encode_seq(seq, n);
+  unsigned char *ok = (unsigned char *)calloc((size_t)W * (size_t)W, 1);
+  int *nextp = (int *)malloc(sizeof(int) * (size_t)(n + 3));
+  unsigned char *any = (unsigned char *)calloc((size_t)n + 2, 1);
+  for (int i = 1; i <= n; i++)
+    for (int j = i + 1; j <= n; j++)
+      if (KPAIR(i, j)) { ok[IDX(i, j)] = 1; any[i] = 1; }
+  nextp[n + 1] = nextp[n + 2] = n + 1;
+  for (int i = n; i >= 1; i--) nextp[i] = any[i] ? i : nextp[i + 1];
+  enumctx X = {P, seq, S, n, cut, K, 0, ok, nextp, NULL, NULL, NULL, E, ss, 0};
+  X.db = (char *)malloc((size_t)n + 1);
+  memset(X.db, '.', (size_t)n);
+  X.db[n] = 0;
+  X.stk = (int *)malloc(sizeof(int) * (size_t)(n + 2));
+  X.pt = (int *)malloc(sizeof(int) * (size_t)(n + 2));
+  for (int r = 0; r < K; r++) { E[r] = INF; memset(ss + (size_t)r * n, '.', (size_t)n); }
+  en_rec(&X, 1, n, NULL);
+  if (count) *count = X.count;
+  free(S); free(ok); free(nextp); free(any); free(X.db); free(X.stk); free(X.pt);
+  return 1;
+}

@@ -95,6 +95,20 @@ void orc_cofold_pf_forbid_batch(const orc_params *P, const char *seq, int n, int
 int orc_two_best(const orc_params *P, const char *seq, int n, int e[2]);
 int orc_subopt_energy(const orc_params *P, const char *seq, int n);
 
+/* The K lowest structure energies of one strand (cut = 0) or of two strands (seq = both without '&', cut = length of the
+ * first), over the structure set of the K-best kernels: canonical non-crossing pairs, at least 3 nucleotides enclosed by a pair
+ * inside a strand, any number by a pair that joins the strands, at most 30 unpaired nucleotides in an interior loop, no symmetry
+ * reduction for two equal strands.  Energies in dcal/mol, ascending, 10000000 where the set has fewer structures.
+ *   orc_enum_kbest        every structure, each scored by orc_eval_structure_cut and by nothing else; ties by string; ss = K
+ *                         strings of n characters (no terminator); *count = number of structures visited
+ *   orc_count_structures  the size of the set (counting recursion; saturates at 9e18), to bound a case before it is enumerated
+ *   orc_kbest_energies    serial K-list dynamic programme (K = 1 .. 8): orc_two_best's recurrences with lists of K, two strands
+ *                         with the nick rules of orc_cofold_mfe; duplicates stay in the lists
+ * Not pinned by the reference; orc_kbest_energies is held to orc_enum_kbest in tests/test_kbest_reference.py. */
+int orc_enum_kbest(const orc_params *P, const char *seq, int n, int cut, int K, int32_t *E, char *ss, long long *count);
+long long orc_count_structures(const char *seq, int n, int cut);
+int orc_kbest_energies(const orc_params *P, const char *seq, int n, int cut, int K, int32_t *E);
+
 /* table dumps for kernel-level parity tests: c / fML as (n+2)*(n+2) row-major int32 */
 int orc_mfe_tables(const orc_params *P, const char *seq, int n, const unsigned char *nopair,
                    int32_t *c, int32_t *fML, int32_t *f5);

@@ -68,6 +68,13 @@ class Oracle:
                                       C.c_uint, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_mfe_tables.restype = C.c_int
         L.orc_mfe_tables.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # (set once here: the tests call these three from several threads)
+        L.orc_kbest_energies.restype = C.c_int
+        L.orc_kbest_energies.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.orc_count_structures.restype = C.c_longlong
+        L.orc_count_structures.argtypes = [C.c_char_p, C.c_int, C.c_int]
+        L.orc_enum_kbest.restype = C.c_int
+        L.orc_enum_kbest.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         blob = np.ascontiguousarray(blob, dtype=np.int32)
         self._P = L.orc_params_create(blob.ctypes.data, blob.size)
         if not self._P:
@@ -209,6 +216,40 @@ class Oracle:
         self._L.orc_subopt_energy.restype = C.c_int
         self._L.orc_subopt_energy.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         return self._L.orc_subopt_energy(self._P, seq.encode(), len(seq))
+
+    @staticmethod
+    def _flat_cut(seq):
+        """'A&B' -> (AB, len(A)); one strand -> (seq, 0)"""
+        if "&" in seq:
+            a, b = seq.split("&")
+            return a + b, len(a)
+        return seq, 0
+
+    def kbest_energies(self, seq, K=8):
+        """the K lowest structure energies (dcal/mol, ascending, 10000000 = no such structure) by the serial K-list fill;
+        seq with '&': two strands"""
+        s, cut = self._flat_cut(seq)
+        E = np.zeros(K, dtype=np.int32)
+        if not self._L.orc_kbest_energies(self._P, s.encode(), len(s), cut, K, E.ctypes.data):
+            raise ValueError("kbest_energies: bad arguments")
+        return [int(e) for e in E]
+
+    def count_structures(self, seq):
+        """number of structures of the set the ranked folds range over (seq with '&': two strands)"""
+        s, cut = self._flat_cut(seq)
+        return int(self._L.orc_count_structures(s.encode(), len(s), cut))
+
+    def enum_kbest(self, seq, K=8):
+        """exhaustive enumeration: (K lowest energies, their strings without '&', number of structures visited); ties by string"""
+        s, cut = self._flat_cut(seq)
+        n = len(s)
+        E = np.zeros(K, dtype=np.int32)
+        ss = np.zeros(K * n, dtype=np.uint8)
+        cnt = C.c_longlong(0)
+        if not self._L.orc_enum_kbest(self._P, s.encode(), n, cut, K, E.ctypes.data, ss.ctypes.data, C.byref(cnt)):
+            raise ValueError("enum_kbest: bad arguments")
+        raw = ss.tobytes().decode("ascii")
+        return [int(e) for e in E], [raw[k * n:(k + 1) * n] for k in range(K)], cnt.value
 
     def simscore(self, ref, query):
         out = (C.c_double * 3)()

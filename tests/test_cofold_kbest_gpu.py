@@ -98,6 +98,7 @@ def test_energies_and_strings_long(eng, oracle, la, R, K):
         row = [int(e) for e in E[k]]
         assert row[0] == int(mfe[k]), s
         assert row[:2] == [int(E12[k, 0]), int(E12[k, 1])], s
+        assert row == oracle.kbest_energies(s, K), s                   # every rank: the oracle's serial K-list fill
         assert row[K - 1] < INF_REF, s                                 # (random pairs of this size have far more than K structures)
         _check_strings(oracle, s, row, ss[k])
 

@@ -445,6 +445,7 @@ def test_ranked_structures(eng400, oracle):
             assert e == sorted(e), s
             two = oracle.two_best(s)
             assert e[0] == oracle.mfe(s)[1] == two[0] and (K < 2 or e[1] == two[1]), s
+            assert e == oracle.kbest_energies(s, K), s                  # every rank: the oracle's serial K-list fill
             real = [x for x, v in zip(ss[k], e) if v < 10000000]
             assert len(set(real)) == len(real), s
             for x, v in zip(ss[k], e):
