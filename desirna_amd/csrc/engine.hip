@@ -29,6 +29,7 @@
 #include "fold_pf.hpp"
 #include "fold_pf_lds.hpp"
 #include "fold_pf_strip.hpp"
+#include "fold_sample.hpp"
 #include "fold_subopt.hpp"
 #include "fold_cofold_subopt.hpp"
 #include "fold_subopt_lds.hpp"
@@ -87,6 +88,9 @@ struct drna_engine {
   hipEvent_t ev_o0 = nullptr, ev_o1 = nullptr, ev_o2 = nullptr;
   hipEvent_t ev_gate = nullptr;                // the partition function's launch waits for it (see pf_gate_round)
   float timing_edef[2] = {0, 0};
+  // stochastic traceback (fold_sample.hpp): the q5 columns of ws_slots sequences, allocated on first use
+  double* d_q5s = nullptr;
+  int sample_calls = 0;     // launches of sample_kernel (read-only option "sample_calls")
   // ragged batches: per-sequence descriptors (len, off, target, two index lists) and the structures' pair tables.  Three blocks
   // of 7 max_R ints (rg_block): a lock-step loop keeps its scoring plan, its ensemble-defect plan and the second-best fold's
   // lists on the device side by side
@@ -392,7 +396,7 @@ extern "C" void drna_destroy(drna_engine* e) {
   void* bufs[] = {e->d_mfeT, e->d_pfT, e->d_plan, e->d_hp_len, e->d_bulge_len, e->d_int_len, e->d_hp_w, e->d_scale,
                   e->d_eMLb, e->d_ws_mfe, e->d_ws_pf, e->d_seqs, e->d_Epf, e->d_Emfe, e->d_ss, e->d_Ed, e->d_pt,
                   e->d_ws_out, e->d_edef, e->d_rg, e->d_rpt, e->d_rpt_off, e->d_F4, e->d_ws_kb, e->d_kbE, e->d_kbss,
-                  e->dflags.d, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->sflags.d, e->d_srec, e->d_sdbg, e->d_sclk, e->pflags.d};
+                  e->dflags.d, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->sflags.d, e->d_srec, e->d_sdbg, e->d_sclk, e->pflags.d, e->d_q5s};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_status) (void)hipHostFree(e->h_status);
@@ -453,6 +457,7 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "edef_lds_max")) { *value = EDEF_LDS_HOST_MAX; return DRNA_OK; }     // what the host sends there; the kernel holds EDEF_LDS_MAX
   if (!strcmp(name, "cofold_edef_lds_max")) { *value = CO_EDEF_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "edef_lds_calls")) { *value = e->edef_lds_calls; return DRNA_OK; }
+  if (!strcmp(name, "sample_calls")) { *value = e->sample_calls; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds")) { *value = e->subopt_lds ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds_max")) { *value = SUB_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "self_dimer_lds")) { *value = e->self_dimer_lds ? 1 : 0; return DRNA_OK; }
@@ -1105,6 +1110,83 @@ extern "C" int drna_last_edef_timing(const drna_engine* e, float out[2]) {
   if (!e || !out) return DRNA_ERR_ARG;
   out[0] = e->timing_edef[0]; out[1] = e->timing_edef[1];
   return DRNA_OK;
+}
+
+// ---------------------------------------------------------------- stochastic traceback (fold_sample.hpp)
+
+constexpr int SAMPLE_NT = 256;      // four waves, i.e. four samples in flight per workgroup (56 KB of LDS: two workgroups per CU)
+
+// m sequences that fit the workspaces (the caller's r_base, r_base + 1, ...): pf_kernel, then sample_kernel on its tables, both on
+// the partition function's stream and timed as the ensemble defect's two launches are (timing_edef).  G workgroups per sequence so
+// that the chip is covered twice over (a wave takes the samples of its stride one after the other).
+static int sample_impl(drna_engine* e, int m, int L, int S, const char* d_seqs, const uint64_t* d_seeds, char* d_ss, int32_t* d_E,
+                       int r_base) {
+  const int ld = L + 2;
+  SampleArgs a{};
+  a.pf = pf_args(e, d_seqs, L, ld, e->d_Epf);
+  a.pf.q5out = e->d_q5s; a.pf.q5_stride = ld;
+  a.ev = eval_args(e, d_seqs, L, nullptr);
+  a.seeds = d_seeds; a.S = S; a.ss = d_ss; a.E = d_E;
+  constexpr int NW = SAMPLE_NT / WAVE;
+  a.G = std::max(1, std::min((S + NW - 1) / NW, (4 * e->cus + m - 1) / m));
+  e->sample_calls++;
+  return inside_outside(e, m, r_base, "unexpected status of the partition function",
+                        [&] { hipLaunchKernelGGL(pf_kernel<1024>, dim3(m), dim3(1024), 0, e->s_pf, a.pf); },
+                        [&] { hipLaunchKernelGGL(sample_kernel<SAMPLE_NT>, dim3(m * a.G), dim3(SAMPLE_NT), 0, e->s_pf, a); });
+}
+
+// chunks of the workspace slots (and of max_R: the staging buffer and the status words), one pf_kernel and one sample launch each
+static int sample_batch_host(drna_engine* e, int R, int L, const char* seqs, int S, const uint64_t* seeds, char* ss, int32_t* E,
+                             double* Epf, uint64_t* d_seeds, char* d_ss, int32_t* d_E, int step) {
+  float sum[2] = {0, 0};
+  for (int r0 = 0; r0 < R; r0 += step) {
+    const int m = std::min(step, R - r0);
+    const size_t cells = (size_t)m * S;
+    HIP_TRY(hipMemcpy(e->d_seqs, seqs + (size_t)r0 * L, (size_t)m * L, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_seeds, seeds + r0, (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice));
+    const int rc = sample_impl(e, m, L, S, e->d_seqs, d_seeds, d_ss, E ? d_E : nullptr, r0);
+    if (rc != DRNA_OK) return rc;
+    sum[0] += e->timing_edef[0]; sum[1] += e->timing_edef[1];
+    HIP_TRY(hipMemcpy(ss + (size_t)r0 * S * L, d_ss, cells * L, hipMemcpyDeviceToHost));
+    if (E) HIP_TRY(hipMemcpy(E + (size_t)r0 * S, d_E, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (Epf) HIP_TRY(hipMemcpy(Epf + r0, e->d_Epf, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  e->timing_edef[0] = sum[0]; e->timing_edef[1] = sum[1];
+  return DRNA_OK;
+}
+
+extern "C" int drna_sample_structures_batch(drna_engine* e, int R, int L, const char* seqs, int S, const uint64_t* seeds, char* ss,
+                                            int32_t* E, double* Epf) {
+  if (!e) return DRNA_ERR_ARG;
+  const char* who = "drna_sample_structures_batch";
+  { const int rc = aux_check(e, who, std::min(R, e->max_R), L, nullptr, S >= 1 && seqs && seeds && ss, "S >= 1; seqs, seeds and ss required");
+    if (rc != DRNA_OK) return rc; }
+  if ((long long)R * S > (long long)DRNA_SAMPLE_MAX_CHARS / L) {
+    e->err = std::string(who) + ": R x S x L above DRNA_SAMPLE_MAX_CHARS";
+    return DRNA_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->d_q5s) {
+    const size_t b = (size_t)e->ws_slots * (e->max_L + 2) * sizeof(double);
+    HIP_TRY(hipMalloc((void**)&e->d_q5s, b));
+    e->ws_bytes += b;
+  }
+  const int step = std::min(std::min(e->ws_slots, e->max_R), R);
+  uint64_t* d_seeds = nullptr;
+  char* d_ss = nullptr;
+  int32_t* d_E = nullptr;
+  int rc = DRNA_OK;
+  if (hipMalloc((void**)&d_seeds, (size_t)step * sizeof(uint64_t)) != hipSuccess ||
+      hipMalloc((void**)&d_ss, (size_t)step * S * L) != hipSuccess ||
+      hipMalloc((void**)&d_E, (size_t)step * S * sizeof(int32_t)) != hipSuccess) {
+    e->err = std::string(who) + ": hipMalloc of the sample buffers failed";
+    rc = DRNA_ERR_DEVICE;
+  }
+  if (rc == DRNA_OK) rc = sample_batch_host(e, R, L, seqs, S, seeds, ss, E, Epf, d_seeds, d_ss, d_E, step);
+  if (d_seeds) (void)hipFree(d_seeds);
+  if (d_ss) (void)hipFree(d_ss);
+  if (d_E) (void)hipFree(d_E);
+  return rc;
 }
 
 // ---------------------------------------------------------------- ragged batches (sequences of different lengths)

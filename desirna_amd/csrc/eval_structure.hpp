@@ -147,26 +147,11 @@ __device__ inline int eval_loop(const EvalSmem& sm, const EvalArgs& A, int i, in
   return T.MLclosing + T.MLintern + (tc > 2 ? T.TermAU : 0) + eval_mm(T.mmM, tc, sj1, si1) + unp * T.MLbase + e_stems;
 }
 
-// one (sequence, structure) evaluation by one wave; `sm` is that wave's own (the wave synchronises its LDS traffic itself, so
-// this also runs inside a larger workgroup: the helper workgroups of pf_lds_kernel evaluate their sequence while they wait for
-// the first rows of the fill)
-__device__ __forceinline__ void eval_one(EvalSmem& sm, EvalArgs A, int r, int k, int lane) {
+// energy of the structure whose pair table (sm.pt[0 .. n+1]) and codes (sm.S[0 .. n+1], wrap ends set) the wave has put into its
+// sm, every lane's LDS stores done (wave_lds_sync): the sum of the loops and the exterior stems, the same value in every lane.
+// The stochastic traceback (fold_sample.hpp) scores the structure it has just drawn with it.
+__device__ __forceinline__ int eval_loaded(const EvalSmem& sm, const EvalArgs& A, int n, int lane) {
   const MfeTables& T = *A.T;
-  const bool ragged = A.rg.len != nullptr;
-  if (ragged) A.L = A.rg.len[r];
-  const int n = A.L;
-  const char* seq = A.seqs + (ragged ? (long long)A.rg.off[r] : (long long)r * n);
-  const short* pt = ragged ? A.pt + A.pt_off[A.target_of[r]] : A.pt + (long long)k * (n + 2);
-  bool bad = false;
-  for (int x = lane; x < n; x += WAVE) {
-    const int c = enc_nt(seq[x]);
-    bad |= c < 0;
-    sm.S[x + 1] = (unsigned char)(c < 0 ? 0 : c);
-  }
-  for (int x = lane; x < n + 2; x += WAVE) sm.pt[x] = pt[x];
-  wave_lds_sync();
-  if (lane == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
-  wave_lds_sync();
   int e = 0;
   for (int i = lane + 1; i <= n; i += WAVE)
     if (sm.pt[i] > i) e += eval_loop(sm, A, i, sm.pt[i]);
@@ -184,7 +169,29 @@ __device__ __forceinline__ void eval_one(EvalSmem& sm, EvalArgs A, int r, int k,
       } else i++;
     }
   }
-  e = wave_sum_i32(e);
+  return wave_sum_i32(e);
+}
+
+// one (sequence, structure) evaluation by one wave; `sm` is that wave's own (the wave synchronises its LDS traffic itself, so
+// this also runs inside a larger workgroup: the helper workgroups of pf_lds_kernel evaluate their sequence while they wait for
+// the first rows of the fill)
+__device__ __forceinline__ void eval_one(EvalSmem& sm, EvalArgs A, int r, int k, int lane) {
+  const bool ragged = A.rg.len != nullptr;
+  if (ragged) A.L = A.rg.len[r];
+  const int n = A.L;
+  const char* seq = A.seqs + (ragged ? (long long)A.rg.off[r] : (long long)r * n);
+  const short* pt = ragged ? A.pt + A.pt_off[A.target_of[r]] : A.pt + (long long)k * (n + 2);
+  bool bad = false;
+  for (int x = lane; x < n; x += WAVE) {
+    const int c = enc_nt(seq[x]);
+    bad |= c < 0;
+    sm.S[x + 1] = (unsigned char)(c < 0 ? 0 : c);
+  }
+  for (int x = lane; x < n + 2; x += WAVE) sm.pt[x] = pt[x];
+  wave_lds_sync();
+  if (lane == 0) { sm.S[0] = sm.S[n]; sm.S[n + 1] = sm.S[1]; }
+  wave_lds_sync();
+  const int e = eval_loaded(sm, A, n, lane);
   const unsigned long long anybad = __ballot(bad);
   if (lane == 0) A.Ed[ragged ? (long long)r : (long long)r * A.n_targets + k] = anybad ? INF_REF : e;
   wave_lds_sync();                         // the wave may reuse sm for its next structure

@@ -823,8 +823,48 @@ def _cli_driver(a, inp):
     return (run_design if python_host else run_design_fast), extra
 
 
+def ensemble_report(engine, result, input_file, S, top=5, seed=0):
+    """Where the probability of each reported sequence goes: S structures per sequence drawn from its Boltzmann ensemble
+    (``engine.sample_structures``, one call for the puzzle: the lengths are equal) and counted.  The reported sequences are
+    ``result["reported"]`` (the ranked results the command line has just written) or, without it, the ranking of
+    ``outputs.sort_and_filter`` over the run's records.  Returns the rows of ``<name>_ensemble.csv`` (``outputs.ENSEMBLE_COLUMNS``),
+    per sequence: the ``top`` most frequent structures (kind ``top``, most frequent first, ties by string), a row for the target
+    itself (kind ``target``, count 0 allowed; it repeats a ``top`` row when the target is one of them) and a row ``other`` with the
+    samples that are neither among the top nor the target -- so top + other, plus target where it is not among the top, add up to S.
+    Energies in kcal/mol (the target's, when it was not drawn, from the run's record of the sequence), 1 - MCC to the target by
+    ``HostKernels.simscore``.  One strand only."""
+    from collections import Counter
+    from . import engine as _engine
+    from . import outputs
+    target = input_file.sec_struct
+    if "&" in target:
+        raise ValueError("ensemble_report: one strand only")
+    seqs = list(result.get("reported") or [r["sequence"] for r in outputs.sort_and_filter(result["simulation_data"])])
+    S, top = int(S), int(top)
+    ss, E, Epf = engine.sample_structures(seqs, S, seed)
+    hk = _engine.HostKernels()
+    known = {r["sequence"]: r.get("edesired") for r in result.get("simulation_data") or []}
+    rows = []
+    for r, seq in enumerate(seqs):
+        cnt = Counter(ss[r])
+        energy = {s: int(E[r][k]) / 100.0 for k, s in enumerate(ss[r])}
+        first = sorted(cnt, key=lambda s: (-cnt[s], s))[:top]
+        listed = first + [target]
+        mcc = 1.0 - hk.simscore(target, np.frombuffer("".join(listed).encode("ascii"), dtype=np.uint8).reshape(len(listed), -1))[0]
+        row = lambda kind, rank, s, c, e, m: dict(sequence=seq, Epf=float(Epf[r]), kind=kind, rank=rank, structure=s, count=int(c),
+                                                  frequency=c / S, energy=e, mcc=m)
+        for k, s in enumerate(first):
+            rows.append(row("top", k + 1, s, cnt[s], energy[s], float(mcc[k])))
+        e_t = energy.get(target, known.get(seq))
+        rows.append(row("target", "", target, cnt.get(target, 0), "" if e_t is None else float(e_t), float(mcc[-1])))
+        rest = S - sum(cnt[s] for s in set(first) | {target})
+        rows.append(row("other", "", "", rest, "", ""))
+    return rows
+
+
 def _cli_report(a, filename, inp, res):
-    """What the command line leaves of one finished design: with -o the reference's result files, and the summary lines"""
+    """What the command line leaves of one finished design: with -o the reference's result files (and, with --ensemble, the
+    sampled ensemble of every reported sequence beside them), and the summary lines"""
     if a.outdir:
         import os
         from . import outputs
@@ -837,10 +877,16 @@ def _cli_report(a, filename, inp, res):
         stats = SimpleNamespace(step=st["acc_mc"] + st["rej_mc"], global_step=res["steps"], acc_mc_step=st["acc_mc"],
                                 acc_mc_better_e=st["acc_mc_better"], rej_mc_step=st["rej_mc"], acc_re_step=st["acc_re"],
                                 rej_re_step=st["rej_re"])
-        outputs.write_all(res["simulation_data"], inp.name, os.path.basename(filename), outname, stats, st["elapsed_s"], a.timlim,
-                          time.strftime("%Y%m%d.%H%M%S"), num_results=a.num_results, directory=a.outdir,
-                          alt_sec_structs=list(inp.alt_sec_structs or []) or None, engine=res.get("engine"),
-                          oligo_state=oligo_state, subopt=a.subopt, sec_struct=inp.sec_struct)
+        ranked, _ = outputs.write_all(res["simulation_data"], inp.name, os.path.basename(filename), outname, stats, st["elapsed_s"],
+                                      a.timlim, time.strftime("%Y%m%d.%H%M%S"), num_results=a.num_results, directory=a.outdir,
+                                      alt_sec_structs=list(inp.alt_sec_structs or []) or None, engine=res.get("engine"),
+                                      oligo_state=oligo_state, subopt=a.subopt, sec_struct=inp.sec_struct)
+        if a.ensemble:
+            from . import engine as _engine
+            eng = res.get("engine") or _engine.Engine(max_R=max(1, len(ranked)), max_L=len(inp.sec_struct))
+            rows = ensemble_report(eng, dict(res, reported=[r["sequence"] for r in ranked]), inp, a.ensemble, a.ensemble_top,
+                                   a.ensemble_seed)
+            outputs.write_ensemble(rows, outname, a.outdir)
     b = res["best"]
     print("Design solved succesfully!" if res["solved"] else "Design not solved.")
     print(b.sequence)
@@ -879,7 +925,15 @@ def main(argv=None):
     ap.add_argument("--python-host", action="store_true", help="per-replica Python host loop instead of the native batched one")
     ap.add_argument("-o", "--outdir", default=None, help="write the reference's result files (_results.csv, _traj.csv, "
                     "_stats, _best_str, fasta files) into this directory")
+    ap.add_argument("--ensemble", type=int, default=0, metavar="S", help="after the run, draw S structures from the Boltzmann "
+                    "ensemble of every reported sequence and write <name>_ensemble.csv beside _results.csv (needs -o; one strand)")
+    ap.add_argument("--ensemble-top", type=int, default=5, metavar="T", help="structures listed per sequence, most frequent first")
+    ap.add_argument("--ensemble-seed", type=int, default=0, help="seed of the samples (sequence r of the report: seed + r)")
     a = ap.parse_args(argv)
+    if a.ensemble < 0 or a.ensemble_top < 1:
+        ap.error("--ensemble takes S >= 1 and --ensemble-top T >= 1")
+    if a.ensemble and not a.outdir:
+        ap.error("--ensemble writes its file beside _results.csv: give -o")
     common = dict(replicas=a.replicas, exchange=a.exchange, steps=a.steps, timelimit=a.timlim, t_min=a.t_min, t_max=a.t_max,
                   scoring_f=a.scoring_f, tm_max=a.tm_max, tm_min=a.tm_min, point_mutations=a.pm, seed=a.in_seed,
                   stop_when_solved=a.sws == "on", num_results=a.num_results if a.sws == "on" else None)
@@ -890,6 +944,8 @@ def main(argv=None):
             ap.error(str(err))
     if a.set_files:
         inputs = [read_input(f) for f in a.set_files]
+        if a.ensemble and any("&" in i.sec_struct for i in inputs):
+            ap.error("--ensemble samples one strand: a two-strand input is refused")
         # the switches under run_design_fast's names, so that run_puzzle_set can tell which inputs may share the batch; the
         # per-puzzle driver gets each input's own keywords (_cli_driver)
         switches = dict(negative_design=a.subopt, oligo=a.oligo, **(dict(acgu=True) if a.percs == "on" or a.python_host else {}))
@@ -902,6 +958,8 @@ def main(argv=None):
                        on_result=lambda k, inp, res: _cli_report(a, a.set_files[k], inp, res))
         return
     inp = read_input(a.name)
+    if a.ensemble and "&" in inp.sec_struct:
+        ap.error("--ensemble samples one strand: a two-strand input is refused")
     drv, extra = _cli_driver(a, inp)
     _cli_report(a, a.name, inp, drv(inp, **extra, **common))
 

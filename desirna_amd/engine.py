@@ -75,6 +75,7 @@ _SIGNATURES = {
     "drna_set_motifs": (_ci, [_vp, _ci, _vp, _str, _vp]),
     "drna_rng_seed": (_ci, [_ci, _vp, _vp]),
     "drna_rng_random": (_ci, [_ci, _vp, _vp]),
+    "drna_sample_structures_batch": (_ci, [_vp, _ci, _ci, _str, _ci, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -566,6 +567,35 @@ class Engine:
         self._check(self._L.drna_ensemble_defect_ragged(self._h, R, lens.ctypes.data, flat_u8.ctypes.data_as(C.c_char_p),
                                                         tof.ctypes.data, ed.ctypes.data))
         return ed
+
+    def sample_structures(self, seqs, S, seed=0):
+        """String form of :meth:`sample_structures_arrays`: (R lists of S dot-bracket strings, E (R, S) int32, Epf (R,))."""
+        ss, E, Epf = self.sample_structures_arrays(_as_u8(seqs), S, seed)
+        R, _, L = ss.shape
+        raw = ss.tobytes().decode("ascii")
+        return [[raw[(r * S + k) * L:(r * S + k + 1) * L] for k in range(S)] for r in range(R)], E, Epf
+
+    def sample_structures_arrays(self, seqs_u8, S, seed=0):
+        """S structures per sequence ((R, L) uint8 ASCII letters) drawn from its Boltzmann ensemble (stochastic traceback on the
+        partition function's tables; ViennaRNA's pbacktrack).  Returns (ss (R, S, L) uint8 of ``( ) .``, E (R, S) int32 in
+        dcal/mol, Epf (R,) in kcal/mol).  An integer ``seed`` gives sequence r the seed ``seed + r`` (mod 2^64); an array of R
+        uint64 gives the seeds themselves.  Sample s of a sequence depends on the sequence, its seed and s alone.
+        R is not limited by max_R; ``R * S * L`` is (1 << 30 at most)."""
+        seqs_u8 = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
+        R, L = seqs_u8.shape
+        S = int(S)
+        if np.ndim(seed) == 0:
+            seeds = np.array([(int(seed) + r) % (1 << 64) for r in range(R)], dtype=np.uint64)
+        else:
+            seeds = np.ascontiguousarray(seed, dtype=np.uint64)
+            if seeds.shape != (R,):
+                raise ValueError("seed must be an integer or one uint64 per sequence")
+        ss = np.zeros((R, max(S, 0), L), dtype=np.uint8)
+        E = np.zeros((R, max(S, 0)), dtype=np.int32)
+        Epf = np.zeros(R, dtype=np.float64)
+        self._check(self._L.drna_sample_structures_batch(self._h, R, L, seqs_u8.ctypes.data_as(C.c_char_p), S, seeds.ctypes.data,
+                                                         ss.ctypes.data, E.ctypes.data, Epf.ctypes.data))
+        return ss, E, Epf
 
     def last_edef_timing(self):
         out = (C.c_float * 2)()

@@ -7,6 +7,9 @@ single-chain branch), ``sort_and_filter_simulation_data_alternative`` (:422-460,
 ``round_floats`` (``utils/sequence_utils.py:1254-1274``).  A record is ``vars(ScoreSeq)``: the CSV header is its key order.
 
 Not written: ``_replicas.csv`` (a pandas pivot), the PNG plot, ``_random.csv``.
+
+Beyond the reference: ``_ensemble.csv`` (``--ensemble``), the sampled Boltzmann ensemble of every reported sequence
+(``design.ensemble_report``).
 """
 import csv
 import io
@@ -192,3 +195,24 @@ def write_all(simulation_data, input_name, infile, outname, stats, finish_time, 
     with open(base + '_stats', 'w', newline='\n', encoding='utf-8') as fh:
         fh.write(stats_text(stats, res, ok, finish_time, outname, timlim))
     return res, ok
+
+
+ENSEMBLE_COLUMNS = ("sequence", "Epf", "kind", "rank", "structure", "count", "frequency", "energy", "mcc")
+
+
+def ensemble_csv_text(rows):
+    """rows of design.ensemble_report: per sequence its most frequent sampled structures (kind top), the target and ``other``"""
+    buf = io.StringIO(newline='')
+    w = csv.DictWriter(buf, fieldnames=list(ENSEMBLE_COLUMNS))
+    w.writeheader()
+    for r in rows:
+        w.writerow(round_floats(dict(r)))
+    return buf.getvalue()
+
+
+def write_ensemble(rows, outname, directory="."):
+    import os
+    path = os.path.join(directory, outname + '_ensemble.csv')
+    with open(path, 'w', newline='', encoding='utf-8') as fh:
+        fh.write(ensemble_csv_text(rows))
+    return path

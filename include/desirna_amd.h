@@ -214,6 +214,26 @@ int drna_ensemble_defect_batch(drna_engine *e, int R, int L, const char *seqs, d
 int drna_ensemble_defect_batch_device(drna_engine *e, int R, int L, const char *d_seqs, double *d_edef,
                                       double *d_bpp);
 
+/*
+ * Stochastic traceback: S structures per sequence drawn from its Boltzmann ensemble (ViennaRNA's pbacktrack, RNAsubopt -p),
+ * p(structure) = exp(-E / kT) / Z under the partition function's loop model.  One inside fill (pf_kernel) and one sample launch
+ * per chunk of workspace slots: R is not limited by max_R.  One strand, equal lengths.
+ *   S      >= 1 samples per sequence; R x S x L <= DRNA_SAMPLE_MAX_CHARS, beyond it DRNA_ERR_ARG
+ *   seeds  R uint64.  Sample s of sequence r depends on the sequence, seeds[r] and s ALONE -- not on S, on R, on the neighbours in
+ *          the batch or on the launch: the walk's draw k of sample s is u(seeds[r], s, k) of csrc/sample_rng.hpp (a counter-based
+ *          function without state), so the first S' samples of a call are the S'-sample call
+ *   ss     R x S x L chars of ( ) . (no terminator)                                       out
+ *   E      R x S int32, dcal/mol: drna_score_batch's E(structure) of each sample           out, may be NULL
+ *   Epf    R doubles, kcal/mol: the ensemble free energy of the fill the samples come from out, may be NULL
+ * A sequence with a bad letter is DRNA_ERR_SEQUENCE, a partition function out of range DRNA_ERR_PF_RANGE, as for
+ * drna_ensemble_defect_batch; the outputs are then unspecified.  drna_last_edef_timing afterwards: out[0] = the inside kernel,
+ * out[1] = the sample launch, summed over the chunks.  The read-only option "sample_calls" counts the sample launches.
+ * A new symbol: no existing signature or buffer changes, DRNA_ABI_VERSION stays 3.
+ */
+#define DRNA_SAMPLE_MAX_CHARS (1u << 30)
+int drna_sample_structures_batch(drna_engine *e, int R, int L, const char *seqs, int S, const uint64_t *seeds, char *ss,
+                                 int32_t *E, double *Epf);
+
 /* device ms summed over the drna_score_batch[_device] calls since the last reset: out[0..3] as drna_last_timing, out[4] = number
  * of calls; out may be NULL (reset only).  Lets a caller time a loop of calls without a query per call. */
 int drna_timing_sums(drna_engine *e, double out[5], int reset);

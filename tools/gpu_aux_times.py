@@ -1,5 +1,7 @@
 """GPU box: device times of the auxiliary paths, one JSON line with a section per path (all, or those named as arguments).
 Per shape the first round warms up and the median of the others is kept.
+`sampling` (kept as profiles/sampling.json): the stochastic traceback at R = 64 x L = 200 x S = 1,024 next to the ensemble defect of
+the same sequences, the other consumer of pf_kernel's tables.
 `puzzle_set` (only when named; minutes): the Eterna100 set as a design run, lock-step batch against one puzzle after the other.
 `puzzle_set_aux` (only when named): the same pair for the puzzles of at most 200 nt with -nd on, and with an Edef term added."""
 import json
@@ -19,6 +21,23 @@ def edef(eng, seqs):
     eng.ensemble_defect(seqs)
     t = eng.last_edef_timing()
     return {"inside_ms": t["inside"], "outside_ms": t["outside"]}
+
+
+SAMPLES = 1024
+
+
+def sampling(eng, seqs):
+    """stochastic traceback (pf_kernel + sample_kernel, SAMPLES structures per sequence with their energies) and, in the same
+    round, drna_ensemble_defect_batch on the same sequences (pf_kernel + outside_kernel)"""
+    u8 = np.frombuffer("".join(seqs).encode(), dtype=np.uint8).reshape(len(seqs), -1)
+    c0 = eng.get_option("sample_calls")
+    eng.sample_structures_arrays(u8, SAMPLES, seed=1)
+    t = eng.last_edef_timing()
+    out = {"pf_ms": t["inside"], "sample_ms": t["outside"], "sample_launches": eng.get_option("sample_calls") - c0}
+    eng.ensemble_defect(seqs)
+    t = eng.last_edef_timing()
+    out["edef_ms"] = t["inside"] + t["outside"]
+    return out
 
 
 def cofold_subopt(eng, seqs):
@@ -191,6 +210,8 @@ CO_EDEF_MAX = 57      # CO_EDEF_LDS_MAX
 SECTIONS = {
     edef: (((64, 200), (128, 400)), 20260101, True, 3,
            lambda R, v: ("defects_per_s", R / ((v["inside_ms"] + v["outside_ms"]) * 1e-3))),
+    sampling: (((64, 200),), 20260101, True, 5,
+               lambda R, v: ("samples_per_s", R * SAMPLES / (v["sample_ms"] * 1e-3))),
     cofold_subopt: (PAIRS, 5, False, 5, lambda R, v: ("ratio", v["cofold_subopt_ms"] / v["cofold_mfe_ms"])),
     cofold_edef: (PAIRS, 5, False, 5, lambda R, v: ("ratio", v["cofold_outside_ms"] / v["cofold_pf_ms"])),
     subopt_energy: (((64, 36), (64, SUB_MAX), (64, 18, 18), (64, 100), (64, 200)), 5, False, 5,
