@@ -371,9 +371,11 @@ struct FmlGlobal {
 // Sector containers of the traceback.  TbStack: the private stack of the one-wave traceback (general and strip kernels).  TbShared
 // (round 3, LDS-resident kernels): a queue in LDS that several waves work from -- the sectors of a structure (exterior stems, the
 // branches of a multiloop) are independent, the traceback is ~0.9 us of mostly scalar control flow per event, and one wave took
-// 0.074 of the MFE fold's 0.50 ms at 200 nt with fifteen waves idle.  Entry c is published by its ml + 1 in sec_ml[c] (0 = not
-// written yet); tbq = {next to claim, next free, sectors pushed and not finished, 1 done / 2 failed}.  The caller zeroes sec_ml
-// and tbq and writes entry 0 before the barrier in front of the traceback.
+// 0.074 of the MFE fold's 0.50 ms at 200 nt with fifteen waves idle.  Entry c is ONE word, tbw[c] = word(i, j, ml) (0 = not
+// written yet): payload and flag travel together, so publishing it takes no fence; tbq = {next to claim, next free, sectors pushed
+// and not finished, state: 0 running, 1 done, >= 2 failed (every failing wave adds 2)}.  Every access to a word that another wave
+// polls is an LDS atomic (a volatile access compiles to the flat path, whose wait also waits for the wave's global loads).  The
+// caller zeroes tbw and tbq and writes entry 0 before the barrier in front of the traceback.
 template <class SM> struct TbStack {
   SM& sm;
   int sp = 0;
@@ -391,20 +393,24 @@ template <class SM> struct TbStack {
 };
 template <class SM> struct TbShared {
   SM& sm;
+  static constexpr int CAP = (int)(sizeof(SM::tbw) / sizeof(int));
+  static __host__ __device__ constexpr int word(int i, int j, int ml) { return i | (j << 11) | ((ml + 1) << 22); }      // i, j <= MAXN < 2048
+  __device__ __forceinline__ int peek(int* p) const {        // a queue word as it stands, for the whole wave
+    int v = 0;
+    if (lane_id() == 0) v = atomicAdd(p, 0);
+    return __builtin_amdgcn_readfirstlane(v);
+  }
   __device__ __forceinline__ void init(int) {}
   __device__ __forceinline__ bool pop(int& i, int& j, int& ml) {
-    int c = 0;
-    if (lane_id() == 0) c = atomicAdd(&sm.tbq[0], 1);
-    c = __builtin_amdgcn_readfirstlane(c);
-    if (c > (int)(sizeof(sm.sec_ml) / sizeof(sm.sec_ml[0])) - 1) return false;
+    const int c = queue_pop(&sm.tbq[0], lane_id());
+    if (c > CAP - 1) return false;
     for (;;) {
-      const int m = __builtin_amdgcn_readfirstlane((int)*reinterpret_cast<volatile unsigned char*>(&sm.sec_ml[c]));
-      if (m) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");      // pairs with push()'s release: the payload loads stay behind the flag read
-        i = sm.sec_i[c]; j = sm.sec_j[c]; ml = m - 1;
+      const int w = peek(&sm.tbw[c]);
+      if (w) {
+        i = w & 2047; j = (w >> 11) & 2047; ml = (w >> 22) - 1;
         return true;
       }
-      if (__builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile int*>(&sm.tbq[3]))) return false;
+      if (peek(&sm.tbq[3])) return false;
       spin_pause();
     }
   }
@@ -415,22 +421,41 @@ template <class SM> struct TbShared {
       // The queue is append-only, so it must hold every sector of a structure at once: each push is a distinct interval that
       // holds a pair of its own (an exterior stem or a multiloop branch), hence at most n / 2 + 1 <= NLEN + 2 entries.  The guard
       // is for a corrupted table only; it ends the traceback as a failure (ST_TRACEBACK), like every table value it cannot reproduce.
-      if (c > (int)(sizeof(sm.sec_ml) / sizeof(sm.sec_ml[0])) - 1) { *reinterpret_cast<volatile int*>(&sm.tbq[3]) = 2; return; }
-      sm.sec_i[c] = (short)i; sm.sec_j[c] = (short)j;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      *reinterpret_cast<volatile unsigned char*>(&sm.sec_ml[c]) = (unsigned char)(ml + 1);
+      if (c > CAP - 1) { atomicAdd(&sm.tbq[3], 2); return; }
+      atomicAdd(&sm.tbw[c], word(i, j, ml));                      // (the entry was zero)
     }
   }
   __device__ __forceinline__ void done_one() {
-    if (lane_id() == 0 && atomicAdd(&sm.tbq[2], -1) == 1) *reinterpret_cast<volatile int*>(&sm.tbq[3]) = 1;
+    if (lane_id() == 0 && atomicAdd(&sm.tbq[2], -1) == 1) atomicAdd(&sm.tbq[3], 1);
   }
-  __device__ __forceinline__ void fail() { if (lane_id() == 0) *reinterpret_cast<volatile int*>(&sm.tbq[3]) = 2; }
-  __device__ __forceinline__ bool failed() const { return *reinterpret_cast<volatile int*>(&sm.tbq[3]) == 2; }
+  __device__ __forceinline__ void fail() { if (lane_id() == 0) atomicAdd(&sm.tbq[3], 2); }
+  __device__ __forceinline__ bool failed() const { return peek(&sm.tbq[3]) >= 2; }
 };
 
-template <class SM, class FMLACC, class QUEUE>
+// hairpin size term by loop size: from global memory (general and strip kernels), or from what the LDS kernel staged (sm.hpl)
+struct HplGlobal {
+  const int* p;
+  __device__ __forceinline__ int operator()(int u) const { return p[u]; }
+};
+template <class SM> struct HplLds {
+  const SM* sm;
+  __device__ __forceinline__ int operator()(int u) const { return sm->hpl[u]; }
+};
+
+// special hairpin (tri / tetra / hexa loop) with the code `code`: lane k holds entry k of the table (cnt <= MAX_SPECIAL = one wave),
+// the first match in table order counts -- one round trip where a loop over the table took one per entry
+__device__ __forceinline__ bool tb_special_hairpin(const int* codes, const int* es, int cnt, int code, int lane, int& e) {
+  static_assert(MAX_SPECIAL <= WAVE, "one table entry per lane");
+  const int c = lane < cnt ? codes[lane] : -1, v = lane < cnt ? es[lane] : 0;     // (codes are non-negative)
+  const int fl = first_lane(__ballot(c == code));
+  if (fl < 0) return false;
+  e = __builtin_amdgcn_readlane(v, fl);
+  return true;
+}
+
+template <class SM, class FMLACC, class HPLACC, class QUEUE>
 __device__ __forceinline__ bool mfe_traceback_q(SM& sm, const MfeArgs& A, const int32_t* __restrict__ Wc,
-                                       const FMLACC FML, const int32_t* __restrict__ EXT, QUEUE Q) {
+                                       const FMLACC FML, const HPLACC HPL, const int32_t* __restrict__ EXT, QUEUE Q) {
   const MfeTables& T = *A.T;
   const Plan& P = *A.plan;
   const int n = A.L, ld = A.ld, lane = lane_id();
@@ -438,15 +463,41 @@ __device__ __forceinline__ bool mfe_traceback_q(SM& sm, const MfeArgs& A, const 
   bool ok = true;
   // The interior scan gives lane l of round r the candidate k = 64 r + l of the canonical order.  Its shape, its kind and its
   // size term (what E_IntLoop adds for the loop size and asymmetry) are fixed for the whole traceback: fetched and computed
-  // once, kept in registers, so that a scan round is LDS lookups plus at most one global load (2x1 / 1x2 / 2x2 lanes).
-  constexpr int NRND = (NPLAN + WAVE - 1) / WAVE;
+  // once, kept in registers, so that a scan is LDS lookups plus two rounds of global loads (cells; 2x1 / 1x2 / 2x2 tables).
+  // One 8-byte load per round through a buffer descriptor: a scalar base, the lane's offset formed HERE (as_vector: nothing of
+  // this is loop-invariant code that could move in front of the fill and sit in registers or scratch through it), the round as
+  // an immediate; the loads go out back to back and are waited for once.
+  constexpr int NRND = NPLAN_TB / WAVE;
   int tb_shape[NRND], tb_L[NRND];
+  {
+    const auto rsP = __builtin_amdgcn_make_buffer_rsrc((void*)&P.tb_pack[0][0], (short)0, (int)sizeof(P.tb_pack), 0x00020000);
+    const int voff = as_vector(lane) * 8;
 #pragma unroll
-  for (int rnd = 0; rnd < NRND; rnd++) {        // (packed on the host, tables.hpp: sixteen independent loads, first used by the first scan)
-    const int k = rnd * WAVE + lane;
-    tb_shape[rnd] = k < NPLAN ? P.tb_shape[k] : (PK_STACK << 16);
-    tb_L[rnd] = k < NPLAN ? P.tb_L[k] : 0;
+    for (int rnd = 0; rnd < NRND; rnd++) {
+      const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsP, voff, rnd * WAVE * 8, 0);
+      tb_shape[rnd] = (int)v[0]; tb_L[rnd] = (int)v[1];
+    }
   }
+  // Model constants of the traceback: read once here and pinned (keep_i32), so that no loop below holds a global load -- the
+  // queue's atomics keep the compiler from hoisting them, and each would be a round trip with a full wait behind it.
+  const int cMLbase = keep_i32(T.MLbase), cMLintern = keep_i32(T.MLintern), cMLclosing = keep_i32(T.MLclosing), cTermAU = keep_i32(T.TermAU);
+  const int n_tri = keep_i32(T.n_tri), n_tetra = keep_i32(T.n_tetra), n_hexa = keep_i32(T.n_hexa);
+  // E_Hairpin of the (wave-uniform) pair (i,j): mfe_hairpin_e with the constants above and the special tables one entry per lane
+  auto hairpin = [&](int i, int j, int t) -> int {
+    const int u = j - i - 1, e = HPL(u);
+    if (u == 3 || u == 4 || u == 6) {
+      int code = 0;
+      for (int k = 0; k < u + 2; k++) code |= sm.S[i + k] << (2 * k);
+      int es = 0;
+      if (u == 3) {
+        if (n_tri && tb_special_hairpin(T.tri_code, T.tri_e, n_tri, code, lane, es)) return es;
+        return e + (t > 2 ? cTermAU : 0);
+      }
+      if (u == 4 ? (n_tetra && tb_special_hairpin(T.tetra_code, T.tetra_e, n_tetra, code, lane, es))
+                 : (n_hexa && tb_special_hairpin(T.hexa_code, T.hexa_e, n_hexa, code, lane, es))) return es;
+    }
+    return e + sm.mmH[t * 16 + sm.S[i + 1] * 4 + sm.S[j - 1]];
+  };
   // one sector: an exterior interval (ml 0), a multiloop segment (ml 1); returns false when a table value cannot be reproduced
   Q.init(n);
   auto sector = [&](int i, int j, const int ml) -> bool {
@@ -486,7 +537,7 @@ __device__ __forceinline__ bool mfe_traceback_q(SM& sm, const MfeArgs& A, const 
         bool stop = true;
         if (jx > i) {
           const int a = FML(jx - i, i), bq = (jx - 1 - i) >= 0 ? FML(jx - 1 - i, i) : INF_DEV;
-          stop = !(a == bq + T.MLbase);
+          stop = !(a == bq + cMLbase);
         }
         const int fl = first_lane(__ballot(stop));
         if (fl >= 0) { j -= fl; break; }
@@ -497,7 +548,7 @@ __device__ __forceinline__ bool mfe_traceback_q(SM& sm, const MfeArgs& A, const 
         bool stop = true;
         if (ix < j) {
           const int a = FML(j - ix, ix), bq = FML(j - ix - 1, ix + 1);
-          stop = !(a == bq + T.MLbase);
+          stop = !(a == bq + cMLbase);
         }
         const int fl = first_lane(__ballot(stop));
         if (fl >= 0) { i += fl; break; }
@@ -510,7 +561,7 @@ __device__ __forceinline__ bool mfe_traceback_q(SM& sm, const MfeArgs& A, const 
       const int cij = w >> 8;
       const int t = pair_type(sm.Sp[i], sm.Sp[j]);
       if (t && cij < HALF &&
-          fij == cij + T.MLintern + (t > 2 ? T.TermAU : 0) + sm.mmM[t * 16 + sm.S[i - 1] * 4 + sm.S[j + 1]]) {
+          fij == cij + cMLintern + (t > 2 ? cTermAU : 0) + sm.mmM[t * 16 + sm.S[i - 1] * 4 + sm.S[j + 1]]) {
         have_pair = true;
       } else {
         int u = -1;
@@ -537,44 +588,68 @@ __device__ __forceinline__ bool mfe_traceback_q(SM& sm, const MfeArgs& A, const 
       // ViennaRNA's order, so one L2 round trip settles the step instead of three (cell, plan words, inner cells)
       const int w_in = d - 2 > TURN ? Wc[(d - 2) * ld + i + 1] : INF_DEV * 256;
       const int cij = Wc[d * ld + i] >> 8;
-      if (cij == mfe_hairpin(sm, A, i, j, t)) break;
+      if (cij == hairpin(i, j, t)) break;
       const int si1 = sm.S[i + 1], sj1 = sm.S[j - 1];
       if ((w_in >> 8) < HALF && cij == (w_in >> 8) + mfe_intloop(sm, T, 0, 0, t, si1, sj1, w_in & 127)) {
         i++; j--;
         continue;
       }
-      int found = -1;
-      const int tij = t * 16 + si1 * 4 + sj1, tauI = t > 2 ? T.TermAU : 0;
+      // The scan by GROUPS of rounds, three passes over a group: the cells of all its rounds are requested, then the table words
+      // of all their 2x1 / 1x2 / 2x2 lanes, then the rounds are judged in canonical order and the first hit is taken -- two round
+      // trips per group instead of up to two per round.  Rounds 0 and 1 (u1 <= 3: every bulge on the 3' side, the table-driven
+      // small loops) hold nearly every hit of a natural structure and make the first group; the second one is the rest, so a
+      // multiloop reaches its split scan after four round trips instead of up to 2 NRND.  (All rounds as ONE group costs the
+      // common event eight cell loads and their decoding for nothing: measured, the tail 1.5 - 2 us longer than before.)
+      const int tij = t * 16 + si1 * 4 + sj1, tauI = t > 2 ? cTermAU : 0;
+      constexpr int TB_GRP[] = {0, 2, NRND};
+      int wq[NRND], eq[NRND];
+      int fshape = -1;
 #pragma unroll
-      for (int rnd = 0; rnd < NRND; rnd++) {
-        if (found >= 0) break;
-        const int k = rnd * WAVE + lane;
-        const int u1 = tb_shape[rnd] & 255, u2 = (tb_shape[rnd] >> 8) & 255, kind = tb_shape[rnd] >> 16;
-        const int dp = d - 2 - u1 - u2;
-        const bool live = k < NPLAN && dp > TURN;
-        const int w = live ? Wc[dp * ld + i + 1 + u1] : INF_DEV * 256;
-        const int cpq = w >> 8, info = w & 127, t2 = info >> 4, sq1 = (info >> 2) & 3, sp1 = info & 3;
-        // the mismatch-pair kinds share one code path through the table of their kind (mm1n, mm23, mmI: LDS)
-        const int* mm = kind == PK_1XN ? sm.mm1n : kind == PK_INT23 ? sm.mm23 : sm.mmI;
-        int en = mm[tij] + mm[info];
-        const int e_stack = sm.stack[t * 8 + t2], e_11 = sm.int11[(t * 8 + t2) * 16 + si1 * 4 + sj1];
-        en = kind == PK_STACK || kind == PK_BULGE1 ? e_stack : en;
-        en = kind == PK_BULGEN ? tauI + (t2 > 2 ? T.TermAU : 0) : en;
-        en = kind == PK_INT11 ? e_11 : en;
-        if (kind == PK_INT21) en = T.int21[(t * 8 + t2) * 64 + si1 * 16 + sq1 * 4 + sj1];
-        else if (kind == PK_INT12) en = T.int21[(t2 * 8 + t) * 64 + sq1 * 16 + si1 * 4 + sp1];
-        else if (kind == PK_INT22) en = T.int22[(t * 8 + t2) * 256 + si1 * 64 + sp1 * 16 + sq1 * 4 + sj1];
-        const bool hit = live && cpq < HALF && cij == cpq + en + tb_L[rnd];
-        const int fl = first_lane(__ballot(hit));
-        if (fl >= 0) found = rnd * WAVE + fl;
+      for (int g = 0; g + 1 < (int)(sizeof(TB_GRP) / sizeof(int)); g++) {
+        if (fshape >= 0) break;
+#pragma unroll
+        for (int rnd = TB_GRP[g]; rnd < TB_GRP[g + 1]; rnd++) {
+          const int u1 = tb_shape[rnd] & 255, u2 = (tb_shape[rnd] >> 8) & 255;
+          const int dp = d - 2 - u1 - u2;
+          const bool live = rnd * WAVE + lane < NPLAN && dp > TURN;          // (candidates whose inner pair cannot exist stay masked)
+          wq[rnd] = live ? Wc[dp * ld + i + 1 + u1] : INF_DEV * 256;
+        }
+#pragma unroll
+        for (int rnd = TB_GRP[g]; rnd < TB_GRP[g + 1]; rnd++) {
+          const int kind = tb_shape[rnd] >> 16;
+          const int info = wq[rnd] & 127, t2 = info >> 4, sq1 = (info >> 2) & 3, sp1 = info & 3;
+          int en = 0;
+          if (kind == PK_INT21) en = T.int21[(t * 8 + t2) * 64 + si1 * 16 + sq1 * 4 + sj1];
+          else if (kind == PK_INT12) en = T.int21[(t2 * 8 + t) * 64 + sq1 * 16 + si1 * 4 + sp1];
+          else if (kind == PK_INT22) en = T.int22[(t * 8 + t2) * 256 + si1 * 64 + sp1 * 16 + sq1 * 4 + sj1];
+          eq[rnd] = en;
+        }
+#pragma unroll
+        for (int rnd = TB_GRP[g]; rnd < TB_GRP[g + 1]; rnd++) {
+          if (fshape >= 0) break;
+          const int kind = tb_shape[rnd] >> 16;
+          const int cpq = wq[rnd] >> 8, info = wq[rnd] & 127, t2 = info >> 4;
+          // the mismatch-pair kinds share one code path through the table of their kind (mm1n, mm23, mmI: LDS)
+          const int* mm = kind == PK_1XN ? sm.mm1n : kind == PK_INT23 ? sm.mm23 : sm.mmI;
+          int en = mm[tij] + mm[info];
+          const int e_stack = sm.stack[t * 8 + t2], e_11 = sm.int11[(t * 8 + t2) * 16 + si1 * 4 + sj1];
+          en = kind == PK_STACK || kind == PK_BULGE1 ? e_stack : en;
+          en = kind == PK_BULGEN ? tauI + (t2 > 2 ? cTermAU : 0) : en;
+          en = kind == PK_INT11 ? e_11 : en;
+          en = kind == PK_INT21 || kind == PK_INT12 || kind == PK_INT22 ? eq[rnd] : en;
+          // (a masked lane holds INF: cpq >= HALF)
+          const bool hit = cpq < HALF && cij == cpq + en + tb_L[rnd];
+          const int fl = first_lane(__ballot(hit));
+          if (fl >= 0) fshape = __builtin_amdgcn_readlane(tb_shape[rnd], fl);    // the winner's u1 | u2 << 8 | kind << 16
+        }
       }
-      if (found >= 0) {
-        i = i + 1 + P.tb_u1[found];
-        j = j - 1 - P.tb_u2[found];
+      if (fshape >= 0) {
+        i = i + 1 + (fshape & 255);
+        j = j - 1 - ((fshape >> 8) & 255);
         continue;
       }
       // multiloop closed by (i,j): vrna_BT_mb_loop
-      const int e = cij - T.MLclosing - T.MLintern - (t > 2 ? T.TermAU : 0) -
+      const int e = cij - cMLclosing - cMLintern - (t > 2 ? cTermAU : 0) -
                     sm.mmM[rtype_of(t) * 16 + sj1 * 4 + si1];
       int u = -1;
       for (int base = i + 2 + TURN; base < j - 2 - TURN && u < 0; base += WAVE) {
@@ -603,7 +678,7 @@ __device__ __forceinline__ bool mfe_traceback_q(SM& sm, const MfeArgs& A, const 
 template <class SM, class FMLACC>
 __device__ inline bool mfe_traceback(SM& sm, const MfeArgs& A, const int32_t* __restrict__ Wc,
                                      const FMLACC FML, const int32_t* __restrict__ EXT) {
-  return mfe_traceback_q(sm, A, Wc, FML, EXT, TbStack<SM>{sm});
+  return mfe_traceback_q(sm, A, Wc, FML, HplGlobal{A.hp_len}, EXT, TbStack<SM>{sm});
 }
 
 

@@ -56,6 +56,7 @@ struct MfeFastSmem : MfeSmemCore<MFE_FAST_NMAX> {
   int eshape_rows[128];          // shape slots of the 16-lane-row E items (one-workgroup kernel): s | kind << 5 | u1 << 8 | size term << 16
   int sync_fail;                 // two-workgroup kernel: a wait for the helper expired
   int tbq[4];                    // sector queue of the traceback (TbShared, fold_mfe.hpp)
+  int tbw[MFE_FAST_NMAX + 2];    // ... its entries, one word each
   int etab[2][128];              // the same shapes as seen from one diagonal: byte offset of the inner pair's ring cell
                                  // for column 0 | size term << 16 (shapes without an inner pair yet point at the INF row)
   int twc[32][2];                // by total loop size s: {asymmetry term of the two new shapes (2, s-2) (s-2, 2), size term (INF below 6)} (mfe_tower2_step)
@@ -1030,18 +1031,15 @@ __device__ __forceinline__ void mfe_lds_body(MfeFastSmem<NT>& sm, MfeArgs A, int
     if (DUAL && sm.sync_fail) { status = ST_SYNC; break; }
     // traceback by TB_WAVES waves working from one queue of sectors in LDS (TbShared): entry 0 = the whole exterior interval
     constexpr int TB_WAVES = NT / WAVE < 8 ? NT / WAVE : 8;
-    for (int k = tid; k < (int)(sizeof(sm.sec_ml) / sizeof(sm.sec_ml[0])); k += NT) sm.sec_ml[k] = 0;
+    for (int k = tid; k < TbShared<MfeFastSmem<NT>>::CAP; k += NT) sm.tbw[k] = k ? 0 : TbShared<MfeFastSmem<NT>>::word(1, n, 0);
+    if (tid == 0) { sm.tbq[0] = 0; sm.tbq[1] = 1; sm.tbq[2] = 1; sm.tbq[3] = 0; }
     __syncthreads();
-    if (tid == 0) {
-      sm.sec_i[0] = 1; sm.sec_j[0] = (short)n; sm.sec_ml[0] = 1;          // ml 0, published
-      sm.tbq[0] = 0; sm.tbq[1] = 1; sm.tbq[2] = 1; sm.tbq[3] = 0;
-    }
-    __syncthreads();
-    if (wave_id() < TB_WAVES) (void)mfe_traceback_q(sm, A, Wc, FmlLds<NT>{&sm, n}, EXT, TbShared<MfeFastSmem<NT>>{sm});
+    if (wave_id() < TB_WAVES)
+      (void)mfe_traceback_q(sm, A, Wc, FmlLds<NT>{&sm, n}, HplLds<MfeFastSmem<NT>>{&sm}, EXT, TbShared<MfeFastSmem<NT>>{sm});
     __syncthreads();
     if (tid == 0) {
       if (round == 0) A.Emfe[r] = sm.f5[n];
-      sm.flag = sm.tbq[3] == 2 ? 1 : 0;
+      sm.flag = sm.tbq[3] >= 2 ? 1 : 0;
     }
     __syncthreads();
     if (sm.flag) { status = ST_TRACEBACK; break; }

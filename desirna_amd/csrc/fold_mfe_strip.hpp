@@ -750,6 +750,7 @@ __global__ __launch_bounds__(NT) void mfe_strip_kernel(MfeArgs A, StripLink lk, 
 constexpr int TRACE_WAVES = 8;
 struct MfeTraceSmem : MfeSmemCore<STRIP_NMAX> {
   int tbq[4];                    // sector queue of the traceback (TbShared)
+  int tbw[STRIP_NMAX + 2];       // ... its entries, one word each
 };
 
 __device__ inline void mfe_strip_trace_body(MfeTraceSmem& sm, MfeArgs A, const int* idx, int q, int round, int r0 = 0) {
@@ -776,7 +777,7 @@ __device__ inline void mfe_strip_trace_body(MfeTraceSmem& sm, MfeArgs A, const i
   for (int k = tid; k < 32; k += NT) { sm.d5[k] = T.d5[k]; sm.d3[k] = T.d3[k]; }
   for (int k = tid; k < n; k += NT) sm.ssw[k] = '.';
   for (int k = tid; k <= n; k += NT) sm.f5[k] = Wc[ld + k];
-  for (int k = tid; k < (int)(sizeof(sm.sec_ml) / sizeof(sm.sec_ml[0])); k += NT) sm.sec_ml[k] = 0;
+  for (int k = tid; k < TbShared<MfeTraceSmem>::CAP; k += NT) sm.tbw[k] = 0;
   load_sequence<NT>(sm, A.seqs + so, n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.Emfe[r] = 0; Wc[0] = 0; }
@@ -796,13 +797,13 @@ __device__ inline void mfe_strip_trace_body(MfeTraceSmem& sm, MfeArgs A, const i
   }
   if (tid == 0) {
     sm.Sp[0] = 4; sm.Sp[n + 1] = 4;
-    sm.sec_i[0] = 1; sm.sec_j[0] = (short)n; sm.sec_ml[0] = 1;          // entry 0 = the whole exterior interval (ml 0), published
+    sm.tbw[0] = TbShared<MfeTraceSmem>::word(1, n, 0);                  // entry 0 = the whole exterior interval (ml 0), published
     sm.tbq[0] = 0; sm.tbq[1] = 1; sm.tbq[2] = 1; sm.tbq[3] = 0;
   }
   __syncthreads();
-  (void)mfe_traceback_q(sm, A, Wc, FmlGlobal{FML, ld}, EXT, TbShared<MfeTraceSmem>{sm});
+  (void)mfe_traceback_q(sm, A, Wc, FmlGlobal{FML, ld}, HplGlobal{A.hp_len}, EXT, TbShared<MfeTraceSmem>{sm});
   __syncthreads();
-  if (sm.tbq[3] == 2) {                                // a wave could not reproduce a table value
+  if (sm.tbq[3] >= 2) {                               // a wave could not reproduce a table value
     if (tid == 0) { A.status[r] = ST_TRACEBACK; Wc[0] = 0; if (round == 0) A.Emfe[r] = sm.f5[n]; }
     for (int k = tid; k < n; k += NT) A.ss[so + k] = sm.sspk[k];
     return;

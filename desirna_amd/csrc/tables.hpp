@@ -27,6 +27,7 @@ constexpr int INF_DEV = 1 << 22;    // device-side "infinity": (INF_DEV << 8) st
 constexpr int TURN = 3;
 constexpr int MAXLOOP = 30;
 constexpr int NPLAN = 496;          // #(u1,u2) with u1+u2 <= 30
+constexpr int NPLAN_TB = (NPLAN + 63) / 64 * 64;   // ... rounded up to whole waves of 64 lanes (the traceback's scan rounds)
 constexpr int NPAIR_MAX = 256;      // slots of consecutive generic entries (200 pairs / 109 quads with MAXLOOP = 30)
 constexpr int MAX_SPECIAL = 64;
 
@@ -43,7 +44,9 @@ struct Plan {
   int seg[PK_NKINDS + 1];  // entries of kind k are [seg[k], seg[k+1])
   // canonical traceback order (p ascending, q descending): SURVEY App. A.4
   int tb_u1[NPLAN], tb_u2[NPLAN];
-  int tb_shape[NPLAN], tb_L[NPLAN];   // ... packed for the traceback's scan: u1 | u2 << 8 | kind << 16, and the candidate's size term
+  // ... packed for the traceback's scan, one 8-byte word pair per candidate: {u1 | u2 << 8 | kind << 16, the candidate's size
+  // term}; padded to whole waves with entries that are never live (u1 = u2 = 255), so a lane's pair of every round is one load
+  int tb_pack[NPLAN_TB][2];
   // The generic entries are ordered by (u1+u2, u1): entries of one loop size read CONSECUTIVE cells of one table row, so a
   // lane can fetch them 16 bytes at a time.  Slots of two (fp64 tables) and of four (int32 tables) consecutive entries:
   // first entry and number of entries (a slot never crosses a loop size).
@@ -297,8 +300,9 @@ inline std::string build_tables(const int32_t* b, int n_int32, HostTables& T) {
       else if (k == PK_1XN) L = M.interior[nl + 1] + std::min(M.max_ninio, (nl - ns) * M.ninio);
       else if (k == PK_INT23) L = M.interior[5] + M.ninio;
       else if (k == PK_GENERIC) L = M.interior[nl + ns] + std::min(M.max_ninio, (nl - ns) * M.ninio);
-      P.tb_u1[e] = u1; P.tb_u2[e] = u2; P.tb_shape[e] = u1 | (u2 << 8) | (k << 16); P.tb_L[e] = L; e++;
+      P.tb_u1[e] = u1; P.tb_u2[e] = u2; P.tb_pack[e][0] = u1 | (u2 << 8) | (k << 16); P.tb_pack[e][1] = L; e++;
     }
+  for (; e < NPLAN_TB; e++) { P.tb_pack[e][0] = 255 | (255 << 8) | (PK_STACK << 16); P.tb_pack[e][1] = 0; }
   return "";
 }
 
