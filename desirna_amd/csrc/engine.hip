@@ -30,6 +30,7 @@
 #include "fold_pf_lds.hpp"
 #include "fold_pf_strip.hpp"
 #include "fold_sample.hpp"
+#include "fold_cofold_sample.hpp"
 #include "fold_subopt.hpp"
 #include "fold_cofold_subopt.hpp"
 #include "fold_subopt_lds.hpp"
@@ -91,6 +92,9 @@ struct drna_engine {
   // stochastic traceback (fold_sample.hpp): the q5 columns of ws_slots sequences, allocated on first use
   double* d_q5s = nullptr;
   int sample_calls = 0;     // launches of sample_kernel (read-only option "sample_calls")
+  // ... for two strands (fold_cofold_sample.hpp): the columns q5, qA3, qB5, q5c of ws_slots pairs, allocated on first use
+  double* d_cocols = nullptr;
+  int cofold_sample_calls = 0;   // launches of cofold_sample_kernel (read-only option "cofold_sample_calls")
   // ragged batches: per-sequence descriptors (len, off, target, two index lists) and the structures' pair tables.  Three blocks
   // of 7 max_R ints (rg_block): a lock-step loop keeps its scoring plan, its ensemble-defect plan and the second-best fold's
   // lists on the device side by side
@@ -396,7 +400,7 @@ extern "C" void drna_destroy(drna_engine* e) {
   void* bufs[] = {e->d_mfeT, e->d_pfT, e->d_plan, e->d_hp_len, e->d_bulge_len, e->d_int_len, e->d_hp_w, e->d_scale,
                   e->d_eMLb, e->d_ws_mfe, e->d_ws_pf, e->d_seqs, e->d_Epf, e->d_Emfe, e->d_ss, e->d_Ed, e->d_pt,
                   e->d_ws_out, e->d_edef, e->d_rg, e->d_rpt, e->d_rpt_off, e->d_F4, e->d_ws_kb, e->d_kbE, e->d_kbss,
-                  e->dflags.d, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->sflags.d, e->d_srec, e->d_sdbg, e->d_sclk, e->pflags.d, e->d_q5s};
+                  e->dflags.d, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->sflags.d, e->d_srec, e->d_sdbg, e->d_sclk, e->pflags.d, e->d_q5s, e->d_cocols};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_status) (void)hipHostFree(e->h_status);
@@ -458,6 +462,7 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "cofold_edef_lds_max")) { *value = CO_EDEF_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "edef_lds_calls")) { *value = e->edef_lds_calls; return DRNA_OK; }
   if (!strcmp(name, "sample_calls")) { *value = e->sample_calls; return DRNA_OK; }
+  if (!strcmp(name, "cofold_sample_calls")) { *value = e->cofold_sample_calls; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds")) { *value = e->subopt_lds ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds_max")) { *value = SUB_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "self_dimer_lds")) { *value = e->self_dimer_lds ? 1 : 0; return DRNA_OK; }
@@ -1133,42 +1138,53 @@ static int sample_impl(drna_engine* e, int m, int L, int S, const char* d_seqs, 
                         [&] { hipLaunchKernelGGL(sample_kernel<SAMPLE_NT>, dim3(m * a.G), dim3(SAMPLE_NT), 0, e->s_pf, a); });
 }
 
-// chunks of the workspace slots (and of max_R: the staging buffer and the status words), one pf_kernel and one sample launch each
-static int sample_batch_host(drna_engine* e, int R, int L, const char* seqs, int S, const uint64_t* seeds, char* ss, int32_t* E,
-                             double* Epf, uint64_t* d_seeds, char* d_ss, int32_t* d_E, int step) {
+// two strands: cofold_pf_kernel (always the workspace instance: the LDS instance leaves no tables), then the columns launch and
+// cofold_sample_kernel on its tables; pairs r_base, r_base + 1, ...
+static int cofold_sample_impl(drna_engine* e, int m, int L, int cut, int S, const char* d_seqs, const uint64_t* d_seeds, char* d_ss,
+                              int32_t* d_E, int r_base) {
+  CoSampleArgs a{};
+  a.co = co_args(e, d_seqs, L, cut, L + 2);
+  a.ev = eval_args(e, d_seqs, L, nullptr);
+  a.ev.cut = cut; a.ev.DuplexInit = e->H.DuplexInit;
+  a.cols = e->d_cocols; a.col_stride = e->max_L + 2;
+  a.seeds = d_seeds; a.S = S; a.ss = d_ss; a.E = d_E;
+  constexpr int NW = SAMPLE_NT / WAVE;
+  a.G = std::max(1, std::min((S + NW - 1) / NW, (4 * e->cus + m - 1) / m));
+  e->cofold_sample_calls++;
+  return inside_outside(e, m, r_base, "unexpected status of the co-fold partition function",
+                        [&] { hipLaunchKernelGGL(cofold_pf_kernel<1024>, dim3(m), dim3(1024), 0, e->s_pf, a.co); },
+                        [&] {
+                          hipLaunchKernelGGL(cofold_columns_kernel<256>, dim3(m), dim3(256), 0, e->s_pf, a);
+                          hipLaunchKernelGGL(cofold_sample_kernel<SAMPLE_NT>, dim3(m * a.G), dim3(SAMPLE_NT), 0, e->s_pf, a);
+                        });
+}
+
+// The sample buffers of a call and its chunks of the workspace slots (and of max_R: the staging buffer and the status words).
+// impl(m, d_seeds, d_ss, d_E, r0) folds and samples the m sequences (pairs) of a chunk from e->d_seqs; extra(m, r0) copies out what
+// else the entry point returns per sequence.  last_edef_timing = the chunks' sums
+template <class Impl, class Extra>
+static int sample_chunks(drna_engine* e, int R, int L, const char* seqs, int S, const uint64_t* seeds, char* ss, int32_t* E,
+                         uint64_t* d_seeds, char* d_ss, int32_t* d_E, int step, Impl&& impl, Extra&& extra) {
   float sum[2] = {0, 0};
   for (int r0 = 0; r0 < R; r0 += step) {
     const int m = std::min(step, R - r0);
     const size_t cells = (size_t)m * S;
     HIP_TRY(hipMemcpy(e->d_seqs, seqs + (size_t)r0 * L, (size_t)m * L, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_seeds, seeds + r0, (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice));
-    const int rc = sample_impl(e, m, L, S, e->d_seqs, d_seeds, d_ss, E ? d_E : nullptr, r0);
+    int rc = impl(m, d_seeds, d_ss, E ? d_E : nullptr, r0);
     if (rc != DRNA_OK) return rc;
     sum[0] += e->timing_edef[0]; sum[1] += e->timing_edef[1];
     HIP_TRY(hipMemcpy(ss + (size_t)r0 * S * L, d_ss, cells * L, hipMemcpyDeviceToHost));
     if (E) HIP_TRY(hipMemcpy(E + (size_t)r0 * S, d_E, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (Epf) HIP_TRY(hipMemcpy(Epf + r0, e->d_Epf, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
+    rc = extra(m, r0);
+    if (rc != DRNA_OK) return rc;
   }
   e->timing_edef[0] = sum[0]; e->timing_edef[1] = sum[1];
   return DRNA_OK;
 }
-
-extern "C" int drna_sample_structures_batch(drna_engine* e, int R, int L, const char* seqs, int S, const uint64_t* seeds, char* ss,
-                                            int32_t* E, double* Epf) {
-  if (!e) return DRNA_ERR_ARG;
-  const char* who = "drna_sample_structures_batch";
-  { const int rc = aux_check(e, who, std::min(R, e->max_R), L, nullptr, S >= 1 && seqs && seeds && ss, "S >= 1; seqs, seeds and ss required");
-    if (rc != DRNA_OK) return rc; }
-  if ((long long)R * S > (long long)DRNA_SAMPLE_MAX_CHARS / L) {
-    e->err = std::string(who) + ": R x S x L above DRNA_SAMPLE_MAX_CHARS";
-    return DRNA_ERR_ARG;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  if (!e->d_q5s) {
-    const size_t b = (size_t)e->ws_slots * (e->max_L + 2) * sizeof(double);
-    HIP_TRY(hipMalloc((void**)&e->d_q5s, b));
-    e->ws_bytes += b;
-  }
+template <class Impl, class Extra>
+static int sample_batch_host(drna_engine* e, const char* who, int R, int L, const char* seqs, int S, const uint64_t* seeds, char* ss,
+                             int32_t* E, Impl&& impl, Extra&& extra) {
   const int step = std::min(std::min(e->ws_slots, e->max_R), R);
   uint64_t* d_seeds = nullptr;
   char* d_ss = nullptr;
@@ -1180,11 +1196,62 @@ extern "C" int drna_sample_structures_batch(drna_engine* e, int R, int L, const 
     e->err = std::string(who) + ": hipMalloc of the sample buffers failed";
     rc = DRNA_ERR_DEVICE;
   }
-  if (rc == DRNA_OK) rc = sample_batch_host(e, R, L, seqs, S, seeds, ss, E, Epf, d_seeds, d_ss, d_E, step);
+  if (rc == DRNA_OK) rc = sample_chunks(e, R, L, seqs, S, seeds, ss, E, d_seeds, d_ss, d_E, step, impl, extra);
   if (d_seeds) (void)hipFree(d_seeds);
   if (d_ss) (void)hipFree(d_ss);
   if (d_E) (void)hipFree(d_E);
   return rc;
+}
+// the argument errors of both sample entry points (cut: two strands)
+static int sample_check(drna_engine* e, const char* who, int R, int L, const int* cut, int S, bool ptrs) {
+  const int rc = aux_check(e, who, std::min(R, e->max_R), L, cut, S >= 1 && ptrs, "S >= 1; seqs, seeds and ss required");
+  if (rc != DRNA_OK) return rc;
+  if ((long long)R * S > (long long)DRNA_SAMPLE_MAX_CHARS / L) {
+    e->err = std::string(who) + ": R x S x L above DRNA_SAMPLE_MAX_CHARS";
+    return DRNA_ERR_ARG;
+  }
+  return DRNA_OK;
+}
+// a per-slot buffer of the samplers, allocated on first use: per_slot doubles for each of the ws_slots sequences
+static int sample_columns(drna_engine* e, double** buf, size_t per_slot) {
+  if (*buf) return DRNA_OK;
+  const size_t b = (size_t)e->ws_slots * per_slot * sizeof(double);
+  HIP_TRY(hipMalloc((void**)buf, b));
+  e->ws_bytes += b;
+  return DRNA_OK;
+}
+
+extern "C" int drna_sample_structures_batch(drna_engine* e, int R, int L, const char* seqs, int S, const uint64_t* seeds, char* ss,
+                                            int32_t* E, double* Epf) {
+  if (!e) return DRNA_ERR_ARG;
+  const char* who = "drna_sample_structures_batch";
+  { const int rc = sample_check(e, who, R, L, nullptr, S, seqs && seeds && ss); if (rc != DRNA_OK) return rc; }
+  HIP_TRY(hipSetDevice(e->device));
+  { const int rc = sample_columns(e, &e->d_q5s, (size_t)e->max_L + 2); if (rc != DRNA_OK) return rc; }
+  return sample_batch_host(
+      e, who, R, L, seqs, S, seeds, ss, E,
+      [&](int m, const uint64_t* d_seeds, char* d_ss, int32_t* d_E, int r0) -> int { return sample_impl(e, m, L, S, e->d_seqs, d_seeds, d_ss, d_E, r0); },
+      [&](int m, int r0) -> int {
+        if (Epf) HIP_TRY(hipMemcpy(Epf + r0, e->d_Epf, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
+        return DRNA_OK;
+      });
+}
+
+extern "C" int drna_cofold_sample_structures_batch(drna_engine* e, int R, int L, int cut, const char* seqs, int S, const uint64_t* seeds,
+                                                   char* ss, int32_t* E, double* F4) {
+  if (!e) return DRNA_ERR_ARG;
+  const char* who = "drna_cofold_sample_structures_batch";
+  { const int rc = sample_check(e, who, R, L, &cut, S, seqs && seeds && ss); if (rc != DRNA_OK) return rc; }
+  HIP_TRY(hipSetDevice(e->device));
+  { const int rc = sample_columns(e, &e->d_cocols, (size_t)CO_COLS * (e->max_L + 2)); if (rc != DRNA_OK) return rc; }
+  if (!e->d_F4) HIP_TRY(hipMalloc((void**)&e->d_F4, (size_t)4 * e->max_R * sizeof(double)));
+  return sample_batch_host(
+      e, who, R, L, seqs, S, seeds, ss, E,
+      [&](int m, const uint64_t* d_seeds, char* d_ss, int32_t* d_E, int r0) -> int { return cofold_sample_impl(e, m, L, cut, S, e->d_seqs, d_seeds, d_ss, d_E, r0); },
+      [&](int m, int r0) -> int {
+        if (F4) HIP_TRY(hipMemcpy(F4 + (size_t)4 * r0, e->d_F4, (size_t)4 * m * sizeof(double), hipMemcpyDeviceToHost));
+        return DRNA_OK;
+      });
 }
 
 // ---------------------------------------------------------------- ragged batches (sequences of different lengths)

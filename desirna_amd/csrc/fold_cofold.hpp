@@ -492,6 +492,31 @@ __device__ __forceinline__ void co_q5_column(SM& sm, const LAY& lay, const doubl
   }
 }
 
+// q5c[0 .. n]: the CONNECTED part of q5 -- the prefixes [1 .. j] whose exterior loop holds a pair that joins the strands (exactly
+// one can: a second would cross it) -- built directly, never as q5[j] - (unconnected part): the stochastic traceback
+// (fold_cofold_sample.hpp) cannot draw from a difference.  0 up to the nick; beyond it the stem term is q5's, on q5c[i - 1] left of
+// a pair inside strand B and on q5[i - 1] left of a joining pair.  Needs sm.q5[0 .. cut - 1].
+template <class SM, class LAY>
+__device__ __forceinline__ void co_q5c_column(SM& sm, const LAY& lay, const double* QB, const unsigned char* INFO,
+                                              double tAU, double sc1, int lane) {
+  const int n = lay.n, cut = lay.cut;
+  for (int j = 0; j <= cut; j++) sm.q5c[j] = 0.0;
+  for (int j = cut + 1; j <= n; j++) {
+    double s = 0.0;
+    for (int i = lane + 1; i < j; i += WAVE) {
+      const int c = lay.at(j - i, i);
+      const int fi = INFO[c];
+      if (!fi) continue;
+      const int t = rtype_of(fi >> 4);
+      const bool h5 = i > 1 && co_same(i - 1, i, cut), h3 = j < n && co_same(j, j + 1, cut);
+      s += (i <= cut ? sm.q5[i - 1] : sm.q5c[i - 1]) * QB[c] * (t > 2 ? tAU : 1.0) *
+           co_pf_endstem(sm.mmExt, sm, t, h5, sm.S[i - 1], h3, sm.S[j + 1]);
+    }
+    s = wave_sum_f64(s);
+    sm.q5c[j] = sm.q5c[j - 1] * sc1 + s;
+  }
+}
+
 // q3[1 .. n + 1]: the suffix column of [i .. n], built the way q5 is (the outside kernel's exterior term)
 template <class SM, class LAY>
 __device__ __forceinline__ void co_q3_column(SM& sm, const LAY& lay, const double* QB, const unsigned char* INFO,

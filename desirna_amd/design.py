@@ -832,16 +832,21 @@ def ensemble_report(engine, result, input_file, S, top=5, seed=0):
     itself (kind ``target``, count 0 allowed; it repeats a ``top`` row when the target is one of them) and a row ``other`` with the
     samples that are neither among the top nor the target -- so top + other, plus target where it is not among the top, add up to S.
     Energies in kcal/mol (the target's, when it was not drawn, from the run's record of the sequence), 1 - MCC to the target by
-    ``HostKernels.simscore``.  One strand only."""
+    ``HostKernels.simscore``.  A two-strand design (an ``&`` in the target, the sequences ``'AAAA&BBBB'``) is sampled from the
+    co-fold ensemble (``engine.cofold_sample_structures``): every structure compared and written keeps its ``&``, ``Epf`` is FAB,
+    and 1 - MCC takes the ``&`` as ``Ee`` like every two-strand score."""
     from collections import Counter
     from . import engine as _engine
     from . import outputs
     target = input_file.sec_struct
-    if "&" in target:
-        raise ValueError("ensemble_report: one strand only")
+    two = "&" in target
     seqs = list(result.get("reported") or [r["sequence"] for r in outputs.sort_and_filter(result["simulation_data"])])
     S, top = int(S), int(top)
-    ss, E, Epf = engine.sample_structures(seqs, S, seed)
+    if two:
+        ss, E, F4 = engine.cofold_sample_structures(seqs, S, seed)
+        Epf = F4[:, 3]
+    else:
+        ss, E, Epf = engine.sample_structures(seqs, S, seed)
     hk = _engine.HostKernels()
     known = {r["sequence"]: r.get("edesired") for r in result.get("simulation_data") or []}
     rows = []
@@ -850,7 +855,8 @@ def ensemble_report(engine, result, input_file, S, top=5, seed=0):
         energy = {s: int(E[r][k]) / 100.0 for k, s in enumerate(ss[r])}
         first = sorted(cnt, key=lambda s: (-cnt[s], s))[:top]
         listed = first + [target]
-        mcc = 1.0 - hk.simscore(target, np.frombuffer("".join(listed).encode("ascii"), dtype=np.uint8).reshape(len(listed), -1))[0]
+        sub = [s.replace("&", "Ee") for s in listed]         # the '&' -> 'Ee' substitution of every two-strand 1 - MCC
+        mcc = 1.0 - hk.simscore(sub[-1], np.frombuffer("".join(sub).encode("ascii"), dtype=np.uint8).reshape(len(sub), -1))[0]
         row = lambda kind, rank, s, c, e, m: dict(sequence=seq, Epf=float(Epf[r]), kind=kind, rank=rank, structure=s, count=int(c),
                                                   frequency=c / S, energy=e, mcc=m)
         for k, s in enumerate(first):

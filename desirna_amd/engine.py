@@ -76,6 +76,7 @@ _SIGNATURES = {
     "drna_rng_seed": (_ci, [_ci, _vp, _vp]),
     "drna_rng_random": (_ci, [_ci, _vp, _vp]),
     "drna_sample_structures_batch": (_ci, [_vp, _ci, _ci, _str, _ci, _vp, _vp, _vp, _vp]),
+    "drna_cofold_sample_structures_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _ci, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -161,6 +162,16 @@ def _split_pairs(seqs):
             raise ValueError("all pairs of a batch must have the same strand lengths")
         flat.append(a + b)
     return "".join(flat).encode("ascii"), len(flat), L, cut
+
+
+def _sample_seeds(seed, R):
+    """the seed rule of the samplers: an integer gives sequence r the seed seed + r (mod 2^64), an array the R seeds themselves"""
+    if np.ndim(seed) == 0:
+        return np.array([(int(seed) + r) % (1 << 64) for r in range(R)], dtype=np.uint64)
+    seeds = np.ascontiguousarray(seed, dtype=np.uint64)
+    if seeds.shape != (R,):
+        raise ValueError("seed must be an integer or one uint64 per sequence")
+    return seeds
 
 
 _LIVE = None          # weak set of open engines, _CLOSED_FALLBACKS: the counters of the closed ones (sync_fallbacks_total)
@@ -584,18 +595,34 @@ class Engine:
         seqs_u8 = np.ascontiguousarray(seqs_u8, dtype=np.uint8)
         R, L = seqs_u8.shape
         S = int(S)
-        if np.ndim(seed) == 0:
-            seeds = np.array([(int(seed) + r) % (1 << 64) for r in range(R)], dtype=np.uint64)
-        else:
-            seeds = np.ascontiguousarray(seed, dtype=np.uint64)
-            if seeds.shape != (R,):
-                raise ValueError("seed must be an integer or one uint64 per sequence")
+        seeds = _sample_seeds(seed, R)
         ss = np.zeros((R, max(S, 0), L), dtype=np.uint8)
         E = np.zeros((R, max(S, 0)), dtype=np.int32)
         Epf = np.zeros(R, dtype=np.float64)
         self._check(self._L.drna_sample_structures_batch(self._h, R, L, seqs_u8.ctypes.data_as(C.c_char_p), S, seeds.ctypes.data,
                                                          ss.ctypes.data, E.ctypes.data, Epf.ctypes.data))
         return ss, E, Epf
+
+    def cofold_sample_structures(self, seqs, S, seed=0):
+        """Two strands: S co-fold structures per 'AAAA&BBBB' pair drawn from the ensemble of :meth:`cofold_batch`'s partition
+        function (connected structures weighted by expDuplexInit, halved for two equal strands, where a structure and its
+        rotation are two structures; the weights sum to exp(-FAB / kT)).  Returns (R lists of S dot-bracket strings with the
+        ``&`` put back at the cut, E (R, S) int32 in dcal/mol -- :meth:`cofold_batch`'s E(structure), DuplexInit included for a
+        connected structure --, F4 (R, 4): FA, FB, FcAB, FAB in kcal/mol).  Seeds as for :meth:`sample_structures`: an integer
+        gives pair r the seed ``seed + r`` (mod 2^64), an array of R uint64 the seeds themselves; sample s of a pair depends on
+        the two sequences, its seed and s alone.  R is not limited by max_R."""
+        flat, R, L, cut = _split_pairs(seqs)
+        S = int(S)
+        seeds = _sample_seeds(seed, R)
+        ss = np.zeros((R, max(S, 0), L), dtype=np.uint8)
+        E = np.zeros((R, max(S, 0)), dtype=np.int32)
+        F4 = np.zeros((R, 4), dtype=np.float64)
+        self._check(self._L.drna_cofold_sample_structures_batch(self._h, R, L, cut, flat, S, seeds.ctypes.data, ss.ctypes.data,
+                                                                E.ctypes.data, F4.ctypes.data))
+        raw = ss.tobytes().decode("ascii")
+        out = [[raw[(r * S + k) * L:(r * S + k) * L + cut] + "&" + raw[(r * S + k) * L + cut:(r * S + k + 1) * L] for k in range(S)]
+               for r in range(R)]
+        return out, E, F4
 
     def last_edef_timing(self):
         out = (C.c_float * 2)()

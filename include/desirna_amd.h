@@ -234,6 +234,30 @@ int drna_ensemble_defect_batch_device(drna_engine *e, int R, int L, const char *
 int drna_sample_structures_batch(drna_engine *e, int R, int L, const char *seqs, int S, const uint64_t *seeds, char *ss,
                                  int32_t *E, double *Epf);
 
+/*
+ * Stochastic traceback for two strands: S co-fold structures per sequence pair drawn from the ensemble of drna_cofold_batch and
+ * drna_cofold_ensemble_defect_batch.  A structure of the concatenation weighs its Boltzmann factor under the partition
+ * function's loop model, times kappa if at least one pair joins the strands (kappa = expDuplexInit, halved when the two strands
+ * are the same sequence); the weights sum to exp(-FAB / kT), so p(structure) = weight / exp(-FAB / kT).  For X&X a structure and
+ * its rotation by `cut` are two structures, each with the halved weight.  Pairs as for drna_cofold_batch: total length L, both
+ * strands concatenated WITHOUT the '&', the first strand `cut` nucleotides long (1 <= cut < L <= max_L).  One inside fill
+ * (cofold_pf_kernel, always with its tables in the workspace, whatever "cofold_lds" says), one launch that rebuilds the exterior
+ * columns and one sample launch per chunk of workspace slots: R is not limited by max_R.
+ *   S      >= 1 samples per pair; R x S x L <= DRNA_SAMPLE_MAX_CHARS, beyond it DRNA_ERR_ARG
+ *   seeds  R uint64.  Sample s of pair r depends on the two sequences, seeds[r] and s ALONE, as for drna_sample_structures_batch:
+ *          draw k of sample s is u(seeds[r], s, k) of csrc/sample_rng.hpp, k = index of the walk's step
+ *   ss     R x S x L chars of ( ) . over the concatenation (no terminator, no '&')          out
+ *   E      R x S int32, dcal/mol: drna_cofold_batch's E(structure) of each sample, DuplexInit
+ *          included for a connected structure                                                out, may be NULL
+ *   F4     R x 4 doubles, kcal/mol: FA, FB, FcAB, FAB of the fill, as drna_cofold_batch        out, may be NULL
+ * A pair with a bad letter is DRNA_ERR_SEQUENCE, a partition function out of range DRNA_ERR_PF_RANGE, as for
+ * drna_cofold_ensemble_defect_batch; the outputs are then unspecified.  drna_last_edef_timing afterwards: out[0] = the inside
+ * kernel, out[1] = the columns and sample launches, summed over the chunks.  The read-only option "cofold_sample_calls" counts the
+ * sample launches.  A new symbol: no existing signature or buffer changes, DRNA_ABI_VERSION stays 3.
+ */
+int drna_cofold_sample_structures_batch(drna_engine *e, int R, int L, int cut, const char *seqs, int S, const uint64_t *seeds,
+                                        char *ss, int32_t *E, double *F4);
+
 /* device ms summed over the drna_score_batch[_device] calls since the last reset: out[0..3] as drna_last_timing, out[4] = number
  * of calls; out may be NULL (reset only).  Lets a caller time a loop of calls without a query per call. */
 int drna_timing_sums(drna_engine *e, double out[5], int reset);

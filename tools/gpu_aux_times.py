@@ -2,6 +2,9 @@
 Per shape the first round warms up and the median of the others is kept.
 `sampling` (kept as profiles/sampling.json): the stochastic traceback at R = 64 x L = 200 x S = 1,024 next to the ensemble defect of
 the same sequences, the other consumer of pf_kernel's tables.
+`cofold_sampling` (kept as profiles/cofold_sampling.json): the two-strand stochastic traceback at 64 pairs of 18+18, 50+50 and
+100+100 nt x S = 1,024 next to the two-strand ensemble defect of the same pairs and, at 100+100, the one-strand sampler on the
+same letters read as single strands of 200.
 `puzzle_set` (only when named; minutes): the Eterna100 set as a design run, lock-step batch against one puzzle after the other.
 `puzzle_set_aux` (only when named): the same pair for the puzzles of at most 200 nt with -nd on, and with an Edef term added."""
 import json
@@ -37,6 +40,29 @@ def sampling(eng, seqs):
     eng.ensemble_defect(seqs)
     t = eng.last_edef_timing()
     out["edef_ms"] = t["inside"] + t["outside"]
+    return out
+
+
+def cofold_sampling(eng, seqs):
+    """two-strand stochastic traceback (cofold_pf_kernel, then cofold_columns_kernel + cofold_sample_kernel, SAMPLES structures per
+    pair with their energies); the same call with ONE sample per pair (its second figure is the columns launch plus an all but
+    empty sample launch); drna_cofold_ensemble_defect_batch on the same pairs; at 100+100 also pf_kernel + sample_kernel on the
+    same letters as single strands"""
+    c0 = eng.get_option("cofold_sample_calls")
+    eng.cofold_sample_structures(seqs, SAMPLES, seed=1)
+    t = eng.last_edef_timing()
+    out = {"cofold_pf_ms": t["inside"], "columns_and_sample_ms": t["outside"], "sample_launches": eng.get_option("cofold_sample_calls") - c0}
+    eng.cofold_sample_structures(seqs, 1, seed=1)
+    out["columns_and_one_sample_ms"] = eng.last_edef_timing()["outside"]
+    eng.cofold_ensemble_defect(seqs)
+    t = eng.last_edef_timing()
+    out["cofold_edef_ms"] = t["inside"] + t["outside"]
+    flat = [s.replace("&", "") for s in seqs]
+    if len(flat[0]) == 200:
+        u8 = np.frombuffer("".join(flat).encode(), dtype=np.uint8).reshape(len(flat), -1)
+        eng.sample_structures_arrays(u8, SAMPLES, seed=1)
+        t = eng.last_edef_timing()
+        out["one_strand_pf_ms"], out["one_strand_sample_ms"] = t["inside"], t["outside"]
     return out
 
 
@@ -212,6 +238,8 @@ SECTIONS = {
            lambda R, v: ("defects_per_s", R / ((v["inside_ms"] + v["outside_ms"]) * 1e-3))),
     sampling: (((64, 200),), 20260101, True, 5,
                lambda R, v: ("samples_per_s", R * SAMPLES / (v["sample_ms"] * 1e-3))),
+    cofold_sampling: (PAIRS, 5, False, 5,
+                      lambda R, v: ("samples_per_s", R * SAMPLES / (v["columns_and_sample_ms"] * 1e-3))),
     cofold_subopt: (PAIRS, 5, False, 5, lambda R, v: ("ratio", v["cofold_subopt_ms"] / v["cofold_mfe_ms"])),
     cofold_edef: (PAIRS, 5, False, 5, lambda R, v: ("ratio", v["cofold_outside_ms"] / v["cofold_pf_ms"])),
     subopt_energy: (((64, 36), (64, SUB_MAX), (64, 18, 18), (64, 100), (64, 200)), 5, False, 5,
