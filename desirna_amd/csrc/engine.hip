@@ -31,6 +31,7 @@
 #include "fold_pf_strip.hpp"
 #include "fold_sample.hpp"
 #include "fold_cofold_sample.hpp"
+#include "fold_mea.hpp"
 #include "fold_subopt.hpp"
 #include "fold_cofold_subopt.hpp"
 #include "fold_subopt_lds.hpp"
@@ -95,6 +96,12 @@ struct drna_engine {
   // ... for two strands (fold_cofold_sample.hpp): the columns q5, qA3, qB5, q5c of ws_slots pairs, allocated on first use
   double* d_cocols = nullptr;
   int cofold_sample_calls = 0;   // launches of cofold_sample_kernel (read-only option "cofold_sample_calls")
+  // MEA and centroid structures (fold_mea.hpp): an all-unpaired pair table for the outside pass in front of them, allocated on first use
+  short* d_mea_pt = nullptr;
+  bool mea_lds = true;      // option "mea_lds": sequences of at most MEA_LDS_MAX nt keep the table M in LDS
+  int mea_calls = 0;        // launches of mea_kernel (read-only option "mea_calls")
+  int mea_cands = 0;        // candidate pairs the pruning left in the last call, all sequences (read-only option "mea_candidates")
+  float timing_mea[3] = {0, 0, 0};
   // ragged batches: per-sequence descriptors (len, off, target, two index lists) and the structures' pair tables.  Three blocks
   // of 7 max_R ints (rg_block): a lock-step loop keeps its scoring plan, its ensemble-defect plan and the second-best fold's
   // lists on the device side by side
@@ -400,7 +407,7 @@ extern "C" void drna_destroy(drna_engine* e) {
   void* bufs[] = {e->d_mfeT, e->d_pfT, e->d_plan, e->d_hp_len, e->d_bulge_len, e->d_int_len, e->d_hp_w, e->d_scale,
                   e->d_eMLb, e->d_ws_mfe, e->d_ws_pf, e->d_seqs, e->d_Epf, e->d_Emfe, e->d_ss, e->d_Ed, e->d_pt,
                   e->d_ws_out, e->d_edef, e->d_rg, e->d_rpt, e->d_rpt_off, e->d_F4, e->d_ws_kb, e->d_kbE, e->d_kbss,
-                  e->dflags.d, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->sflags.d, e->d_srec, e->d_sdbg, e->d_sclk, e->pflags.d, e->d_q5s, e->d_cocols};
+                  e->dflags.d, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->sflags.d, e->d_srec, e->d_sdbg, e->d_sclk, e->pflags.d, e->d_q5s, e->d_cocols, e->d_mea_pt};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_status) (void)hipHostFree(e->h_status);
@@ -430,6 +437,7 @@ extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!strcmp(name, "cofold_lds")) { e->cofold_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds")) { e->subopt_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "edef_lds")) { e->edef_lds = value != 0; return DRNA_OK; }
+  if (!strcmp(name, "mea_lds")) { e->mea_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "self_dimer_lds")) { e->self_dimer_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "helper_fault")) { e->helper_fault = value != 0; return DRNA_OK; }
   if (!strcmp(name, "strip_fault")) { e->strip_fault = value != 0; return DRNA_OK; }
@@ -463,6 +471,10 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "edef_lds_calls")) { *value = e->edef_lds_calls; return DRNA_OK; }
   if (!strcmp(name, "sample_calls")) { *value = e->sample_calls; return DRNA_OK; }
   if (!strcmp(name, "cofold_sample_calls")) { *value = e->cofold_sample_calls; return DRNA_OK; }
+  if (!strcmp(name, "mea_lds")) { *value = e->mea_lds ? 1 : 0; return DRNA_OK; }
+  if (!strcmp(name, "mea_lds_max")) { *value = MEA_LDS_MAX; return DRNA_OK; }
+  if (!strcmp(name, "mea_calls")) { *value = e->mea_calls; return DRNA_OK; }
+  if (!strcmp(name, "mea_candidates")) { *value = e->mea_cands; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds")) { *value = e->subopt_lds ? 1 : 0; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds_max")) { *value = SUB_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "self_dimer_lds")) { *value = e->self_dimer_lds ? 1 : 0; return DRNA_OK; }
@@ -1252,6 +1264,131 @@ extern "C" int drna_cofold_sample_structures_batch(drna_engine* e, int R, int L,
         if (F4) HIP_TRY(hipMemcpy(F4 + (size_t)4 * r0, e->d_F4, (size_t)4 * m * sizeof(double), hipMemcpyDeviceToHost));
         return DRNA_OK;
       });
+}
+
+// ---------------------------------------------------------------- MEA and centroid structures (fold_mea.hpp)
+
+constexpr int MEA_NT = 512;         // 64 cells of a diagonal at a time (MEA_GW lanes each)
+
+// the device buffers of one call: the chunk's pair probabilities and what mea_kernel returns per sequence
+struct MeaBuffers {
+  double *bpp = nullptr, *val = nullptr, *dist = nullptr;
+  char *mss = nullptr, *css = nullptr;
+  int32_t *E = nullptr, *nc = nullptr;
+  ~MeaBuffers() {
+    for (void* p : {(void*)bpp, (void*)val, (void*)dist, (void*)mss, (void*)css, (void*)E, (void*)nc})
+      if (p) (void)hipFree(p);
+  }
+};
+
+// mea_kernel on the m matrices of a chunk (timed: timing_mea[2] grows by the launch); the stream is idle before and after
+static int mea_launch(drna_engine* e, int m, int L, int cut, double gamma, const MeaBuffers& b, bool want_E) {
+  MeaArgs a;
+  a.ev = eval_args(e, e->d_seqs, L, nullptr);
+  a.ev.cut = cut; a.ev.DuplexInit = cut ? e->H.DuplexInit : 0;
+  a.bpp = b.bpp; a.ws = e->d_ws_out; a.ws_stride = outside_ws_stride(L + 2); a.gamma = gamma;
+  a.mea_ss = b.mss; a.mea_val = b.val; a.cen_ss = b.css; a.cen_dist = b.dist; a.E = want_E ? b.E : nullptr; a.ncand = b.nc;
+  e->mea_calls++;
+  HIP_TRY(hipEventRecord(e->ev_o0, e->s_pf));
+  if (e->mea_lds && L <= MEA_LDS_MAX) hipLaunchKernelGGL((mea_kernel<MEA_NT, true>), dim3(m), dim3(MEA_NT), 0, e->s_pf, a);
+  else hipLaunchKernelGGL((mea_kernel<MEA_NT, false>), dim3(m), dim3(MEA_NT), 0, e->s_pf, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_o1, e->s_pf));
+  HIP_TRY(hipStreamSynchronize(e->s_pf));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, e->ev_o0, e->ev_o1));
+  e->timing_mea[2] += ms;
+  return DRNA_OK;
+}
+
+// the chunks of a call: inside and outside pass by edef_batch_device against the all-unpaired pair table (its edef is dropped),
+// then mea_kernel on the chunk's matrices
+static int mea_chunks(drna_engine* e, int R, int L, int cut, const char* seqs, double gamma, char* mea_ss, double* mea_val,
+                      char* cen_ss, double* cen_dist, int32_t* E, double* bpp, int step, const MeaBuffers& b) {
+  const size_t cells = (size_t)(L + 1) * (L + 1);
+  std::vector<int32_t> nc(step);
+  for (int r0 = 0; r0 < R; r0 += step) {
+    const int m = std::min(step, R - r0);
+    HIP_TRY(hipMemcpy(e->d_seqs, seqs + (size_t)r0 * L, (size_t)m * L, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(b.bpp, 0, (size_t)m * cells * sizeof(double), e->s_pf));     // the outside pass writes the pairs only
+    float t[2] = {0, 0};
+    int rc = edef_batch_device(e, m, L, cut, e->d_seqs, e->d_edef, b.bpp, r0, t);
+    if (rc != DRNA_OK) return rc;
+    e->timing_mea[0] += t[0]; e->timing_mea[1] += t[1];
+    rc = mea_launch(e, m, L, cut, gamma, b, E != nullptr);
+    if (rc != DRNA_OK) return rc;
+    HIP_TRY(hipMemcpy(mea_ss + (size_t)r0 * L, b.mss, (size_t)m * L, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cen_ss + (size_t)r0 * L, b.css, (size_t)m * L, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mea_val + r0, b.val, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cen_dist + r0, b.dist, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
+    if (E) HIP_TRY(hipMemcpy(E + 2 * (size_t)r0, b.E, 2 * (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (bpp) HIP_TRY(hipMemcpy(bpp + (size_t)r0 * cells, b.bpp, (size_t)m * cells * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nc.data(), b.nc, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int q = 0; q < m; q++) e->mea_cands = (int)std::min<long long>((long long)e->mea_cands + nc[q], 0x7fffffff);
+  }
+  return DRNA_OK;
+}
+
+// cut = 0: one strand.  Needs no installed targets and leaves them alone
+static int mea_batch_host(drna_engine* e, const char* who, int R, int L, int cut, const char* seqs, double gamma, char* mea_ss,
+                          double* mea_val, char* cen_ss, double* cen_dist, int32_t* E, double* bpp) {
+  {
+    const bool ok = gamma > 0.0 && std::isfinite(gamma) && seqs && mea_ss && mea_val && cen_ss && cen_dist;
+    const int rc = aux_check(e, who, std::min(R, e->max_R), L, cut ? &cut : nullptr, ok,
+                             "gamma > 0 and finite; seqs, mea_ss, mea_val, cen_ss and cen_dist required");
+    if (rc != DRNA_OK) return rc;
+  }
+  // a failed call leaves zeros
+  memset(mea_ss, 0, (size_t)R * L); memset(cen_ss, 0, (size_t)R * L);
+  std::fill(mea_val, mea_val + R, 0.0); std::fill(cen_dist, cen_dist + R, 0.0);
+  if (E) std::fill(E, E + 2 * (size_t)R, 0);
+  HIP_TRY(hipSetDevice(e->device));
+  { const int rc = outside_workspace(e); if (rc != DRNA_OK) return rc; }      // M beyond MEA_LDS_MAX, candidate lists beyond MEA_CAND_LDS
+  if (3ll * (L + 2) * (L + 2) > outside_ws_stride(L + 2)) { e->err = std::string(who) + ": workspace slot too small"; return DRNA_ERR_INTERNAL; }
+  if (!e->d_edef) HIP_TRY(hipMalloc((void**)&e->d_edef, (size_t)e->max_R * sizeof(double)));
+  if (!e->d_mea_pt) {
+    HIP_TRY(hipMalloc((void**)&e->d_mea_pt, (size_t)(e->max_L + 2) * sizeof(short)));
+    HIP_TRY(hipMemset(e->d_mea_pt, 0, (size_t)(e->max_L + 2) * sizeof(short)));
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  const int step = std::min(std::min(e->ws_slots, e->max_R), R);
+  const size_t cells = (size_t)(L + 1) * (L + 1);
+  MeaBuffers b;
+  if (hipMalloc((void**)&b.bpp, (size_t)step * cells * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&b.val, (size_t)step * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&b.dist, (size_t)step * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&b.mss, (size_t)step * L) != hipSuccess || hipMalloc((void**)&b.css, (size_t)step * L) != hipSuccess ||
+      hipMalloc((void**)&b.E, 2 * (size_t)step * sizeof(int32_t)) != hipSuccess ||
+      hipMalloc((void**)&b.nc, (size_t)step * sizeof(int32_t)) != hipSuccess) {
+    e->err = std::string(who) + ": hipMalloc of the call's buffers failed";
+    return DRNA_ERR_DEVICE;
+  }
+  e->timing_mea[0] = e->timing_mea[1] = e->timing_mea[2] = 0;
+  e->mea_cands = 0;
+  short* const installed = e->d_pt;
+  e->d_pt = e->d_mea_pt;
+  const int rc = mea_chunks(e, R, L, cut, seqs, gamma, mea_ss, mea_val, cen_ss, cen_dist, E, bpp, step, b);
+  e->d_pt = installed;
+  return rc;
+}
+
+extern "C" int drna_mea_structures_batch(drna_engine* e, int R, int L, const char* seqs, double gamma, char* mea_ss, double* mea_val,
+                                         char* cen_ss, double* cen_dist, int32_t* E, double* bpp) {
+  if (!e) return DRNA_ERR_ARG;
+  return mea_batch_host(e, "drna_mea_structures_batch", R, L, 0, seqs, gamma, mea_ss, mea_val, cen_ss, cen_dist, E, bpp);
+}
+
+extern "C" int drna_cofold_mea_structures_batch(drna_engine* e, int R, int L, int cut, const char* seqs, double gamma, char* mea_ss,
+                                                double* mea_val, char* cen_ss, double* cen_dist, int32_t* E, double* bpp) {
+  if (!e) return DRNA_ERR_ARG;
+  if (cut < 1 || cut >= L) { e->err = "drna_cofold_mea_structures_batch: bad argument (1 <= cut < L)"; return DRNA_ERR_ARG; }
+  return mea_batch_host(e, "drna_cofold_mea_structures_batch", R, L, cut, seqs, gamma, mea_ss, mea_val, cen_ss, cen_dist, E, bpp);
+}
+
+extern "C" int drna_last_mea_timing(const drna_engine* e, float out[3]) {
+  if (!e || !out) return DRNA_ERR_ARG;
+  for (int k = 0; k < 3; k++) out[k] = e->timing_mea[k];
+  return DRNA_OK;
 }
 
 // ---------------------------------------------------------------- ragged batches (sequences of different lengths)

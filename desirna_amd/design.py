@@ -868,9 +868,52 @@ def ensemble_report(engine, result, input_file, S, top=5, seed=0):
     return rows
 
 
+KT_37 = 1.98717e-3 * 310.15          # kcal/mol at 37 C: the engine's partition functions are taken at this temperature
+
+
+def structure_report(engine, result, input_file, gamma=1.0):
+    """Which single structure stands for the ensemble of each reported sequence: beside the MFE structure the two predictors read
+    from the pair probabilities, the centroid (the pairs with P > 1/2) and the maximum-expected-accuracy structure for the weight
+    ``gamma`` (``engine.mea_structures``; two strands ``engine.cofold_mea_structures``; ViennaRNA's fc.centroid() and fc.MEA()).
+    "MFE = target" with a centroid that is something else is the classic fragile design.  The reported sequences are chosen as in
+    :func:`ensemble_report`.  Returns the rows of ``<name>_structures.csv`` (``outputs.STRUCTURE_COLUMNS``), three per sequence,
+    ``kind`` = ``mfe``, ``centroid``, ``mea``: the structure, its energy in kcal/mol, ``Epf`` (two strands: FAB), its probability
+    ``p_structure = exp(-(energy - Epf) / kT)``, ``value`` (blank / the centroid's expected base-pair distance to the ensemble /
+    the MEA structure's expected accuracy) and ``mcc``, 1 - MCC to the target (``&`` -> ``Ee`` for two strands)."""
+    import math
+    from . import engine as _engine
+    from . import outputs
+    target = input_file.sec_struct
+    two = "&" in target
+    seqs = list(result.get("reported") or [r["sequence"] for r in outputs.sort_and_filter(result["simulation_data"])])
+    step = max(1, int(getattr(engine, "max_R", len(seqs)) or len(seqs)))
+    mfe_ss, Emfe, Epf = [], [], []
+    for r0 in range(0, len(seqs), step):           # (the scoring entry points take max_R sequences at a time)
+        part = seqs[r0:r0 + step]
+        flags = _engine.NEED_PF | _engine.NEED_MFE
+        out = engine.cofold_batch(part, flags) if two else engine.score_batch(part, flags)
+        mfe_ss += list(out["mfe_ss"])
+        Emfe += [int(x) for x in out["Emfe"]]
+        Epf += [float(x) for x in (out["FAB"] if two else out["Epf"])]
+    m = engine.cofold_mea_structures(seqs, gamma) if two else engine.mea_structures(seqs, gamma)
+    hk = _engine.HostKernels()
+    rows = []
+    for r, seq in enumerate(seqs):
+        listed = [mfe_ss[r], m["centroid"][r], m["mea"][r], target]
+        sub = [s.replace("&", "Ee") for s in listed]         # the '&' -> 'Ee' substitution of every two-strand 1 - MCC
+        mcc = 1.0 - hk.simscore(sub[-1], np.frombuffer("".join(sub).encode("ascii"), dtype=np.uint8).reshape(len(sub), -1))[0]
+        energy = [Emfe[r] / 100.0, int(m["E"][r][1]) / 100.0, int(m["E"][r][0]) / 100.0]
+        value = ["", float(m["centroid_distance"][r]), float(m["mea_value"][r])]
+        for k, kind in enumerate(("mfe", "centroid", "mea")):
+            rows.append(dict(sequence=seq, Epf=Epf[r], kind=kind, structure=listed[k], energy=energy[k],
+                             p_structure=math.exp(-(energy[k] - Epf[r]) / KT_37), value=value[k], mcc=float(mcc[k])))
+    return rows
+
+
 def _cli_report(a, filename, inp, res):
     """What the command line leaves of one finished design: with -o the reference's result files (and, with --ensemble, the
-    sampled ensemble of every reported sequence beside them), and the summary lines"""
+    sampled ensemble of every reported sequence beside them; with --structures, their MFE, centroid and MEA structures), and the
+    summary lines"""
     if a.outdir:
         import os
         from . import outputs
@@ -893,6 +936,11 @@ def _cli_report(a, filename, inp, res):
             rows = ensemble_report(eng, dict(res, reported=[r["sequence"] for r in ranked]), inp, a.ensemble, a.ensemble_top,
                                    a.ensemble_seed)
             outputs.write_ensemble(rows, outname, a.outdir)
+        if a.structures:
+            from . import engine as _engine
+            eng = res.get("engine") or _engine.Engine(max_R=max(1, len(ranked)), max_L=len(inp.sec_struct))
+            rows = structure_report(eng, dict(res, reported=[r["sequence"] for r in ranked]), inp, a.structures)
+            outputs.write_structures(rows, outname, a.outdir)
     b = res["best"]
     print("Design solved succesfully!" if res["solved"] else "Design not solved.")
     print(b.sequence)
@@ -935,7 +983,14 @@ def main(argv=None):
                     "ensemble of every reported sequence and write <name>_ensemble.csv beside _results.csv (needs -o; one strand)")
     ap.add_argument("--ensemble-top", type=int, default=5, metavar="T", help="structures listed per sequence, most frequent first")
     ap.add_argument("--ensemble-seed", type=int, default=0, help="seed of the samples (sequence r of the report: seed + r)")
+    ap.add_argument("--structures", type=float, default=None, metavar="GAMMA", help="after the run, write the MFE, centroid and "
+                    "maximum-expected-accuracy structure (weight GAMMA > 0) of every reported sequence into <name>_structures.csv "
+                    "beside _results.csv (needs -o; one or two strands)")
     a = ap.parse_args(argv)
+    if a.structures is not None and not (a.structures > 0 and a.structures < float("inf")):
+        ap.error("--structures takes a weight GAMMA > 0")
+    if a.structures and not a.outdir:
+        ap.error("--structures writes its file beside _results.csv: give -o")
     if a.ensemble < 0 or a.ensemble_top < 1:
         ap.error("--ensemble takes S >= 1 and --ensemble-top T >= 1")
     if a.ensemble and not a.outdir:

@@ -77,6 +77,9 @@ _SIGNATURES = {
     "drna_rng_random": (_ci, [_ci, _vp, _vp]),
     "drna_sample_structures_batch": (_ci, [_vp, _ci, _ci, _str, _ci, _vp, _vp, _vp, _vp]),
     "drna_cofold_sample_structures_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _ci, _vp, _vp, _vp, _vp]),
+    "drna_mea_structures_batch": (_ci, [_vp, _ci, _ci, _str, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drna_cofold_mea_structures_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drna_last_mea_timing": (_ci, [_vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -623,6 +626,50 @@ class Engine:
         out = [[raw[(r * S + k) * L:(r * S + k) * L + cut] + "&" + raw[(r * S + k) * L + cut:(r * S + k + 1) * L] for k in range(S)]
                for r in range(R)]
         return out, E, F4
+
+    def _mea(self, flat, R, L, cut, gamma, want_bpp):
+        mea = np.zeros((R, L), dtype=np.uint8)
+        cen = np.zeros((R, L), dtype=np.uint8)
+        val = np.zeros(R, dtype=np.float64)
+        dist = np.zeros(R, dtype=np.float64)
+        E = np.zeros((R, 2), dtype=np.int32)
+        bpp = np.zeros((R, L + 1, L + 1), dtype=np.float64) if want_bpp else None
+        tail = (float(gamma), mea.ctypes.data, val.ctypes.data, cen.ctypes.data, dist.ctypes.data, E.ctypes.data,
+                bpp.ctypes.data if want_bpp else None)
+        if cut:
+            self._check(self._L.drna_cofold_mea_structures_batch(self._h, R, L, cut, flat, *tail))
+        else:
+            self._check(self._L.drna_mea_structures_batch(self._h, R, L, flat, *tail))
+        put = (lambda x: x[:cut] + "&" + x[cut:]) if cut else (lambda x: x)
+        txt = lambda a: [put(row.tobytes().decode("ascii")) for row in a]
+        out = {"mea": txt(mea), "mea_value": val, "centroid": txt(cen), "centroid_distance": dist, "E": E}
+        if want_bpp:
+            out["bpp"] = bpp
+        return out
+
+    def mea_structures(self, seqs, gamma=1.0, want_bpp=False):
+        """The two structures that represent each sequence's ensemble, read from its pair probabilities on the device
+        (ViennaRNA's fc.MEA(gamma) and fc.centroid(); drna_mea_structures_batch).  Returns a dict: ``mea`` (R dot-bracket
+        strings, a maximiser of the expected accuracy sum_unpaired q(i) + 2 gamma sum_pairs P(i,j)), ``mea_value`` (R,),
+        ``centroid`` (the pairs with P > 1/2), ``centroid_distance`` (R,; its expected base-pair distance to the ensemble),
+        ``E`` ((R, 2) int32, dcal/mol: MEA, centroid) and, with want_bpp, ``bpp`` ((R, L+1, L+1), the matrix of
+        :meth:`ensemble_defect`).  Needs no targets and leaves installed ones alone; R is not limited by max_R."""
+        u8 = np.ascontiguousarray(_as_u8(seqs), dtype=np.uint8)
+        R, L = u8.shape
+        return self._mea(u8.ctypes.data_as(C.c_char_p), R, L, 0, gamma, want_bpp)
+
+    def cofold_mea_structures(self, seqs, gamma=1.0, want_bpp=False):
+        """Two strands: :meth:`mea_structures` of each 'AAAA&BBBB' pair in the ensemble of :meth:`cofold_ensemble_defect`
+        (drna_cofold_mea_structures_batch).  The strings carry the ``&`` at the cut; ``E`` is :meth:`cofold_batch`'s
+        E(structure), DuplexInit included for a connected structure; ``bpp`` is over the concatenation."""
+        flat, R, L, cut = _split_pairs(seqs)
+        return self._mea(flat, R, L, cut, gamma, want_bpp)
+
+    def last_mea_timing(self):
+        """device ms of the last :meth:`mea_structures` / :meth:`cofold_mea_structures` call, summed over its chunks"""
+        out = (C.c_float * 3)()
+        self._check(self._L.drna_last_mea_timing(self._h, out))
+        return {"inside": out[0], "outside": out[1], "mea": out[2]}
 
     def last_edef_timing(self):
         out = (C.c_float * 2)()

@@ -216,3 +216,24 @@ def write_ensemble(rows, outname, directory="."):
     with open(path, 'w', newline='', encoding='utf-8') as fh:
         fh.write(ensemble_csv_text(rows))
     return path
+
+
+STRUCTURE_COLUMNS = ("sequence", "Epf", "kind", "structure", "energy", "p_structure", "value", "mcc")
+
+
+def structures_csv_text(rows):
+    """rows of design.structure_report: per sequence its MFE, centroid and MEA structure (kind mfe / centroid / mea)"""
+    buf = io.StringIO(newline='')
+    w = csv.DictWriter(buf, fieldnames=list(STRUCTURE_COLUMNS))
+    w.writeheader()
+    for r in rows:
+        w.writerow(round_floats(dict(r)))
+    return buf.getvalue()
+
+
+def write_structures(rows, outname, directory="."):
+    import os
+    path = os.path.join(directory, outname + '_structures.csv')
+    with open(path, 'w', newline='', encoding='utf-8') as fh:
+        fh.write(structures_csv_text(rows))
+    return path

@@ -258,6 +258,42 @@ int drna_sample_structures_batch(drna_engine *e, int R, int L, const char *seqs,
 int drna_cofold_sample_structures_batch(drna_engine *e, int R, int L, int cut, const char *seqs, int S, const uint64_t *seeds,
                                         char *ss, int32_t *E, double *F4);
 
+/*
+ * The two structures that represent an ensemble, from its pair probabilities (csrc/fold_mea.hpp; ViennaRNA's fc.MEA(gamma) and
+ * fc.centroid()).  P(i,j), 1 <= i < j <= L, is what drna_ensemble_defect_batch (two strands: drna_cofold_ensemble_defect_batch,
+ * over the concatenation without '&') returns in bpp -- same values, same layout [i*(L+1)+j].
+ *   q(i)       = 1 - sum_j P(min(i,j), max(i,j)), summed in ascending j, not clamped
+ *   EA(s)      = sum_{i unpaired in s} q(i) + 2 gamma sum_{(i,j) in s} P(i,j)     for a nested set s of pairs with P > 0
+ *   MEA        a maximiser of EA:  M(i,i-1) = 0,
+ *              M(i,j) = max( M(i,j-1) + q(j), max_{i <= k < j, P(k,j) > 0} M(i,k-1) + M(k+1,j-1) + 2 gamma P(k,j) ), value M(1,L).
+ *              Tie rule: "j unpaired" first, then k ascending; a later candidate replaces only if it is strictly greater.
+ *              No hairpin-length or pair-type rule of its own: P > 0 carries both, and for two strands the nick.
+ *   centroid   {(i,j) : P(i,j) > 0.5}, always nested; distance = sum_{(i,j) in c} (1 - P(i,j)) + sum_{(i,j) not in c} P(i,j)
+ * Arguments:
+ *   gamma      > 0 and finite, else DRNA_ERR_ARG
+ *   mea_ss     R x L chars of ( ) . (no terminator, no '&')                               out
+ *   mea_val    R doubles: EA of mea_ss, M(1,L)                                            out
+ *   cen_ss     R x L chars                                                                out
+ *   cen_dist   R doubles: expected base-pair distance of the centroid to the ensemble     out
+ *   E          R x 2 int32, dcal/mol: drna_score_batch's (two strands: drna_cofold_batch's, DuplexInit included for a connected
+ *              structure) E(structure) of mea_ss and of cen_ss                            out, may be NULL
+ *   bpp        R*(L+1)*(L+1) doubles: the matrix both structures were read from           out, may be NULL
+ * A NULL among seqs, mea_ss, mea_val, cen_ss, cen_dist is DRNA_ERR_ARG.  R is not limited by max_R (chunks of the workspace
+ * slots).  The calls need no drna_set_targets() and leave installed targets untouched.  A sequence with a bad letter is
+ * DRNA_ERR_SEQUENCE, a partition function out of range DRNA_ERR_PF_RANGE, as for drna_ensemble_defect_batch; the outputs
+ * then hold zeros.  Options (drna_set_option / drna_get_option): "mea_lds" (default 1) keeps the table M of sequences of at most
+ * "mea_lds_max" (read-only) nucleotides in LDS, 0 puts it into the workspace for every length -- the results are the same bits
+ * either way; "mea_calls" (read-only) counts the MEA launches, "mea_candidates" (read-only) the pairs the last call's pruning
+ * kept, all sequences.  drna_last_mea_timing: device ms of the last call's inside, outside and MEA launches, summed over its chunks
+ * (short inputs take the fused inside + outside launch: out[1] is then ~0).
+ * New symbols: no existing signature or buffer changes, DRNA_ABI_VERSION stays 3.
+ */
+int drna_mea_structures_batch(drna_engine *e, int R, int L, const char *seqs, double gamma, char *mea_ss, double *mea_val,
+                              char *cen_ss, double *cen_dist, int32_t *E, double *bpp);
+int drna_cofold_mea_structures_batch(drna_engine *e, int R, int L, int cut, const char *seqs, double gamma, char *mea_ss,
+                                     double *mea_val, char *cen_ss, double *cen_dist, int32_t *E, double *bpp);
+int drna_last_mea_timing(const drna_engine *e, float out[3]);
+
 /* device ms summed over the drna_score_batch[_device] calls since the last reset: out[0..3] as drna_last_timing, out[4] = number
  * of calls; out may be NULL (reset only).  Lets a caller time a loop of calls without a query per call. */
 int drna_timing_sums(drna_engine *e, double out[5], int reset);

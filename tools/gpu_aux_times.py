@@ -5,6 +5,9 @@ the same sequences, the other consumer of pf_kernel's tables.
 `cofold_sampling` (kept as profiles/cofold_sampling.json): the two-strand stochastic traceback at 64 pairs of 18+18, 50+50 and
 100+100 nt x S = 1,024 next to the two-strand ensemble defect of the same pairs and, at 100+100, the one-strand sampler on the
 same letters read as single strands of 200.
+`mea` (kept as profiles/mea.json): MEA and centroid structures (drna_mea_structures_batch) at R = 64 x L = 36, 100, 200, 400 and pairs
+of 30+27 and 100+100: the inside, outside and MEA launches of the same call, the MEA launch with M in LDS and in the workspace
+where the length allows both, and the candidates per column the pruning leaves.
 `puzzle_set` (only when named; minutes): the Eterna100 set as a design run, lock-step batch against one puzzle after the other.
 `puzzle_set_aux` (only when named): the same pair for the puzzles of at most 200 nt with -nd on, and with an Edef term added."""
 import json
@@ -63,6 +66,25 @@ def cofold_sampling(eng, seqs):
         eng.sample_structures_arrays(u8, SAMPLES, seed=1)
         t = eng.last_edef_timing()
         out["one_strand_pf_ms"], out["one_strand_sample_ms"] = t["inside"], t["outside"]
+    return out
+
+
+def mea(eng, seqs):
+    """MEA and centroid structures with their energies at gamma = 1: the three launches of the call (short inputs: inside and
+    outside are ONE fused launch, outside_ms ~ 0), the candidates per column that the pruning leaves, and, where M fits LDS, the MEA
+    launch with M in the workspace instead"""
+    two = "&" in seqs[0]
+    call = eng.cofold_mea_structures if two else eng.mea_structures
+    L = len(seqs[0].replace("&", ""))
+    call(seqs, 1.0)
+    t = eng.last_mea_timing()
+    out = {"inside_ms": t["inside"], "outside_ms": t["outside"], "mea_ms": t["mea"],
+           "candidates_per_column": eng.get_option("mea_candidates") / (len(seqs) * L)}
+    if L <= eng.get_option("mea_lds_max"):
+        eng.set_option("mea_lds", 0)
+        call(seqs, 1.0)
+        eng.set_option("mea_lds", 1)
+        out["mea_ms_workspace"] = eng.last_mea_timing()["mea"]
     return out
 
 
@@ -254,6 +276,8 @@ SECTIONS = {
     self_dimer: (((64, 36), (64, SD_MAX), (64, 100)), 5, False, 7, lambda R, v: ("lds_over_general", v["pf_ms_lds1"] / v["pf_ms_lds0"])),
     edef_paths: (((64, 36), (64, 18, 18), (64, EDEF_MAX), (64, CO_EDEF_MAX // 2, CO_EDEF_MAX - CO_EDEF_MAX // 2)), 5, False, 5,
                  lambda R, v: ("lds_over_general", v["edef_ms_lds1"] / v["edef_ms_lds0"])),
+    mea: (((64, 36), (64, 100), (64, 200), (64, 400), (64, 30, 27), (64, 100, 100)), 5, False, 5,
+          lambda R, v: ("mea_over_inside_outside", v["mea_ms"] / (v["inside_ms"] + v["outside_ms"]))),
     mc_cofold: (((64, 18, 18),), 5, False, 3,
                 lambda R, v: ("native_over_python", v["design_native_iter_per_s"] / v["design_python_iter_per_s"])),
 }
