@@ -37,6 +37,7 @@
 #include "fold_subopt_lds.hpp"
 #include "fold_cofold_outside.hpp"
 #include "fold_edef_lds.hpp"
+#include "fold_access.hpp"
 #include "host_driver.hpp"
 #include "tables.hpp"
 
@@ -115,6 +116,13 @@ struct drna_engine {
   bool self_dimer_lds = true;   // option "self_dimer_lds": self-dimers of at most SD_LDS_MAX nt keep their tables in LDS (fold_self_dimer.hpp)
   bool edef_lds = true;     // option "edef_lds": ensemble defects of at most EDEF_LDS_HOST_MAX nt (pairs: CO_EDEF_LDS_MAX) in one launch, tables in LDS (fold_edef_lds.hpp)
   int edef_lds_calls = 0;   // launches of that kernel (read-only option "edef_lds_calls")
+  // partition function with positions held unpaired (fold_access.hpp): the masks of the last call on the device, grown on demand
+  unsigned char* d_nopair = nullptr;
+  size_t nopair_cap = 0;
+  bool access_lds = true;   // option "access_lds": sequences of at most ACCESS_LDS_HOST_MAX nt keep their tables in LDS (access_lds_kernel)
+  bool access_lds_force = false;   // option "access_lds" = 2: up to the kernel's own ACCESS_LDS_MAX (tests, the timing tool)
+  int access_lds_calls = 0; // launches of that kernel (read-only option "access_lds_calls")
+  float timing_access = 0;  // device time of the last drna_pf_unpaired_batch call, its chunks summed (drna_last_access_timing)
   bool subopt_lds = true;   // option "subopt_lds": second-best folds of at most SUB_LDS_MAX nt keep their tables in LDS (fold_subopt_lds.hpp)
   // K-best structures: workspace for kb_chunk sequences, allocated on first use
   int32_t* d_ws_kb = nullptr;
@@ -407,7 +415,7 @@ extern "C" void drna_destroy(drna_engine* e) {
   void* bufs[] = {e->d_mfeT, e->d_pfT, e->d_plan, e->d_hp_len, e->d_bulge_len, e->d_int_len, e->d_hp_w, e->d_scale,
                   e->d_eMLb, e->d_ws_mfe, e->d_ws_pf, e->d_seqs, e->d_Epf, e->d_Emfe, e->d_ss, e->d_Ed, e->d_pt,
                   e->d_ws_out, e->d_edef, e->d_rg, e->d_rpt, e->d_rpt_off, e->d_F4, e->d_ws_kb, e->d_kbE, e->d_kbss,
-                  e->dflags.d, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->sflags.d, e->d_srec, e->d_sdbg, e->d_sclk, e->pflags.d, e->d_q5s, e->d_cocols, e->d_mea_pt};
+                  e->dflags.d, e->d_xs, e->d_xa_mfe, e->d_xb_mfe, e->sflags.d, e->d_srec, e->d_sdbg, e->d_sclk, e->pflags.d, e->d_q5s, e->d_cocols, e->d_mea_pt, e->d_nopair};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_status) (void)hipHostFree(e->h_status);
@@ -437,6 +445,7 @@ extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!strcmp(name, "cofold_lds")) { e->cofold_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "subopt_lds")) { e->subopt_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "edef_lds")) { e->edef_lds = value != 0; return DRNA_OK; }
+  if (!strcmp(name, "access_lds")) { e->access_lds = value != 0; e->access_lds_force = value == 2; return DRNA_OK; }
   if (!strcmp(name, "mea_lds")) { e->mea_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "self_dimer_lds")) { e->self_dimer_lds = value != 0; return DRNA_OK; }
   if (!strcmp(name, "helper_fault")) { e->helper_fault = value != 0; return DRNA_OK; }
@@ -469,6 +478,10 @@ extern "C" int drna_get_option(const drna_engine* e, const char* name, int* valu
   if (!strcmp(name, "edef_lds_max")) { *value = EDEF_LDS_HOST_MAX; return DRNA_OK; }     // what the host sends there; the kernel holds EDEF_LDS_MAX
   if (!strcmp(name, "cofold_edef_lds_max")) { *value = CO_EDEF_LDS_MAX; return DRNA_OK; }
   if (!strcmp(name, "edef_lds_calls")) { *value = e->edef_lds_calls; return DRNA_OK; }
+  if (!strcmp(name, "access_lds")) { *value = e->access_lds ? (e->access_lds_force ? 2 : 1) : 0; return DRNA_OK; }
+  if (!strcmp(name, "access_lds_max")) { *value = ACCESS_LDS_HOST_MAX; return DRNA_OK; }     // what the host sends there ...
+  if (!strcmp(name, "access_lds_kernel_max")) { *value = ACCESS_LDS_MAX; return DRNA_OK; }   // ... and what the kernel holds
+  if (!strcmp(name, "access_lds_calls")) { *value = e->access_lds_calls; return DRNA_OK; }
   if (!strcmp(name, "sample_calls")) { *value = e->sample_calls; return DRNA_OK; }
   if (!strcmp(name, "cofold_sample_calls")) { *value = e->cofold_sample_calls; return DRNA_OK; }
   if (!strcmp(name, "mea_lds")) { *value = e->mea_lds ? 1 : 0; return DRNA_OK; }
@@ -2064,6 +2077,75 @@ extern "C" int drna_self_dimer_batch(drna_engine* e, int R, int L, const char* s
   e->timing[1] = e->timing[3] = ms;
   if (oligo_frac)
     for (int r = 0; r < R; r++) oligo_frac[r] = oligo_fraction(F4[4 * (size_t)r], F4[4 * (size_t)r + 1], F4[4 * (size_t)r + 2]);
+  return DRNA_OK;
+}
+
+// ---------------------------------------------------------------- partition function with positions held unpaired (fold_access.hpp)
+
+// m (sequence, mask) pairs, g0 the first (pair g = sequence g / M under mask g % M), whose sequences -- seq0 the first -- the
+// caller has put into hm_seqs and whose M masks are in d_nopair: ONE launch on the partition function's stream, pair g0 + b in
+// workspace slot / status word b, F into hm_Epf[b] (general kernel) or hm_F4[4 b] (tables in LDS); no hipMemcpy.  The caller's
+// other launches have drained (the self-dimer step's rule).  An error names the pair's sequence
+static int access_mapped(drna_engine* e, int m, int L, int M, int g0, int seq0, bool lds) {
+  reset_status(e);
+  HIP_TRY(hipEventRecord(e->ev_p0, e->s_pf));
+  if (lds) {
+    AccessLdsArgs a;
+    a.in = co_args(e, e->dm_seqs, L, L, 0);
+    a.in.F4 = e->dm_F4;
+    a.nopair = e->d_nopair; a.M = M; a.fold0 = g0; a.seq0 = seq0;
+    e->access_lds_calls++;
+    hipLaunchKernelGGL(access_lds_kernel<1024>, dim3(m), dim3(1024), 0, e->s_pf, a);
+  } else {
+    PfMaskArgs a;
+    static_cast<PfArgs&>(a) = pf_args(e, e->dm_seqs, L, L + 2, e->dm_Epf);
+    a.nopair = e->d_nopair; a.M = M; a.fold0 = g0; a.seq0 = seq0;
+    hipLaunchKernelGGL((pf_kernel<1024, true>), dim3(m), dim3(1024), 0, e->s_pf, a);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->ev_p1, e->s_pf));
+  HIP_TRY(hipStreamSynchronize(e->s_pf));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->ev_p0, e->ev_p1));
+  e->timing_access += ms;
+  std::vector<int> order(m);
+  for (int b = 0; b < m; b++) order[b] = (g0 + b) / M;
+  return fold_status(e, m, false, true, order.data(), 0, "unexpected status of the masked partition function");
+}
+
+extern "C" int drna_pf_unpaired_batch(drna_engine* e, int R, int L, const char* seqs, int M, const unsigned char* nopair, double* F) {
+  if (!e) return DRNA_ERR_ARG;
+  // (no upper limit on R or M: the R M folds go through the workspace slots in chunks)
+  { const int rc = aux_check(e, "drna_pf_unpaired_batch", std::min(R, e->max_R), L, nullptr, M >= 1 && (long long)R * M <= 0x7fffffffll && seqs && nopair && F,
+                             "M >= 1, R M < 2^31; seqs, nopair and F required"); if (rc != DRNA_OK) return rc; }
+  HIP_TRY(hipSetDevice(e->device));
+  const bool lds = e->access_lds && L <= (e->access_lds_force ? ACCESS_LDS_MAX : ACCESS_LDS_HOST_MAX);
+  if (lds) { const int rc = mapped_F4(e); if (rc != DRNA_OK) return rc; }
+  const size_t mb = (size_t)M * L;
+  if (mb > e->nopair_cap) {
+    if (e->d_nopair) (void)hipFree(e->d_nopair);
+    e->d_nopair = nullptr; e->nopair_cap = 0;
+    HIP_TRY(hipMalloc((void**)&e->d_nopair, mb));
+    e->nopair_cap = mb;
+  }
+  HIP_TRY(hipMemcpy(e->d_nopair, nopair, mb, hipMemcpyHostToDevice));
+  e->timing_access = 0.f;
+  // the LDS kernel needs no workspace slot: its chunks are bounded by the status words and the staging buffers alone
+  const long long total = (long long)R * M, step = lds ? e->max_R : e->ws_slots;
+  for (long long g0 = 0; g0 < total; g0 += step) {
+    const int m = (int)std::min(step, total - g0);
+    const int s0 = (int)(g0 / M), s1 = (int)((g0 + m - 1) / M);          // the chunk's sequences: at most m of them
+    std::memcpy(e->hm_seqs, seqs + (size_t)s0 * L, (size_t)(s1 - s0 + 1) * L);
+    const int rc = access_mapped(e, m, L, M, (int)g0, s0, lds);
+    if (rc != DRNA_OK) return rc;
+    for (int b = 0; b < m; b++) F[g0 + b] = lds ? e->hm_F4[4 * (size_t)b] : e->hm_Epf[b];
+  }
+  return DRNA_OK;
+}
+
+extern "C" int drna_last_access_timing(const drna_engine* e, float* ms) {
+  if (!e || !ms) return DRNA_ERR_ARG;
+  *ms = e->timing_access;
   return DRNA_OK;
 }
 

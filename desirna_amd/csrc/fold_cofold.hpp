@@ -566,8 +566,10 @@ __device__ __forceinline__ void co_pf_finish(const SM& sm, const CoArgs& A, cons
 }
 
 // partition function of pair r by the calling workgroup; QB, QM, QM1 (doubles) and INFO (bytes) live where the caller put them
-// (workspace slot or LDS), their cells where the layout says; sm holds the members of CoPfSmemCore
-template <int NT, class SM, class LAY>
+// (workspace slot or LDS), their cells where the layout says; sm holds the members of CoPfSmemCore.
+// MASKED (fold_access.hpp): pairability alone reads the pairing codes sm.Sp (4 = must stay unpaired), which the layout's load()
+// has written beside the letters; every energy look-up keeps reading sm.S.
+template <int NT, bool MASKED = false, class SM, class LAY>
 __device__ __forceinline__ void cofold_pf_body(SM& sm, const CoArgs& A, int r, double* QB, double* QM, double* QM1, unsigned char* INFO,
                                                const LAY lay) {
   const PfTables& T = *A.F;
@@ -599,7 +601,9 @@ __device__ __forceinline__ void cofold_pf_body(SM& sm, const CoArgs& A, int r, d
     for (int i = wave + 1; i <= ncell; i += NT / WAVE) {
       const int j = i + d;
       const bool same = co_same(i, j, cut);
-      const int t = (d > TURN || !same) ? pair_type(sm.S[i], sm.S[j]) : 0;
+      int t;
+      if constexpr (MASKED) t = (d > TURN || !same) ? pair_type(sm.Sp[i], sm.Sp[j]) : 0;
+      else t = (d > TURN || !same) ? pair_type(sm.S[i], sm.S[j]) : 0;
       const double tau = t > 2 ? T.TermAU : 1.0;
       const bool adj_i = co_same(i, i + 1, cut), adj_j = co_same(j - 1, j, cut);
       double qb = 0.0;

@@ -11,6 +11,8 @@
 //     carried by the O(1) recurrence U[i,j] = b (qm1[i+1,j] + U[i+1,j]);
 //   * partial sums of a cell are combined in a fixed order, so results are bit-reproducible.
 #pragma once
+#include <type_traits>
+
 #include "fold_common.hpp"
 
 namespace drna {
@@ -59,6 +61,20 @@ struct PfSmem {
   f64x2 plan_pW[NPAIR_MAX];
 };
 
+// The masked instance pf_kernel<NT, true> (drna_pf_unpaired_batch): workgroup b folds the (sequence, mask) pair g = fold0 + b --
+// sequence g / M (its letters at seqs + (g / M - seq0) L) under mask g % M -- with its tables in workspace slot b and its results
+// at Epf[b] / status[b].  A masked position keeps its letter for every energy look-up (mismatches, dangles, the special hairpins,
+// the small-loop tables read S) and cannot pair: only build_plist and the pair_type look-ups read the pairing codes Sp (4 = masked).
+struct PfMaskArgs : PfArgs {
+  const unsigned char* nopair = nullptr;   // M x L bytes, non-zero = the position stays unpaired
+  int M = 1;
+  int fold0 = 0;
+  int seq0 = 0;
+};
+struct PfMaskSmem : PfSmem {
+  unsigned char Sp[MAXN + 4];
+};
+
 template <class SM>
 __device__ __forceinline__ double pf_hairpin(const SM& sm, const PfArgs& A, int i, int j, int t) {
   const PfTables& T = *A.T;
@@ -95,9 +111,9 @@ __device__ __forceinline__ double pf_endstem(const double* mm, const PfSmem& sm,
   return 1.0;
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT) void pf_kernel(PfArgs A) {
-  __shared__ PfSmem sm;
+template <int NT, bool MASKED = false>
+__global__ __launch_bounds__(NT) void pf_kernel(std::conditional_t<MASKED, PfMaskArgs, PfArgs> A) {
+  __shared__ std::conditional_t<MASKED, PfMaskSmem, PfSmem> sm;
   constexpr int NW = NT / WAVE;
   const PfTables& T = *A.T;
   const Plan& P = *A.plan;
@@ -134,14 +150,22 @@ __global__ __launch_bounds__(NT) void pf_kernel(PfArgs A) {
     QM1[3 * ld + k] = 0.0; UQ[3 * ld + k] = 0.0;
     DQ[2 * ld + k] = 0.0; DQ[3 * ld + k] = 0.0;
   }
-  load_sequence<NT>(sm, A.seqs + A.rg.off_of(r, n), n, tid);
+  if constexpr (MASKED) load_sequence<NT>(sm, A.seqs + (long long)((A.fold0 + r) / A.M - A.seq0) * n, n, tid);
+  else load_sequence<NT>(sm, A.seqs + A.rg.off_of(r, n), n, tid);
   if (sm.flag) {
     if (tid == 0) { A.status[r] = ST_BAD_CHAR; A.Epf[r] = 0.0; }
     return;
   }
+  const unsigned char* codes = sm.S;      // pairing codes: the letters, or Sp of the masked instance
+  if constexpr (MASKED) {
+    const unsigned char* mask = A.nopair + (long long)((A.fold0 + r) % A.M) * n;
+    for (int k = tid; k <= n + 1; k += NT) sm.Sp[k] = k >= 1 && k <= n && !mask[k - 1] ? sm.S[k] : 4;
+    codes = sm.Sp;
+    __syncthreads();
+  }
   const double b1 = A.eMLb[1];
   const double sc2 = A.scale[2];
-  if (wave == 0 && TURN + 1 < n) build_plist(sm, sm.S, TURN + 1, n, lane);
+  if (wave == 0 && TURN + 1 < n) build_plist(sm, codes, TURN + 1, n, lane);
   __syncthreads();
   // QM and QM1 (adjacent tables) through one buffer descriptor
   const auto rsQ = __builtin_amdgcn_make_buffer_rsrc((void*)QM, (short)0, (int)(2 * tab * 8), 0x00020000);
@@ -166,7 +190,7 @@ __global__ __launch_bounds__(NT) void pf_kernel(PfArgs A) {
         const bool act = q < pc;
         const int i = sm.plist[par][act ? q : pc - 1];
         const int j = i + d;
-        const int t = pair_type(sm.S[i], sm.S[j]);
+        const int t = pair_type(codes[i], codes[j]);
         const int si1 = sm.S[i + 1], sj1 = sm.S[j - 1];
         const int ij = t * 16 + si1 * 4 + sj1;
         double accI = 0.0;
@@ -281,7 +305,7 @@ __global__ __launch_bounds__(NT) void pf_kernel(PfArgs A) {
       double aI = 0.0, aK = 0.0;
       for (int h = 0; h < H; h++) aK += sm.partK[(b * H + h) * WAVE + ln];
       const int j = i + d;
-      const int t = pair_type(sm.S[i], sm.S[j]);
+      const int t = pair_type(codes[i], codes[j]);
       if (t) {
         const int pos = sm.cpos[par][i];
         for (int h = 0; h < HI; h++) aI += sm.partI[((pos >> 6) * HI + h) * WAVE + (pos & 63)];
@@ -308,7 +332,7 @@ __global__ __launch_bounds__(NT) void pf_kernel(PfArgs A) {
       DQ[at] = aK;
       QM[at] = m1 + aK + U;
     }
-    if (wave == NW - 1 && d + 1 < n) build_plist(sm, sm.S, d + 1, n, lane);     // list of the next diagonal
+    if (wave == NW - 1 && d + 1 < n) build_plist(sm, codes, d + 1, n, lane);    // list of the next diagonal
     __syncthreads();
   }
 

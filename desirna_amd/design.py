@@ -36,6 +36,10 @@ a candidate adds its value to the score, last of all additions.  ``run_design`` 
 expressions (``energy_scores.score_motifs``); ``run_design_fast`` and ``run_puzzle_batch`` with the native matcher
 (``HostKernels.motif_score`` per iteration, or the engine's motif set -- ``Engine.set_motifs`` -- inside every native loop).
 
+Accessible regions (an input block ``>accessible``, one strand): ``accessible_weight`` x the opening energy of the region
+(``Engine.unpaired_free_energy``) comes after the motif term, in ``run_design`` and in ``run_design_fast``'s per-iteration loop
+(no native loop, no lock-step batch yet); ``--accessibility W`` profiles every window of the reported sequences.
+
 Two strands (hetero-dimer, ``-d on`` homodimer) run through both drivers; together with alternative structures through
 ``run_design`` only.
 
@@ -64,8 +68,24 @@ CAN_PAIR = {'A': ['U'], 'U': ['G', 'A'], 'G': ['U', 'C'], 'C': ['G']}
 WC = {'A': 'U', 'U': 'A', 'G': 'C', 'C': 'G'}
 
 
+def parse_accessible(line, sec_struct):
+    """the ``>accessible`` line of an input: as long as sec_struct, ``x`` = a position of the region that should be free (unpaired
+    in the ensemble, not only in the MFE structure), ``.`` = the rest.  Returns the line; ValueError names what is wrong with it"""
+    if "&" in sec_struct:
+        raise ValueError("accessible: a two-strand input has no accessible region yet (one strand only)")
+    bad = sorted(set(line) - set("x."))
+    if bad:
+        raise ValueError("accessible: character %r (the line holds 'x' for the region and '.' for the rest)" % bad[0])
+    if len(line) != len(sec_struct):
+        raise ValueError("accessible: %d characters for a structure of %d. Check input file." % (len(line), len(sec_struct)))
+    if "x" not in line:
+        raise ValueError("accessible: no 'x' in the line, the region is empty")
+    return line
+
+
 def read_input(path):
-    """``>key`` block format of the reference (name, seq_restr, sec_struct, optional seed_seq / alt_sec_struct)."""
+    """``>key`` block format of the reference (name, seq_restr, sec_struct, optional seed_seq / alt_sec_struct), and the optional
+    block ``>accessible`` (:func:`parse_accessible`): inp.accessible is its line, or None"""
     with open(path, encoding='utf-8') as fh:
         text = fh.read()
     data = {}
@@ -73,12 +93,15 @@ def read_input(path):
         lines = block.split("\n")
         data[lines[0]] = lines[1:]
     inp = SimpleNamespace(name=data['name'][0], sec_struct=data['sec_struct'][0].strip(),
-                          seq_restr=data['seq_restr'][0].strip(), seed_seq=None, alt_sec_struct=None, alt_sec_structs=None)
+                          seq_restr=data['seq_restr'][0].strip(), seed_seq=None, alt_sec_struct=None, alt_sec_structs=None,
+                          accessible=None)
     if 'seed_seq' in data:
         inp.seed_seq = data['seed_seq'][0].strip()
     if 'alt_sec_struct' in data:
         inp.alt_sec_structs = [x.strip() for x in data['alt_sec_struct']]
         inp.alt_sec_struct = inp.alt_sec_structs[0]
+    if 'accessible' in data:
+        inp.accessible = parse_accessible(data['accessible'][0].strip() if data['accessible'] else "", inp.sec_struct)
     return inp
 
 
@@ -316,15 +339,22 @@ def oligo_state_and_pks(sec_struct, dimer="off", oligo="off"):
 # drivers differ in their inner iterations and in how they hold the replica state only.
 
 def _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results, shards,
-           dimer="off", oligo="off", subopt="off", acgu=None, keep_records=True, motifs=None):
+           dimer="off", oligo="off", subopt="off", acgu=None, keep_records=True, motifs=None, accessible_weight=1.0):
     """The run: problem, options, shards, temperature ladder, main stream and initial sequence (the same on every rank).
-    `motifs`: the ``-motifs`` text or what ``energy_scores.parse_motifs`` makes of it; opts.motifs holds the latter, or None"""
+    `motifs`: the ``-motifs`` text or what ``energy_scores.parse_motifs`` makes of it; opts.motifs holds the latter, or None.
+    opts.accessible: the input's ``>accessible`` region as a uint8 mask (None without the block), opts.accessible_weight its weight"""
     if isinstance(motifs, str):
         motifs = es.parse_motifs(motifs)
+    region = getattr(input_file, "accessible", None)
+    if region is not None:
+        region = _engine_mask(parse_accessible(region, input_file.sec_struct))
+        if not accessible_weight > 0:
+            raise ValueError("accessible_weight must be > 0")
     prob = DesignProblem(input_file.sec_struct, input_file.seq_restr, input_file.alt_sec_structs, acgu=acgu)
     oligo_state, pks = oligo_state_and_pks(input_file.sec_struct, dimer, oligo)
     opts = SimpleNamespace(oligo_state=oligo_state, pks=pks, subopt=subopt, motifs=motifs or None, param="1999",
-                           scoring_f=es.parse_scoring_functions(scoring_f))
+                           scoring_f=es.parse_scoring_functions(scoring_f), accessible=region,
+                           accessible_weight=float(accessible_weight))
     shards = shards or rx.ReplicaShards(replicas, 0, 1)
     run = SimpleNamespace(prob=prob, opts=opts, shards=shards, local=shards.local, steps=steps, timelimit=timelimit,
                           stop_when_solved=stop_when_solved, num_results=num_results, keep_records=keep_records, step=0)
@@ -335,6 +365,11 @@ def _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed
     # input_file.seed_seq is read but ignored, as in the reference
     run.init = prob.initial_sequence(run.main_rng)
     return run
+
+
+def _engine_mask(line):
+    """an ``x`` / ``.`` line -> (1, n) uint8 mask of ``Engine.unpaired_free_energy``"""
+    return np.array([[c == "x" for c in line]], dtype=np.uint8)
 
 
 def _start(run, scores, solved, records):
@@ -386,7 +421,7 @@ def _finish(run, best):
 def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
                device=0, shards=None, scorer=None, progress=None, dimer="off", oligo="off", acgu=None, subopt="off",
-               num_results=None, motifs=None):
+               num_results=None, motifs=None, accessible_weight=1.0):
     """Replica-exchange Monte-Carlo design of one target.  Returns dict(best=ScoreSeq, solved=bool, history=..., stats=...).
 
     ``shards`` (a ``replica_exchange.ReplicaShards``) splits the replicas over ranks; every rank proposes and scores its
@@ -400,9 +435,13 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
     first solved replica (an extension used by the tests and by the puzzle-set driver).
 
     ``motifs`` (``-motifs``: the text ``"KEY,VALUE,..."`` or ``energy_scores.parse_motifs`` of it): the scorer adds the motif
-    term to every candidate (``ReplicaScorer.score``).  A ``scorer`` handed in scores with its own ``sim_options``."""
+    term to every candidate (``ReplicaScorer.score``).  A ``scorer`` handed in scores with its own ``sim_options``.
+
+    An input with an ``>accessible`` region (one strand): every candidate's opening energy of the region,
+    ``Eopen = F[region unpaired] - Epf`` (``Engine.unpaired_free_energy``, one call per batch), times ``accessible_weight`` is the
+    last addition to its score, after the motif term; records carry ``opening_energy`` and ``p_unpaired``."""
     run = _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results,
-                 shards, dimer, oligo, subopt, acgu, motifs=motifs)
+                 shards, dimer, oligo, subopt, acgu, motifs=motifs, accessible_weight=accessible_weight)
     prob, local = run.prob, run.local
     scorer = scorer or es.ReplicaScorer(input_file, run.opts, max_replicas=max(1, len(local)), device=device)
     cur = scorer.score([run.init] * len(local)) if local else []
@@ -452,18 +491,19 @@ def run_design(input_file, replicas=10, exchange=100, steps=None, timelimit=60, 
 # ---- what run_design_fast and run_puzzle_batch share: one puzzle's replica state in arrays, and what an inner iteration or a
 # native call does to it.
 
-def _array_state(run, b, exchange, two=False, oa=False, nd=False):
+def _array_state(run, b, exchange, two=False, oa=False, nd=False, region=False):
     """The replica state of one run: the arrays of the scored batch `b` (``energy_scores.score_arrays`` of the initial
     sequence) that ``Engine.mc_run*`` holds, under its names; the best state; the records.  Calls ``_start``."""
     Rl, local = len(run.local), np.array(run.local, dtype=np.int64)
-    keys = ["seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"] + ["oligo_fraction", "bonus"] * (two or oa) + ["subopt_e"] * nd
+    keys = (["seqs", "mfe_ss", "score", "mcc1", "Epf", "Ed"] + ["oligo_fraction", "bonus"] * (two or oa) + ["subopt_e"] * nd
+            + ["opening_energy", "p_unpaired"] * region)
     cur = SimpleNamespace(**{k: np.array(getattr(b, k), dtype=np.uint8 if k in keys[:2] else np.float64) for k in keys})
     bonus_name = "monomer_bonus" if oa else "oligomer_bonus"
     if oa:
         cur.bonus_field = bonus_name                      # (energy_scores.record names the bonus of its records by it)
     # fields of `best`; after the strings, in the order of mc_run's best["vals"] (esubopt_minus_Epf follows from them)
     fields = (["sequence", "mfe_ss", "mcc", "scoring_function", "Epf", "edesired"] + ["oligo_fraction", bonus_name] * (two or oa)
-              + ["subopt_e", "esubopt_minus_Epf"] * nd)
+              + ["subopt_e", "esubopt_minus_Epf"] * nd + ["opening_energy", "p_unpaired"] * region)
     st = SimpleNamespace(keys=keys, cur=cur, nd=nd, Rl=Rl, local=local, vals=[f for f in fields[2:] if f != "esubopt_minus_Epf"])
 
     def best_of(k):
@@ -542,7 +582,7 @@ def _array_result(run, st, eng, native_loop):
 def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit=60, t_min=10.0, t_max=150.0,
                     scoring_f="Ed-Epf:1.0", tm_max=0.7, tm_min=0.0, point_mutations="on", seed=0, stop_when_solved=False,
                     device=0, engine=None, keep_records=True, native_loop=None, shards=None, num_results=None, dimer="off",
-                    negative_design="off", oligo="off", motifs=None):
+                    negative_design="off", oligo="off", motifs=None, accessible_weight=1.0):
     """Same loop as :func:`run_design` with the per-replica host work in native code and no per-step Python objects:
     proposals, SimScore and Metropolis run batched in the C library, the replica state lives in numpy arrays (the batch of
     ``energy_scores.score_arrays``, of which it keeps what ``Engine.mc_run`` holds).  The
@@ -573,7 +613,12 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
     ``utils/energy_scores.py:121-123``): the motif term of every candidate's string (two strands: with its ``&``) is the last
     addition to its score, from ``HostKernels.motif_score`` per iteration or inside the native loop, which takes the set from
     the engine: the run sets it (``Engine.set_motifs``) before its first native call -- to the empty set when it has none, so
-    that an engine handed in does not carry an earlier run's motifs into this one.  No column of its own in the records."""
+    that an engine handed in does not carry an earlier run's motifs into this one.  No column of its own in the records.
+
+    An input with an ``>accessible`` region (one strand; :func:`run_design` has the rule): ``accessible_weight`` x the opening energy
+    of the region is the last addition to every candidate's score, from one ``Engine.unpaired_free_energy`` call per iteration.
+    The native loops do not know the term, so a region turns ``native_loop`` off; records and ``best`` carry ``opening_energy`` and
+    ``p_unpaired``."""
     from . import engine as _engine
     if stop_when_solved and num_results is not None and not keep_records:
         raise ValueError("the -sws rule with num_results ranks the recorded sequences: it needs keep_records=True "
@@ -584,19 +629,25 @@ def run_design_fast(input_file, replicas=10, exchange=100, steps=None, timelimit
                                   "proposer has no snake moves)")
     es.check_scoring_functions(es.parse_scoring_functions(scoring_f))
     run = _setup(input_file, replicas, steps, timelimit, t_min, t_max, scoring_f, seed, stop_when_solved, num_results,
-                 shards, dimer, oligo, keep_records=keep_records, motifs=motifs)
+                 shards, dimer, oligo, keep_records=keep_records, motifs=motifs, accessible_weight=accessible_weight)
     prob, sf, oligo_state, nd = run.prob, run.opts.scoring_f, run.opts.oligo_state, negative_design == "on"
+    region = run.opts.accessible
     oa = oligo_state == "avoid"
     R, L, Rl = replicas, prob.n, len(run.local)
     eng = engine or _engine.Engine(max_R=max(1, Rl), max_L=L - 1 if two else L, device=device)      # L counts the '&'
     hk = _engine.HostKernels()
     eng.set_targets([input_file.sec_struct.replace("&", "")] + list(input_file.alt_sec_structs or []))
     score = lambda seqs_u8: es.score_arrays(eng, hk, input_file.sec_struct, sf, seqs_u8, oligo_state, run.opts.pks, nd, self_dimer=oa,
-                                            motifs=run.opts.motifs)
-    st = _array_state(run, score(np.tile(np.frombuffer(run.init.encode(), dtype=np.uint8), (max(1, Rl), 1))), exchange, two, oa, nd)
+                                            motifs=run.opts.motifs,
+                                            **(dict(accessible=region, accessible_weight=run.opts.accessible_weight)
+                                               if region is not None else {}))
+    st = _array_state(run, score(np.tile(np.frombuffer(run.init.encode(), dtype=np.uint8), (max(1, Rl), 1))), exchange, two, oa, nd,
+                      region is not None)
     cur = st.cur
     if native_loop is None:
         native_loop = True
+    if region is not None:
+        native_loop = False                               # drna_mc_run* has no opening-energy step
     native_loop = native_loop and all(name in eng.TERM_IDS for name, _ in sf)   # (every -sf term, Edef included, has a native id)
     if native_loop and Rl:
         eng.set_motifs(run.opts.motifs)                   # this run's set or none: the engine may come from another run
@@ -649,8 +700,9 @@ class _RaggedSlice:
 
 def batch_eligible(input_file, scoring_f="Ed-Epf:1.0", negative_design="off", oligo="off", subopt="off", acgu=None, **_):
     """Can this input run in :func:`run_puzzle_batch` under these driver keywords?  One strand, the brackets ``( ) .`` only, no
-    alternative structures; -nd, -oa and -acgu off; no Edef term."""
+    alternative structures, no ``>accessible`` region; -nd, -oa and -acgu off; no Edef term."""
     return (set(input_file.sec_struct) <= set("().") and not input_file.alt_sec_structs and negative_design == "off"
+            and getattr(input_file, "accessible", None) is None
             and oligo == "off" and subopt == "off" and acgu is None
             and all(name != "Edef" for name, _ in es.parse_scoring_functions(scoring_f)))
 
@@ -689,10 +741,11 @@ def run_puzzle_batch(inputs, replicas=10, exchange=100, steps=None, timelimit=60
     from . import engine as _engine
     if stop_when_solved and num_results is not None and not keep_records:
         raise ValueError("the -sws rule with num_results ranks the recorded sequences: it needs keep_records=True")
-    bad = [i.name for i in inputs if not (set(i.sec_struct) <= set("().") and not i.alt_sec_structs and oligo == "off")]
+    bad = [i.name for i in inputs if not (set(i.sec_struct) <= set("().") and not i.alt_sec_structs and oligo == "off"
+                                          and getattr(i, "accessible", None) is None)]
     if bad:
         raise ValueError("not a puzzle for the lock-step batch (still refused: two strands, brackets other than ( ) ., "
-                         "alternative structures, -oa on): %s" % ", ".join(bad))
+                         "alternative structures, an >accessible region, -oa on): %s" % ", ".join(bad))
     if not inputs:
         return []
     es.check_scoring_functions(es.parse_scoring_functions(scoring_f))
@@ -820,6 +873,8 @@ def _cli_driver(a, inp):
         if sum(vals) != 100:
             raise SystemExit("The ACGU content should sum up to 100, check your command.")
         extra["acgu"] = dict(zip("ACGU", vals))
+    if getattr(inp, "accessible", None) is not None:          # (only with the block: without it the drivers' keywords are as before)
+        extra["accessible_weight"] = a.accessible_weight
     return (run_design if python_host else run_design_fast), extra
 
 
@@ -865,6 +920,42 @@ def ensemble_report(engine, result, input_file, S, top=5, seed=0):
         rows.append(row("target", "", target, cnt.get(target, 0), "" if e_t is None else float(e_t), float(mcc[-1])))
         rest = S - sum(cnt[s] for s in set(first) | {target})
         rows.append(row("other", "", "", rest, "", ""))
+    return rows
+
+
+def accessibility_report(engine, result, input_file, W):
+    """How available every stretch of each reported sequence is: the opening energy ``Eopen = F[window unpaired] - Epf`` (kcal/mol)
+    and ``p_unpaired = exp(-Eopen / kT)`` of every window of W nucleotides, start a = 1 .. n - W + 1 (1-based, ``end`` = a + W - 1
+    inclusive), from ONE ``engine.unpaired_free_energy`` call per chunk of sequences with all n - W + 1 windows as its masks; Epf
+    from the same chunk's score batch.  With an ``>accessible`` region in the input, its mask rides along as one more and gives the
+    first row of each sequence (kind ``region``, start / end = its first / last ``x``).  The reported sequences are chosen as in
+    :func:`ensemble_report`.  One strand.  Returns the rows of ``<name>_accessibility.csv`` (``outputs.ACCESSIBILITY_COLUMNS``)."""
+    from . import engine as _engine
+    from . import outputs
+    if "&" in input_file.sec_struct:
+        raise ValueError("the accessibility profile takes one strand")
+    n, W = len(input_file.sec_struct), int(W)
+    if not 1 <= W <= n:
+        raise ValueError("window of %d nucleotides on a sequence of %d" % (W, n))
+    seqs = list(result.get("reported") or [r["sequence"] for r in outputs.sort_and_filter(result["simulation_data"])])
+    region = getattr(input_file, "accessible", None)
+    masks = np.zeros((n - W + 1, n), dtype=np.uint8)
+    for a in range(n - W + 1):
+        masks[a, a:a + W] = 1
+    spans = [("window", a + 1, a + W) for a in range(n - W + 1)]
+    if region is not None:
+        masks = np.concatenate([_engine_mask(region), masks])
+        spans = [("region", region.index("x") + 1, region.rindex("x") + 1)] + spans
+    step = max(1, int(getattr(engine, "max_R", len(seqs)) or len(seqs)))
+    rows = []
+    for r0 in range(0, len(seqs), step):           # (the scoring entry points take max_R sequences at a time)
+        part = seqs[r0:r0 + step]
+        Epf = engine.score_batch(part, _engine.NEED_PF)["Epf"]
+        Eopen, p = engine.opening_energy(part, masks, Epf)
+        for r, seq in enumerate(part):
+            for m, (kind, start, end) in enumerate(spans):
+                rows.append(dict(sequence=seq, kind=kind, start=start, end=end, opening_energy=float(Eopen[r, m]),
+                                 p_unpaired=float(p[r, m])))
     return rows
 
 
@@ -941,6 +1032,11 @@ def _cli_report(a, filename, inp, res):
             eng = res.get("engine") or _engine.Engine(max_R=max(1, len(ranked)), max_L=len(inp.sec_struct))
             rows = structure_report(eng, dict(res, reported=[r["sequence"] for r in ranked]), inp, a.structures)
             outputs.write_structures(rows, outname, a.outdir)
+        if a.accessibility:
+            from . import engine as _engine
+            eng = res.get("engine") or _engine.Engine(max_R=max(1, len(ranked)), max_L=len(inp.sec_struct))
+            rows = accessibility_report(eng, dict(res, reported=[r["sequence"] for r in ranked]), inp, a.accessibility)
+            outputs.write_accessibility(rows, outname, a.outdir)
     b = res["best"]
     print("Design solved succesfully!" if res["solved"] else "Design not solved.")
     print(b.sequence)
@@ -986,7 +1082,18 @@ def main(argv=None):
     ap.add_argument("--structures", type=float, default=None, metavar="GAMMA", help="after the run, write the MFE, centroid and "
                     "maximum-expected-accuracy structure (weight GAMMA > 0) of every reported sequence into <name>_structures.csv "
                     "beside _results.csv (needs -o; one or two strands)")
+    ap.add_argument("--accessible-weight", type=float, default=1.0, metavar="W", dest="accessible_weight", help="weight (> 0) of the "
+                    "opening energy of an input's >accessible region in its scoring function")
+    ap.add_argument("--accessibility", type=int, default=None, metavar="W", help="after the run, write the opening energy and the "
+                    "probability of being unpaired of every window of W nucleotides (W >= 1) of every reported sequence into "
+                    "<name>_accessibility.csv beside _results.csv (needs -o; one strand)")
     a = ap.parse_args(argv)
+    if not a.accessible_weight > 0:
+        ap.error("--accessible-weight takes a weight W > 0")
+    if a.accessibility is not None and a.accessibility < 1:
+        ap.error("--accessibility takes a window of W >= 1 nucleotides")
+    if a.accessibility and not a.outdir:
+        ap.error("--accessibility writes its file beside _results.csv: give -o")
     if a.structures is not None and not (a.structures > 0 and a.structures < float("inf")):
         ap.error("--structures takes a weight GAMMA > 0")
     if a.structures and not a.outdir:
@@ -1007,6 +1114,8 @@ def main(argv=None):
         inputs = [read_input(f) for f in a.set_files]
         if a.ensemble and any("&" in i.sec_struct for i in inputs):
             ap.error("--ensemble samples one strand: a two-strand input is refused")
+        if a.accessibility and any("&" in i.sec_struct for i in inputs):
+            ap.error("--accessibility profiles one strand: a two-strand input is refused")
         # the switches under run_design_fast's names, so that run_puzzle_set can tell which inputs may share the batch; the
         # per-puzzle driver gets each input's own keywords (_cli_driver)
         switches = dict(negative_design=a.subopt, oligo=a.oligo, **(dict(acgu=True) if a.percs == "on" or a.python_host else {}))
@@ -1021,6 +1130,8 @@ def main(argv=None):
     inp = read_input(a.name)
     if a.ensemble and "&" in inp.sec_struct:
         ap.error("--ensemble samples one strand: a two-strand input is refused")
+    if a.accessibility and "&" in inp.sec_struct:
+        ap.error("--accessibility profiles one strand: a two-strand input is refused")
     drv, extra = _cli_driver(a, inp)
     _cli_report(a, a.name, inp, drv(inp, **extra, **common))
 

@@ -201,7 +201,17 @@ def score_motifs(seq, sim_options):
     return motif_score
 
 
-def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pks="off", nd=False, self_dimer=False, motifs=None):
+def opening_term(eng, seqs, Epf, accessible):
+    """(opening_energy, p_unpaired), float64[R]: what it costs every sequence's ensemble to keep the region `accessible` (one
+    mask of ``Engine.unpaired_free_energy``: an ``x`` / ``.`` line or a (1, L) array) unpaired, Eopen = F[region unpaired] - Epf
+    with the batch's own Epf, and exp(-Eopen / kT), the probability that the whole region is free.  ONE engine call, M = 1"""
+    F = eng.unpaired_free_energy(seqs, accessible)
+    Eopen = F[:, 0] - np.asarray(Epf, dtype=np.float64)
+    return Eopen, np.exp(-Eopen / (KB * TEMP))
+
+
+def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pks="off", nd=False, self_dimer=False, motifs=None,
+                 accessible=None, accessible_weight=1.0):
     """THE scorer (reference score_sequence(), :70-118, for a whole batch): `eng` an ``engine.Engine`` whose targets are
     sec_struct (+ the alternative structures) without the '&', `hk` an ``engine.HostKernels``, seqs_u8 the (R, L) uint8 candidates
     (two strands -- oligo_state heterodimer / homodimer --: with the '&' column).  Returns the batch as arrays, named like the
@@ -217,6 +227,11 @@ def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pk
     candidate's string (two strands: with the '&'), the last addition of all (reference :121-123).  Off by default:
     ``ReplicaScorer.score`` adds that term itself, too.
 
+    `accessible` (opt-in, one strand; the ``>accessible`` region of the input as a mask of ``Engine.unpaired_free_energy``):
+    :func:`opening_term` of every candidate from one engine call; `accessible_weight` x opening_energy is the last addition of
+    all, after the motif term, and the batch carries opening_energy and p_unpaired.  Off by default, and
+    ``ReplicaScorer.score`` adds that term itself, after its own motif term.
+
     The reference's order of additions: the -sf sum; + (Ed2 - Epf) with alternative structures, every energy / 100 first, then
     the sum, then / count (one strand only, as the two-strand scorer always had it); - (subopt_e - Epf) on the candidates with
     1 - MCC == 0 (`nd`: ONE second-best call for that subset); + the oligomer bonus (hetero-dimer, or homodimer with two different
@@ -227,6 +242,8 @@ def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pk
     R, L = seqs_u8.shape
     strings = lambda rows: [bytes(seqs_u8[k]).decode() for k in rows]
     b = SimpleNamespace(seqs=seqs_u8, n=L, sln_Epf=None, Emfe=None, Edef=None, Ed2=None, subopt_e=None, oligo_fraction=None, bonus=None)
+    if accessible is not None and two:
+        raise ValueError("an accessible region takes one strand")
     ref = sec_struct.replace("&", "Ee")
     if two:
         seqs = strings(range(R))
@@ -274,6 +291,9 @@ def score_arrays(eng, hk, sec_struct, scoring_f, seqs_u8, oligo_state="none", pk
         b.score = b.score + b.bonus
     if motifs:                                            # reference :121-123
         b.score = b.score + hk.motif_score(motifs, seqs_u8)
+    if accessible is not None:
+        b.opening_energy, b.p_unpaired = opening_term(eng, strings(range(R)), b.Epf, accessible)
+        b.score = b.score + accessible_weight * b.opening_energy
     return b
 
 
@@ -306,6 +326,8 @@ def record(b, k):
     if col("oligo_fraction") is not None:
         sc.oligo_fraction = col("oligo_fraction")
         setattr(sc, getattr(b, "bonus_field", "oligomer_bonus"), col("bonus"))     # (-oa on: monomer_bonus, as ReplicaScorer.score names it)
+    if col("opening_energy") is not None:
+        sc.opening_energy, sc.p_unpaired = col("opening_energy"), col("p_unpaired")
     return sc
 
 
@@ -355,6 +377,15 @@ class ReplicaScorer:
         if getattr(self.sim_options, "motifs", None):
             for seq, sc in zip(seqs, res):
                 sc.update_scoring_function_w_motifs(score_motifs(seq, self.sim_options))
+        region = getattr(self.sim_options, "accessible", None)
+        if region is not None:                                # the last addition of all
+            if self.oligo_state in ("heterodimer", "homodimer"):
+                raise ValueError("an accessible region takes one strand")
+            Eopen, p = opening_term(self.engine, seqs, b.Epf, region)
+            w = getattr(self.sim_options, "accessible_weight", 1.0)
+            for k, sc in enumerate(res):
+                sc.opening_energy, sc.p_unpaired = float(Eopen[k]), float(p[k])
+                sc.scoring_function = sc.scoring_function + w * sc.opening_energy
         return res
 
 

@@ -80,6 +80,8 @@ _SIGNATURES = {
     "drna_mea_structures_batch": (_ci, [_vp, _ci, _ci, _str, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
     "drna_cofold_mea_structures_batch": (_ci, [_vp, _ci, _ci, _ci, _str, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
     "drna_last_mea_timing": (_ci, [_vp, _vp]),
+    "drna_pf_unpaired_batch": (_ci, [_vp, _ci, _ci, _str, _ci, _vp, _vp]),
+    "drna_last_access_timing": (_ci, [_vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -165,6 +167,28 @@ def _split_pairs(seqs):
             raise ValueError("all pairs of a batch must have the same strand lengths")
         flat.append(a + b)
     return "".join(flat).encode("ascii"), len(flat), L, cut
+
+
+KT = 0.001987204259 * (273.15 + 37)      # kcal/mol: the kT of energy_scores.kTlog_* (boltzmann constant x the model's 37 degC)
+
+
+def mask_array(masks, L):
+    """masks of :meth:`Engine.unpaired_free_energy` -> (M, L) uint8, 1 = the position stays unpaired.  `masks`: an (M, L) (or one
+    (L,)) uint8 / bool array, one string or a list of strings over 'x' (stays unpaired) and '.'"""
+    if isinstance(masks, str):
+        masks = [masks]
+    if len(masks) and isinstance(masks[0], str):
+        for m in masks:
+            bad = set(m) - set("x.")
+            if bad:
+                raise ValueError("mask %r: character %r (a mask holds 'x' and '.' only)" % (m, sorted(bad)[0]))
+            if len(m) != L:
+                raise ValueError("mask %r: %d characters for sequences of %d" % (m, len(m), L))
+        return np.array([[c == "x" for c in m] for m in masks], dtype=np.uint8).reshape(len(masks), L)
+    a = np.atleast_2d(np.asarray(masks))
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != L:
+        raise ValueError("masks must be (M, %d), M >= 1; got %r" % (L, a.shape))
+    return np.ascontiguousarray(a != 0, dtype=np.uint8)
 
 
 def _sample_seeds(seed, R):
@@ -469,6 +493,38 @@ class Engine:
         frac = np.zeros(R, dtype=np.float64)
         self._check(self._L.drna_self_dimer_batch(self._h, R, L, "".join(seqs).encode("ascii"), F4.ctypes.data, frac.ctypes.data))
         return {"FA": F4[:, 0], "FcAA": F4[:, 2], "FAA": F4[:, 3], "oligo_fraction": frac}
+
+    def unpaired_free_energy(self, seqs, masks):
+        """Free energy (kcal/mol) of every sequence's ensemble with the positions of each mask held unpaired
+        (drna_pf_unpaired_batch; RNAfold -p under the hard constraint 'x'): an (R, M) float64 array.  `masks` (see
+        :func:`mask_array`) are shared by all sequences; an all-zero mask gives the unconstrained Epf.  Any number of sequences
+        and masks."""
+        R, L = _equal_length(seqs)
+        m = mask_array(masks, L)
+        F = np.zeros((R, m.shape[0]), dtype=np.float64)
+        self._check(self._L.drna_pf_unpaired_batch(self._h, R, L, "".join(seqs).encode("ascii"), m.shape[0], m.ctypes.data, F.ctypes.data))
+        return F
+
+    def opening_energy(self, seqs, masks, Epf=None):
+        """(Eopen, p_unpaired), both (R, M): Eopen = F[mask] - Epf (kcal/mol, >= 0 up to rounding) is what it costs to free the
+        masked region, p_unpaired = exp(-Eopen / kT) the probability that all of it is unpaired.  `Epf` (R values): the
+        sequences' unconstrained ensemble free energies if the caller has them (score_batch's Epf), else they come from one extra
+        all-zero mask in the same call."""
+        R, L = _equal_length(seqs)
+        m = mask_array(masks, L)
+        if Epf is None:
+            F = self.unpaired_free_energy(seqs, np.concatenate([m, np.zeros((1, L), dtype=np.uint8)]))
+            F, F0 = F[:, :-1], F[:, -1]
+        else:
+            F, F0 = self.unpaired_free_energy(seqs, m), np.asarray(Epf, dtype=np.float64).reshape(R)
+        Eopen = F - F0[:, None]
+        return Eopen, np.exp(-Eopen / KT)
+
+    def last_access_timing(self):
+        """device ms of the last :meth:`unpaired_free_energy` call's launches, summed over its chunks (drna_last_access_timing)"""
+        t = C.c_float(0)
+        self._check(self._L.drna_last_access_timing(self._h, C.byref(t)))
+        return t.value
 
     def subopt_energy(self, seqs, want_both=False):
         """Energy (dcal/mol) of the second-best structure of each sequence as the reference's -nd on path takes it from

@@ -9,7 +9,8 @@ single-chain branch), ``sort_and_filter_simulation_data_alternative`` (:422-460,
 Not written: ``_replicas.csv`` (a pandas pivot), the PNG plot, ``_random.csv``.
 
 Beyond the reference: ``_ensemble.csv`` (``--ensemble``), the sampled Boltzmann ensemble of every reported sequence
-(``design.ensemble_report``).
+(``design.ensemble_report``); ``_structures.csv`` (``--structures``, ``design.structure_report``); ``_accessibility.csv``
+(``--accessibility``), the opening energy of every window of every reported sequence (``design.accessibility_report``).
 """
 import csv
 import io
@@ -236,4 +237,25 @@ def write_structures(rows, outname, directory="."):
     path = os.path.join(directory, outname + '_structures.csv')
     with open(path, 'w', newline='', encoding='utf-8') as fh:
         fh.write(structures_csv_text(rows))
+    return path
+
+
+ACCESSIBILITY_COLUMNS = ("sequence", "kind", "start", "end", "opening_energy", "p_unpaired")
+
+
+def accessibility_csv_text(rows):
+    """rows of design.accessibility_report: per sequence the input's own region (kind region, if it has one), then every window"""
+    buf = io.StringIO(newline='')
+    w = csv.DictWriter(buf, fieldnames=list(ACCESSIBILITY_COLUMNS))
+    w.writeheader()
+    for r in rows:
+        w.writerow(round_floats(dict(r)))
+    return buf.getvalue()
+
+
+def write_accessibility(rows, outname, directory="."):
+    import os
+    path = os.path.join(directory, outname + '_accessibility.csv')
+    with open(path, 'w', newline='', encoding='utf-8') as fh:
+        fh.write(accessibility_csv_text(rows))
     return path

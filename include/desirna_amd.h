@@ -294,6 +294,30 @@ int drna_cofold_mea_structures_batch(drna_engine *e, int R, int L, int cut, cons
                                      double *mea_val, char *cen_ss, double *cen_dist, int32_t *E, double *bpp);
 int drna_last_mea_timing(const drna_engine *e, float out[3]);
 
+/*
+ * Accessible regions: the partition function with positions held unpaired.  F[r * M + m] (kcal/mol) is the free energy of the
+ * ensemble of sequence r in which every position marked by mask m stays unpaired -- RNAfold -p with the hard constraint 'x' on
+ * those positions.  The opening energy of the region is Eopen = F[mask] - F[no mask] >= 0 and exp(-Eopen / kT) the probability
+ * that the whole region is unpaired.  A masked nucleotide is still that nucleotide next to a pair (mismatches, dangles and the
+ * special hairpins see its letter); it just cannot pair.
+ *   seqs    R*L chars, row-major, no terminators                                        in
+ *   M       masks, >= 1; every sequence is folded under every mask (R*M folds < 2^31)   in
+ *   nopair  M*L bytes, row-major, shared by all sequences: non-zero = stays unpaired    in
+ *   F       R*M doubles, row-major                                                      out
+ * L <= max_L; R and M are not limited by max_R: the R*M folds go through the workspace slots in chunks.  A NULL among seqs,
+ * nopair, F or M < 1 is DRNA_ERR_ARG; a bad letter DRNA_ERR_SEQUENCE (the message names the sequence), a partition function
+ * out of range DRNA_ERR_PF_RANGE, as for drna_self_dimer_batch.  The call needs no drna_set_targets().  Options
+ * (drna_set_option / drna_get_option): "access_lds" (default 1) folds sequences of at most "access_lds_max" (read-only)
+ * nucleotides with their tables in LDS, 0 sends every length to the general kernel -- two independent bodies whose results
+ * agree within 1e-9 kcal/mol, not bit for bit; "access_lds_calls" (read-only) counts the launches of the LDS kernel.  The host's
+ * bound is measured (the LDS kernel loses beyond it); "access_lds" = 2 sends every length the kernel holds,
+ * "access_lds_kernel_max" (read-only), to the LDS kernel -- for tests and timing.
+ * drna_last_access_timing: device ms of the last call's launches, summed over its chunks.
+ * New symbols: no existing signature or buffer changes, DRNA_ABI_VERSION stays 3.
+ */
+int drna_pf_unpaired_batch(drna_engine *e, int R, int L, const char *seqs, int M, const unsigned char *nopair, double *F);
+int drna_last_access_timing(const drna_engine *e, float *ms);
+
 /* device ms summed over the drna_score_batch[_device] calls since the last reset: out[0..3] as drna_last_timing, out[4] = number
  * of calls; out may be NULL (reset only).  Lets a caller time a loop of calls without a query per call. */
 int drna_timing_sums(drna_engine *e, double out[5], int reset);

@@ -8,6 +8,9 @@ same letters read as single strands of 200.
 `mea` (kept as profiles/mea.json): MEA and centroid structures (drna_mea_structures_batch) at R = 64 x L = 36, 100, 200, 400 and pairs
 of 30+27 and 100+100: the inside, outside and MEA launches of the same call, the MEA launch with M in LDS and in the workspace
 where the length allows both, and the candidates per column the pruning leaves.
+`access` (only when named; kept as profiles/access.json): the partition function with positions held unpaired
+(drna_pf_unpaired_batch) -- the masked general kernel beside the unmasked pf_kernel, the general kernel against the LDS kernel
+over the lengths the latter holds, one accessibility profile of 1,930 folds, and what the design term costs per iteration.
 `puzzle_set` (only when named; minutes): the Eterna100 set as a design run, lock-step batch against one puzzle after the other.
 `puzzle_set_aux` (only when named): the same pair for the puzzles of at most 200 nt with -nd on, and with an Edef term added."""
 import json
@@ -401,12 +404,112 @@ def puzzle_set_aux():
     return out
 
 
+ACCESS_ROUNDS = 9            # per figure: one warm-up round, then the median, lowest and highest of the others
+ACCESS_TARGETS = {36: ND_TARGET, 200: "." * 20 + ND_TARGET + "." * 30 + "((((((((....))))))))" + "." * 38 + ND_TARGET + "." * 20}
+
+
+def _spread(values):
+    v = np.array(values[1:], dtype=np.float64)
+    return {"median_ms": float(np.median(v)), "min_ms": float(v.min()), "max_ms": float(v.max())}
+
+
+def access():
+    """Device times (events; drna_last_access_timing) of drna_pf_unpaired_batch at R = 64, M = 1, random ACGU sequences, a random
+    mask of 8 positions, the paths alternating round by round in one process:
+      general_vs_unmasked   pf_kernel<1024, true> (option access_lds = 0) beside the unmasked pf_kernel<1024> (the inside launch of
+                            drna_ensemble_defect_batch with edef_lds = 0) at 36, 100, 200 and 400 nt
+      lds_vs_general        access_lds_kernel (option access_lds = 2: whatever the host's bound) against pf_kernel<1024, true> at
+                            24, 36, 48, 64, 80 nt and the kernel's bound: the table that fixes ACCESS_LDS_HOST_MAX
+      profile               ONE call of 10 sequences x 200 nt x every window of 8 (1,930 folds) on an engine of 64 slots
+      design_term           run_design_fast(native_loop=False), 64 replicas x 36 and 200 nt: wall ms per iteration with and without
+                            an >accessible region of 8 nt, and the device ms of the fused launch that gives Epf beside the masked fill"""
+    from desirna_amd import design
+    rng = np.random.default_rng(20261)
+    R = 64
+    out = {"general_vs_unmasked": {}, "lds_vs_general": {}, "design_term": {}}
+
+    def shape(L, lds_too, plain_too):
+        seqs = ["".join(rng.choice(list("ACGU"), L)) for _ in range(R)]
+        mask = np.zeros((1, L), dtype=np.uint8)
+        mask[0, rng.choice(L, 8, replace=False)] = 1
+        eng = E.Engine(max_R=R, max_L=L, device=0)
+        eng.set_targets(["." * L])
+        eng.set_option("edef_lds", 0)
+        t = {"general": [], "lds": [], "unmasked": []}
+        for _ in range(ACCESS_ROUNDS):
+            eng.set_option("access_lds", 0)
+            eng.unpaired_free_energy(seqs, mask)
+            t["general"].append(eng.last_access_timing())
+            if lds_too:
+                eng.set_option("access_lds", 2)            # (2: beyond the host's bound, up to the kernel's)
+                c0 = eng.get_option("access_lds_calls")
+                eng.unpaired_free_energy(seqs, mask)
+                assert eng.get_option("access_lds_calls") == c0 + 1
+                t["lds"].append(eng.last_access_timing())
+            if plain_too:
+                eng.ensemble_defect(seqs)
+                t["unmasked"].append(eng.last_edef_timing()["inside"])
+        eng.close()
+        return {k: _spread(v) for k, v in t.items() if v}
+
+    for L in (36, 100, 200, 400):
+        out["general_vs_unmasked"]["R%d_L%d" % (R, L)] = shape(L, False, True)
+    eng = E.Engine(max_R=1, max_L=8, device=0)
+    out["access_lds_max_option"], kernel_max = eng.get_option("access_lds_max"), eng.get_option("access_lds_kernel_max")
+    eng.close()
+    for L in sorted({24, 36, 48, 64, 80, kernel_max}):
+        out["lds_vs_general"]["R%d_L%d" % (R, L)] = shape(L, True, False)
+    # one accessibility profile
+    L, W, n_seq = 200, 8, 10
+    seqs = ["".join(rng.choice(list("ACGU"), L)) for _ in range(n_seq)]
+    masks = np.zeros((L - W + 1, L), dtype=np.uint8)
+    for a in range(L - W + 1):
+        masks[a, a:a + W] = 1
+    eng = E.Engine(max_R=R, max_L=L, device=0)
+    ms, wall = [], []
+    for _ in range(4):
+        t0 = time.perf_counter()
+        eng.unpaired_free_energy(seqs, masks)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(eng.last_access_timing())
+    slots = eng.get_option("workspace_slots")
+    folds = n_seq * masks.shape[0]
+    out["profile"] = {"folds": folds, "workspace_slots": slots, "chunks": -(-folds // slots), "device": _spread(ms), "wall": _spread(wall)}
+    eng.close()
+    # the term inside a design
+    for L, target in ACCESS_TARGETS.items():
+        assert len(target) == L
+        free = target.index("....") if L == 36 else 0
+        region = "." * free + "x" * 8 + "." * (L - free - 8)
+        eng = E.Engine(max_R=R, max_L=L, device=0)
+        v = {}
+        for key, acc in (("plain", None), ("region", region), ("plain_again", None)):
+            inp = SimpleNamespace(name="acc", sec_struct=target, seq_restr="N" * L, seed_seq=None, alt_sec_struct=None, alt_sec_structs=None,
+                                  accessible=acc)
+            t0 = time.perf_counter()
+            res = design.run_design_fast(inp, engine=eng, replicas=R, exchange=20, steps=3, seed=3, timelimit=600, native_loop=False,
+                                         keep_records=False)
+            v["iter_wall_ms_" + key] = (time.perf_counter() - t0) * 1e3 / (res["steps"] * 20 + 1)
+        seqs = ["".join(rng.choice(list("ACGU"), L)) for _ in range(R)]
+        fused, masked = [], []
+        for _ in range(ACCESS_ROUNDS):
+            eng.score_batch(seqs)
+            fused.append(eng.last_timing()["total"])
+            eng.unpaired_free_energy(seqs, region)
+            masked.append(eng.last_access_timing())
+        v["score_batch_device"], v["masked_fill_device"] = _spread(fused), _spread(masked)
+        v["masked_over_score_batch"] = v["masked_fill_device"]["median_ms"] / v["score_batch_device"]["median_ms"]
+        out["design_term"]["R%d_L%d" % (R, L)] = v
+        eng.close()
+    return out
+
+
 def main(names):
     if names == ["puzzle_set_profile"]:                      # the child of puzzle_set: the lock-step run alone, profile lines on stderr
         _lockstep(_puzzle_inputs())
         return
     out = {}
-    whole_runs = {"puzzle_set": puzzle_set, "puzzle_set_aux": puzzle_set_aux}
+    whole_runs = {"puzzle_set": puzzle_set, "puzzle_set_aux": puzzle_set_aux, "access": access}
     if set(names) & set(whole_runs):
         for n in names:
             if n in whole_runs:
