@@ -435,6 +435,8 @@ extern "C" void drna_destroy(drna_engine* e) {
 
 extern "C" int drna_abi_version(void) { return DRNA_ABI_VERSION; }
 
+static int poison_scratch(drna_engine* e, int byte);      // option "poison", at the end of the file
+
 extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!e || !name) return DRNA_ERR_ARG;
   if (!strcmp(name, "dual") || !strcmp(name, "strips") || !strcmp(name, "pf_helper") || !strcmp(name, "fused")) { e->fallback_streak = 0; e->solo_left = 0; }
@@ -453,6 +455,10 @@ extern "C" int drna_set_option(drna_engine* e, const char* name, int value) {
   if (!strcmp(name, "mfe_fark_min_strips")) { e->mfe_fark_min_strips = value < 1 ? 1 : value; return DRNA_OK; }
   if (!strcmp(name, "mfe_split")) { e->mfe_split = value < 1 ? 1 : value > 8 ? 8 : value; return DRNA_OK; }
   if (!strcmp(name, "debug_epoch")) { e->sflags.epoch = e->dflags.epoch = e->pflags.epoch = value; return DRNA_OK; }     // tests: jump near the reset point
+  if (!strcmp(name, "poison")) {                                                                                         // tests: a stale read shows in the values
+    if (value < 0 || value > 255) { e->err = "drna_set_option: poison takes a byte, 0 .. 255"; return DRNA_ERR_ARG; }
+    return poison_scratch(e, value);
+  }
   e->err = std::string("drna_set_option: unknown option ") + name;
   return DRNA_ERR_ARG;
 }
@@ -2973,4 +2979,60 @@ extern "C" int drna_mc_run_ragged(MC_RAGGED_PARAMS) { return mc_run_ragged_impl(
 
 extern "C" int drna_mc_run_ragged_nd(MC_RAGGED_PARAMS, double* subopt_e) {
   return mc_run_ragged_impl("drna_mc_run_ragged_nd", MC_RAGGED_ARGS, true, subopt_e);
+}
+
+// ---------------------------------------------------------------- option "poison" (tests)
+
+// Option "poison" (tests): every scratch buffer that exists right now filled with one byte, the streams drained before and after.
+// Scratch is what every call writes before it reads (the table of buffers): the workspaces, the result and staging
+// buffers, the status words, the exchange rows and records, the ragged descriptors and the masks.  State stays as it is: the
+// parameter tables and plans, installed targets (d_pt, d_rpt, d_rpt_off), the all-unpaired table d_mea_pt (written once), the
+// motifs, and the three sets of hand-over flags, whose epoch rule is their own protocol (a poisoned flag is a wait that never ends).
+static int poison_scratch(drna_engine* e, int byte) {
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const int ld = e->max_L + 2;
+  const size_t R = (size_t)e->max_R, L = (size_t)e->max_L, slots = (size_t)e->ws_slots;
+  const size_t kb_stride = (size_t)3 * 8 * ld * ld + (size_t)cofold_kbest_ws_extra(8, ld);        // (ranked_structs_batch)
+  const size_t xrows = (size_t)2 * (MFE_FAST_NMAX + 2) * XP;                                      // (prepare_folds)
+  const struct { void* p; size_t bytes; } dev[] = {
+      {e->d_ws_mfe, mfe_ws_stride(ld) * sizeof(int32_t) * slots},
+      {e->d_ws_pf, pf_ws_stride(ld) * sizeof(double) * slots},
+      {e->d_ws_out, (size_t)outside_ws_stride(ld) * sizeof(double) * slots},
+      {e->d_ws_kb, kb_stride * sizeof(int32_t) * e->kb_chunk},
+      {e->d_kbE, (size_t)8 * e->kb_chunk * sizeof(int32_t)},
+      {e->d_kbss, (size_t)8 * e->kb_chunk * L},
+      {e->d_q5s, slots * ld * sizeof(double)},
+      {e->d_cocols, slots * CO_COLS * ld * sizeof(double)},
+      {e->d_seqs, R * L},
+      {e->d_ss, R * L},
+      {e->d_Epf, R * sizeof(double)},
+      {e->d_Emfe, R * sizeof(int32_t)},
+      {e->d_Ed, R * std::max(1, e->n_targets) * sizeof(int32_t)},
+      {e->d_edef, R * sizeof(double)},
+      {e->d_F4, 4 * R * sizeof(double)},
+      {e->d_xs, (size_t)e->dual_cap * 256 * sizeof(int32_t)},
+      {e->d_xa_mfe, (size_t)e->dual_cap * xrows * sizeof(int32_t)},
+      {e->d_xb_mfe, (size_t)e->dual_cap * xrows * sizeof(int32_t)},
+      {e->d_srec, (size_t)e->srec_stride * R * sizeof(int32_t)},
+      {e->d_rg, (size_t)RG_BLOCKS * 7 * R * sizeof(int)},
+      {e->d_nopair, e->nopair_cap},
+  };
+  for (const auto& b : dev)
+    if (b.p && b.bytes) HIP_TRY(hipMemset(b.p, byte, b.bytes));
+  HIP_TRY(hipDeviceSynchronize());        // (the memsets run on the null stream, the kernels on non-blocking streams of their own)
+  // host-mapped: the status words, the staging buffers and the fused launch's clocks
+  const struct { void* p; size_t bytes; } host[] = {
+      {e->h_status, 2 * R * sizeof(int32_t)},
+      {e->hm_seqs, R * L},
+      {e->hm_ss, R * L},
+      {e->hm_Epf, R * sizeof(double)},
+      {e->hm_Emfe, R * sizeof(int32_t)},
+      {e->hm_Ed, e->hm_Ed_cap * sizeof(int32_t)},
+      {e->hm_F4, 4 * R * sizeof(double)},
+      {e->h_clk, (size_t)2 * e->clk_cap * sizeof(long long)},
+  };
+  for (const auto& b : host)
+    if (b.p && b.bytes) memset(b.p, byte, b.bytes);
+  return DRNA_OK;
 }

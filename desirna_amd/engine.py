@@ -232,7 +232,8 @@ class Engine:
         _LIVE.add(self)
 
     def set_option(self, name, value):
-        """Engine option (``drna_set_option``): ``"dual"`` = fold small batches with two workgroups per sequence (default on)."""
+        """Engine option (``drna_set_option``): ``"dual"`` = fold small batches with two workgroups per sequence (default on).
+        ``"poison"`` (tests) fills every scratch buffer the engine holds with the byte `value`; no result may depend on it."""
         self._check(self._L.drna_set_option(self._h, name.encode(), int(value)))
 
     def get_option(self, name):
@@ -614,6 +615,12 @@ class Engine:
         self._check(self._L.drna_ensemble_defect_batch(self._h, R, L, seqs_u8.ctypes.data_as(C.c_char_p), ed.ctypes.data,
                                                        bpp.ctypes.data if want_bpp else None))
         return (ed, bpp) if want_bpp else ed
+
+    def ensemble_defect_device(self, d_seqs, R, L, d_edef, d_bpp=None):
+        """Device-resident variant of :meth:`ensemble_defect_arrays` (drna_ensemble_defect_batch_device): raw device pointers to
+        the R x L letters, to float64[R] for the defects and, optionally, to the (R, L+1, L+1) matrices, which the caller has
+        ZEROED (the outside pass writes the pairs only).  The caller must have made the inputs visible before the call."""
+        self._check(self._L.drna_ensemble_defect_batch_device(self._h, int(R), int(L), d_seqs, d_edef, d_bpp))
 
     def ensemble_defect_ragged(self, seqs, target_of):
         """String form of :meth:`ensemble_defect_ragged_arrays` (seqs: strings of different lengths)."""

@@ -355,6 +355,9 @@ int drna_last_edef_timing(const drna_engine *e, float out[2]);
  * bit-identical either way.  One strand: the fused kernel sums in another order than outside_kernel, so edef and bpp move in
  * the last bits with the option (about 1e-15; both within 1e-10 of the reference), as Epf does with "strips".  The read-only
  * counter "edef_lds_calls" counts the launches of the fused kernel.
+ * "poison" (tests; value = a byte, 0 .. 255): drains the engine's streams, fills every scratch buffer that exists at that moment
+ * with the byte (workspaces, result and staging buffers, status words, exchange rows; not the tables, installed targets, motifs
+ * or hand-over flags: DESIGN.md 2.1 has the table) and drains again.  No call's results may depend on it.
  */
 int drna_set_option(drna_engine *e, const char *name, int value);
 
